@@ -17,6 +17,14 @@ N>1: one process per GPU under torch.distributed.run.  The SAME problem is cut i
 path of include/pgx.h: RCCL halo exchange of ghost vertex rows + packed all-reduces), so the numbers at N = 1, 2, 4, 8
 are a strong-scaling series of one fixed workload; `--replicas` runs N independent solves instead (and says so).
 DESIGN.md section 7.
+
+A plain run sets up, warms up, times the K steps and prints the result line (`roofline` is then null).  `--full` adds
+the secondary figures after the timed steps: the roofline / V-cycle microbenchmarks (`roofline`, `roofline_csr`,
+`roofline_dominant`, `vcycle_parts`), the profiled solve of the sparse-LU workloads and the CPU baseline
+(`cpu_baseline`, unless --no-cpu-baseline).  `--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy (float64): ex01 `u`, `psi` and `history` (one row per proximal iteration, the columns of
+obstacle.COLUMNS); ex06 `u`, `latent`, ex02 `u`, `psi`, both with `newton_per_lvpp_step`.  A field that does not fit in
+the 64 MB budget is a sample at seeded positions, listed in <name>_index.npy.
 """
 import argparse
 import json
@@ -167,6 +175,31 @@ def host_info():
 
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X fp64 matrix peak (dense)
 
+DUMP_BUDGET_BYTES = 56_000_000  # --dump-outputs: the large arrays together (the small ones add a few kB; 64 MB is the cap)
+DUMP_SEED = 20260101
+
+
+def dump_outputs(directory, large, small):
+    """--dump-outputs: what the timed path returned in its last step, as DIR/<name>.npy in float64.  `large` (the fields) are
+    written whole, in the order given, while they fit in DUMP_BUDGET_BYTES; a field that does not is replaced by a sample at
+    seeded positions - the same for every run with the same arguments - and DIR/<name>_index.npy holds those positions.
+    `small` (iteration histories) are written whole."""
+    os.makedirs(directory, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in large.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.nbytes <= left:
+            np.save(os.path.join(directory, name + ".npy"), a)
+            left -= a.nbytes
+            continue
+        k = left // 16  # 8 B per sampled value + 8 B per position
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=k, replace=False))
+        np.save(os.path.join(directory, name + ".npy"), a[idx])
+        np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+        left -= 16 * k
+    for name, a in small.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
+
 
 def bench_lu_workload(args, rank, world, local_rank, dist, backend):
     """BASELINE configs 4 (ex 06, gradient constraint) and 5 (ex 02, Signorini): a step = one full LVPP solve from the
@@ -305,33 +338,51 @@ def bench_lu_workload(args, rank, world, local_rank, dist, backend):
     dt = time.perf_counter() - t0
     if dist is not None:
         dt, _, _ = reduce_over_ranks(dist, dt, newton_total, 0, "cuda" if backend == "nccl" else "cpu")
-    # roofline of the dominant kernel: one more solve with per-phase HIP-event timing (adds syncs: not part of `value`)
-    problem.profile(True)
-    its_p = one_step()
-    prof = problem.profile(False)
-    st = problem.lu_stats()
-    # ALGORITHMIC flops (the unpadded multifrontal factorisation) decide `achieved`; the level-batched kernels execute
-    # the padded count (fronts of a level share one shape), reported beside it
-    # SYMMETRIC mode (round 5: the Newton matrices of ex 06 and - with the latent rows negated - ex 02 are symmetric): the factorisation
-    # is L D L^T in LU clothing and its flop count HALF the LU's (n^3 / 3 against 2 n^3 / 3 per dense front); `achieved` is priced on
-    # that count, the LU-equivalent rate is reported beside it
-    sym = bool(st.get("symmetric"))
-    fl = 0.5 if sym else 1.0
-    tflops = fl * st["flops"] * sum(its_p) / (prof["lu_factor"] * 1e-3) / 1e12
-    tflops_exec = fl * st["flops_padded"] * sum(its_p) / (prof["lu_factor"] * 1e-3) / 1e12
-    # HBM bytes per factorisation from the committed rocprofv3 --pmc profile of the same workload (tools/profile_nd_traffic.sh:
-    # FETCH_SIZE and WRITE_SIZE in separate passes, FETCH_SIZE doubled per MI355X_MICROARCH.md); its library hash travels with it
-    tj = _ladder("r05_nd_traffic_ex06_1024.json" if args.workload == "ex06" else "r05_nd_traffic_ex02_70.json")
-    traffic = traffic_src = None
-    default_size = (args.workload == "ex06" and N == 1024) or (args.workload != "ex06" and n == 70)
-    if tj and tj.get("per_factorisation") and default_size and world == 1:
-        traffic = tj["per_factorisation"]["traffic_GB"] * 1e9
-        traffic_src = {"file": "profiles/" + ("r05_nd_traffic_ex06_1024.json" if args.workload == "ex06" else "r05_nd_traffic_ex02_70.json"),
-                       "libpgx_sha256_16": tj.get("libpgx_sha256_16"), "per": "factorisation (all k_nd_* kernels of pgx_nd_factor)",
-                       "traffic_over_arena": tj["per_factorisation"].get("traffic_over_arena"),
-                       "note": "FETCH_SIZE counts every read that leaves an XCD's L2, Infinity-Cache hits included; about two thirds of "
-                               "the total are compulsory for a multifrontal factorisation (factors written once, every Schur block "
-                               "written once and gathered once per tree level), the rest panel re-reads of the blocked elimination"}
+    # the iterate the last timed solve left (the caller's get_state()), read before anything else runs on the handle
+    x_last = problem.get_state() if args.dump_outputs else None
+    roofline = None
+    if args.full:
+        # roofline of the dominant kernel: one more solve with per-phase HIP-event timing (adds syncs: not part of `value`)
+        problem.profile(True)
+        its_p = one_step()
+        prof = problem.profile(False)
+        st = problem.lu_stats()
+        # ALGORITHMIC flops (the unpadded multifrontal factorisation) decide `achieved`; the level-batched kernels execute
+        # the padded count (fronts of a level share one shape), reported beside it
+        # SYMMETRIC mode (round 5: the Newton matrices of ex 06 and - with the latent rows negated - ex 02 are symmetric): the factorisation
+        # is L D L^T in LU clothing and its flop count HALF the LU's (n^3 / 3 against 2 n^3 / 3 per dense front); `achieved` is priced on
+        # that count, the LU-equivalent rate is reported beside it
+        sym = bool(st.get("symmetric"))
+        fl = 0.5 if sym else 1.0
+        tflops = fl * st["flops"] * sum(its_p) / (prof["lu_factor"] * 1e-3) / 1e12
+        tflops_exec = fl * st["flops_padded"] * sum(its_p) / (prof["lu_factor"] * 1e-3) / 1e12
+        # HBM bytes per factorisation from the committed rocprofv3 --pmc profile of the same workload (tools/profile_nd_traffic.sh:
+        # FETCH_SIZE and WRITE_SIZE in separate passes, FETCH_SIZE doubled: gfx950 tallies a 128-B request as 64 B); its library hash
+        # travels with it
+        tj = _ladder("r05_nd_traffic_ex06_1024.json" if args.workload == "ex06" else "r05_nd_traffic_ex02_70.json")
+        traffic = traffic_src = None
+        default_size = (args.workload == "ex06" and N == 1024) or (args.workload != "ex06" and n == 70)
+        if tj and tj.get("per_factorisation") and default_size and world == 1:
+            traffic = tj["per_factorisation"]["traffic_GB"] * 1e9
+            traffic_src = {"file": "profiles/" + ("r05_nd_traffic_ex06_1024.json" if args.workload == "ex06" else "r05_nd_traffic_ex02_70.json"),
+                           "libpgx_sha256_16": tj.get("libpgx_sha256_16"), "per": "factorisation (all k_nd_* kernels of pgx_nd_factor)",
+                           "traffic_over_arena": tj["per_factorisation"].get("traffic_over_arena"),
+                           "note": "FETCH_SIZE counts every read that leaves an XCD's L2, Infinity-Cache hits included; about two thirds of "
+                                   "the total are compulsory for a multifrontal factorisation (factors written once, every Schur block "
+                                   "written once and gathered once per tree level), the rest panel re-reads of the blocked elimination"}
+        roofline = {"kernel": "k_nd_gemm8 / k_nd_gemm<2> inside pgx_nd_factor (fp64 MFMA GEMM of the multifrontal LU; the figure is "
+                              "the WHOLE factorisation: algorithmic flops of this rank / its device time - leaf fronts, frame "
+                              "assembly, diagonal blocks and panel solves included; the deep tree levels of 2-D problems are "
+                              "HBM-bound, DESIGN.md section 9)",
+                    "bound": "mfma", "achieved": tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+                    "factorisation": "L D L^T in LU clothing (pgx_nd_set_symmetric): half the LU's flops" if sym else "LU",
+                    "algorithmic_flops_per_factorisation": fl * st["flops"],
+                    "executed_flops_per_factorisation_padded": fl * st["flops_padded"], "executed_TFLOPs": tflops_exec,
+                    "lu_equivalent_TFLOPs": tflops / fl,
+                    "arena_GB": st["arena_doubles"] * 8 / 1e9,
+                    "lu_factor_ms_per_newton_step": prof["lu_factor"] / max(sum(its_p), 1),
+                    "lu_solve_ms_per_newton_step": prof["lu_solve"] / max(sum(its_p), 1)}
     out = None
     if rank == 0:
         out = {
@@ -344,21 +395,9 @@ def bench_lu_workload(args, rank, world, local_rank, dist, backend):
                        "parallelism": "single" if world == 1 else f"replicated iterate, sparse LU distributed over {world} ranks "
                                                                    "(one dissection subtree each, RCCL gather/scatter + all-reduce)"},
             "setup_s": t_setup,
-            "roofline": {"kernel": "k_nd_gemm8 / k_nd_gemm<2> inside pgx_nd_factor (fp64 MFMA GEMM of the multifrontal LU; the figure is "
-                                   "the WHOLE factorisation: algorithmic flops of this rank / its device time - leaf fronts, frame "
-                                   "assembly, diagonal blocks and panel solves included; the deep tree levels of 2-D problems are "
-                                   "HBM-bound, DESIGN.md section 9)",
-                         "bound": "mfma", "achieved": tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                         "factorisation": "L D L^T in LU clothing (pgx_nd_set_symmetric): half the LU's flops" if sym else "LU",
-                         "algorithmic_flops_per_factorisation": fl * st["flops"],
-                         "executed_flops_per_factorisation_padded": fl * st["flops_padded"], "executed_TFLOPs": tflops_exec,
-                         "lu_equivalent_TFLOPs": tflops / fl,
-                         "arena_GB": st["arena_doubles"] * 8 / 1e9,
-                         "lu_factor_ms_per_newton_step": prof["lu_factor"] / max(sum(its_p), 1),
-                         "lu_solve_ms_per_newton_step": prof["lu_solve"] / max(sum(its_p), 1)},
+            "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             steps, secs, what = cpu_leg(25.0)
             n_cpu = args.cpu_n // 4 if args.workload == "ex06" else 24
             n_gpu = N if args.workload == "ex06" else n
@@ -373,6 +412,8 @@ def bench_lu_workload(args, rank, world, local_rank, dist, backend):
             if ex:
                 ex["gpu_over_cpu"] = out["value"] / ex["value"]
                 out["cpu_baseline"]["at_workload"] = ex
+    # the state vector in its two blocks: ex 06 = [u (P2), latent (vector P1)], ex 02 = [u (3 x P1), psi (contact vertices)]
+    nu = (problem.n2 if args.workload == "ex06" else 3 * problem.nv) if args.dump_outputs else 0
     problem.close()
     if comm is not None:
         comm.free()
@@ -380,6 +421,9 @@ def bench_lu_workload(args, rank, world, local_rank, dist, backend):
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"u": x_last[:nu], "latent" if args.workload == "ex06" else "psi": x_last[nu:]},
+                         {"newton_per_lvpp_step": its})
         print(json.dumps(out))
 
 
@@ -456,7 +500,16 @@ def main():
     ap.add_argument("--watchdog", type=float, default=900.0, help="N>1: abort the process after this many seconds")
     ap.add_argument("--workload", choices=["ex01", "ex06", "ex02"], default="ex01",
                     help="ex01 = BASELINE metric (config 2); ex06 / ex02 = configs 4 / 5 through the sparse LU")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures after the timed steps: roofline / V-cycle microbenchmarks, the profiled LU solve "
+                         "and the CPU baseline (without it a run sets up, warms up, times --steps steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes the outputs of a single-GPU run (--gpus 1)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the launcher ourselves, as a CHILD process and before anything in
@@ -507,7 +560,7 @@ def main():
         return bench_lu_workload(args, rank, world, local_rank, dist, backend)
 
     from proximalgalerkin_amd import fem
-    from proximalgalerkin_amd.obstacle import run_outer_loop, setup_problem
+    from proximalgalerkin_amd.obstacle import COLUMNS, run_outer_loop, setup_problem
 
     S = SETTINGS[args.settings]
     N = args.n
@@ -571,16 +624,25 @@ def main():
     comm_counts = problem.comm_counts() if sharded else None  # collectives of the timed solves, this rank
     units = 1 if sharded else world  # solves per step over the whole job
     lin_its = problem.solver.getLinearSolveIterations()
+    outputs = None
+    if args.dump_outputs:  # what run_outer_loop hands its caller: the mixed iterate (u, psi) and the history of the last timed solve
+        nb = sol.function_space.block_size
+        xs = sol.x.array_r  # (read-only pull: the device copy stays the valid one)
+        outputs = ({"u": xs[:nb].copy(), "psi": xs[nb:].copy()},
+                   {"history": np.array([hist[c] for c in COLUMNS], dtype=np.float64).T})
 
-    # ---- roofline of the operator-apply kernel ("SpMV"): HIP events on the library's own stream ----
+    # ---- --full: roofline of the operator-apply kernel ("SpMV"): HIP events on the library's own stream ----
     # structured P1: the solver applies J matrix-free (k_st_spmv_r<true>: 57 B per vertex - the iterate is the float2 z_j the single-precision
     # cycle left; 65 B with an fp64 iterate); the block-CSR stream kernel (general
     # meshes, P2; 232 B per P1 row) is timed beside it on the same matrix and reported as `roofline_csr`
-    problem.assemble_jacobian()  # Jacobian at the final iterate
-    spmv_kind = problem.spmv_select()
+    micro = args.full and not args.solves_only
+    spmv_kind = None
+    if args.full:
+        problem.assemble_jacobian()  # Jacobian at the final iterate
+        spmv_kind = problem.spmv_select()
     spmv_ms = spmv_bytes = csr_ms = csr_bytes = None
     cold_ms, cold_bytes = {}, None
-    if not args.solves_only:
+    if micro:
         spmv_ms, spmv_bytes = problem.spmv_bench(reps=20)
         cold_ms[spmv_kind], cold_bytes = problem.spmv_bench_cold(reps=20)  # (the cold pass applies to an fp64 vector: its own byte count)
         if spmv_kind != 0:
@@ -592,7 +654,7 @@ def main():
             csr_ms, csr_bytes = spmv_ms, spmv_bytes
     n = msh.num_vertices
     smoother = None
-    if not sharded and args.degree == 1 and not args.solves_only:
+    if not sharded and args.degree == 1 and micro:
         sm_ms, sm_bytes = problem.smoother_bench(reps=50)
         # the finest level's smoother launch of the single-precision V-cycle (pgx_mg32.hip): D as one float4, vectors as float2 -
         # 40 B per vertex + the coarse correction; with PGX_MG_F32=0 the fp64 kernel k_st_smoothR (84 B per vertex) is timed instead
@@ -610,7 +672,7 @@ def main():
                     "bound": "hbm", "achieved": sm_bytes / (sm_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                     "frac": sm_bytes / (sm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": sm_traffic, "traffic_source": sm_src,
                     "algorithmic_bytes_per_launch": sm_bytes, "avg_launch_ms": sm_ms}
-    if not sharded and args.degree == 2 and not args.solves_only:
+    if not sharded and args.degree == 2 and micro:
         try:  # P2: the patch sweep of the two-level cycle (k_patch_apply + k_patch_edges) on the inverses of the final Jacobian
             sm_ms, sm_bytes = problem.smoother_bench(reps=20)
             p_traffic = p_src = None
@@ -631,7 +693,7 @@ def main():
             smoother = None
             sys.stderr.write(f"bench.py: no roofline_dominant for this P2 handle: {e}\n")
     coarse = None
-    if not sharded and args.degree == 1 and not args.solves_only:
+    if not sharded and args.degree == 1 and micro:
         # the part of one V-cycle on the levels of at most 513^2 vertices, launches back to back
         lv, part = 0, []
         while True:
@@ -751,7 +813,7 @@ def main():
             out["vcycle_parts"] = coarse
         if prof:
             out["phase_ms"] = prof
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # degree 2: the P2 problem on half the cells per side has the node count of the P1 sample (a `--degree 2`
             # line must not carry a P1 baseline)
             cpu_n = min(args.cpu_n, N) if args.degree == 1 else min(args.cpu_n // 2, N)
@@ -809,6 +871,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if outputs:
+            dump_outputs(args.dump_outputs, *outputs)
         print(json.dumps(out))
 
 

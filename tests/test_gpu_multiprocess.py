@@ -44,7 +44,7 @@ def _single(args):
 
 @pytest.mark.parametrize("nproc,cells", [(2, 256), (4, 512)])
 def test_sharded_obstacle_solve_across_processes(require_gpu, nproc, cells):
-    args = ["--cells", str(cells), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--watchdog", "500"]
+    args = ["--cells", str(cells), "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--watchdog", "500"]
     d = _launch(nproc, args)
     d1 = _single(args)
     assert d["n_gpus"] == nproc and d["scaling"] == "strong"
@@ -58,7 +58,8 @@ def test_sharded_obstacle_solve_across_processes(require_gpu, nproc, cells):
 
 @pytest.mark.parametrize("workload,cells", [("ex02", 10), ("ex06", 48)])
 def test_distributed_lu_workloads_across_processes(require_gpu, workload, cells):
-    args = ["--workload", workload, "--cells", str(cells), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--watchdog", "500"]
+    args = ["--workload", workload, "--cells", str(cells), "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--watchdog",
+            "500"]
     d = _launch(2, args)
     d1 = _single(args)
     assert d["n_gpus"] == 2

@@ -222,7 +222,7 @@ def test_bench_sharded_branch_runs_over_rccl_with_one_rank(require_gpu):
     env = dict(os.environ, BENCH_FORCE_SHARDED="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(port))
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--cells", "256", "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--watchdog", "300"]
+           "--full", "--no-cpu-baseline", "--watchdog", "300"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -16,7 +16,7 @@ for spec in sys.argv[1:]:
     for kv in filter(None, env_s.split(",")):
         k, v = kv.split("=", 1)
         env[k] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "5", "--warmup", "2"] + args_s.split()
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "5", "--warmup", "2"] + args_s.split()
     r = subprocess.run(cmd, env=env, capture_output=True, text=True)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode or not lines:

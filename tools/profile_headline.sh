@@ -13,7 +13,7 @@ BENCH="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --solves-only"
 for what in "$@"; do
   case $what in
     stats)
-      rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/stats.log 2>&1 || exit 1
+      rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/stats.log 2>&1 || exit 1
       cp $(find $OUT/stats -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.csv
       rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o t -- $BENCH > $OUT/trace.log 2>&1 || exit 1
       python3 tools/trace_by_grid.py $OUT/trace > $OUT/trace_by_level.txt; rm -rf $OUT/trace ;;

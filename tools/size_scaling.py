@@ -11,7 +11,7 @@ for n in sizes:
     row = [f"{n}^2"]
     for st in ("A", "B"):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--cells", str(n), "--settings", st, "--steps", "2", "--warmup", "1",
-                            "--no-cpu-baseline"], capture_output=True, text=True)
+                            "--full", "--no-cpu-baseline"], capture_output=True, text=True)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         if "Memory access fault" in r.stderr:
             print(n, st, "GPU FAULT", r.stderr[-300:])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Durations of the operator-apply kernel INSIDE the solves vs in pgx_spmv_bench's back-to-back loop, from a rocprofv3 kernel
-trace of `bench.py` (the loop's launches are the trailing run of consecutive launches of the kernel):
+trace of `bench.py --full` (the loop's launches are the trailing run of consecutive launches of the kernel):
     python tools/spmv_in_solve.py <dir or kernel_trace.csv> [kernel substring, default k_st_spmv_r]"""
 import csv
 import glob
