@@ -284,23 +284,8 @@ SYMBOLS = [
     ("pgx_gc_create_dist", C.c_int, [C.POINTER(pgx_mesh), C.POINTER(pgx_gc_problem), _COMM, C.c_int, C.POINTER(_H)]),
     ("pgx_gc_lu_stats", C.c_int, [_H, C.POINTER(pgx_nd_stats)]),
     ("pgx_gc_lu_is_symmetric", C.c_int, [_H]),
-    ("pgx_gc_destroy", None, [_H]),
-    ("pgx_gc_last_error", C.c_char_p, [_H]),
     ("pgx_gc_num_dofs", C.c_int, [_H, c_int64_p]),
-    ("pgx_gc_set_state", C.c_int, [_H, c_double_p]),
-    ("pgx_gc_get_state", C.c_int, [_H, c_double_p]),
-    ("pgx_gc_set_prev", C.c_int, [_H, c_double_p]),
-    ("pgx_gc_get_prev", C.c_int, [_H, c_double_p]),
-    ("pgx_gc_advance_prev", C.c_int, [_H]),
-    ("pgx_gc_set_alpha", C.c_int, [_H, C.c_double]),
-    ("pgx_gc_residual", C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
-    ("pgx_gc_jacobian_fill", C.c_int, [_H, c_double_p]),
-    ("pgx_gc_csr_export", C.c_int, [_H, c_int64_p, c_int64_p, c_int32_p, c_int32_p, c_double_p]),
-    ("pgx_gc_spmv", C.c_int, [_H, c_double_p, c_double_p]),
-    ("pgx_gc_newton_solve", C.c_int,
-     [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pgx_gc_l2_increment", C.c_int, [_H, c_double_p]),
-    ("pgx_gc_profile", C.c_int, [_H, C.c_int, c_double_p]),
     # example 02: Signorini contact (include/pgx_sg.h)
     ("pgx_sg_create", C.c_int, [C.POINTER(pgx_sg_mesh), C.POINTER(pgx_sg_problem), C.c_int, C.POINTER(_H)]),
     ("pgx_sg_create_dist", C.c_int, [C.POINTER(pgx_sg_mesh), C.POINTER(pgx_sg_problem), _COMM, C.c_int, C.POINTER(_H)]),
@@ -308,64 +293,37 @@ SYMBOLS = [
     ("pgx_sg_partition_info", C.c_int, [_H, c_int64_p, c_int64_p]),
     ("pgx_sg_lu_stats", C.c_int, [_H, C.POINTER(pgx_nd_stats)]),
     ("pgx_sg_lu_is_symmetric", C.c_int, [_H]),
-    ("pgx_sg_destroy", None, [_H]),
-    ("pgx_sg_last_error", C.c_char_p, [_H]),
     ("pgx_sg_num_dofs", C.c_int, [_H, c_int64_p, c_int64_p]),
     ("pgx_sg_contact_vertices", C.c_int, [_H, c_int32_p]),
-    ("pgx_sg_set_state", C.c_int, [_H, c_double_p]),
-    ("pgx_sg_get_state", C.c_int, [_H, c_double_p]),
-    ("pgx_sg_set_prev", C.c_int, [_H, c_double_p]),
-    ("pgx_sg_get_prev", C.c_int, [_H, c_double_p]),
-    ("pgx_sg_advance_prev", C.c_int, [_H]),
-    ("pgx_sg_set_alpha", C.c_int, [_H, C.c_double]),
-    ("pgx_sg_residual", C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
-    ("pgx_sg_jacobian_fill", C.c_int, [_H, c_double_p]),
-    ("pgx_sg_csr_export", C.c_int, [_H, c_int64_p, c_int64_p, c_int32_p, c_int32_p, c_double_p]),
-    ("pgx_sg_spmv", C.c_int, [_H, c_double_p, c_double_p]),
-    ("pgx_sg_newton_solve", C.c_int,
-     [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pgx_sg_u_increment", C.c_int, [_H, c_double_p]),
-    ("pgx_sg_profile", C.c_int, [_H, C.c_int, c_double_p]),
     # example 05: thermoforming QVI (include/pgx_qvi.h)
     ("pgx_qvi_create", C.c_int, [C.POINTER(pgx_mesh), C.POINTER(pgx_qvi_problem), C.c_int, C.POINTER(_H)]),
-    ("pgx_qvi_destroy", None, [_H]),
-    ("pgx_qvi_last_error", C.c_char_p, [_H]),
     ("pgx_qvi_num_dofs", C.c_int, [_H, c_int64_p]),
-    ("pgx_qvi_set_state", C.c_int, [_H, c_double_p]),
-    ("pgx_qvi_get_state", C.c_int, [_H, c_double_p]),
-    ("pgx_qvi_set_prev", C.c_int, [_H, c_double_p]),
-    ("pgx_qvi_get_prev", C.c_int, [_H, c_double_p]),
-    ("pgx_qvi_advance_prev", C.c_int, [_H]),
-    ("pgx_qvi_set_alpha", C.c_int, [_H, C.c_double]),
-    ("pgx_qvi_residual", C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
-    ("pgx_qvi_jacobian_fill", C.c_int, [_H, c_double_p]),
-    ("pgx_qvi_csr_export", C.c_int, [_H, c_int64_p, c_int64_p, c_int32_p, c_int32_p, c_double_p]),
-    ("pgx_qvi_spmv", C.c_int, [_H, c_double_p, c_double_p]),
-    ("pgx_qvi_newton_solve", C.c_int,
-     [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pgx_qvi_h1_increment", C.c_int, [_H, c_double_p]),
-    ("pgx_qvi_profile", C.c_int, [_H, C.c_int, c_double_p]),
     # example 08: intersecting constraints (include/pgx_ic.h)
     ("pgx_ic_create", C.c_int, [C.POINTER(pgx_ic_problem), C.c_int, C.POINTER(_H)]),
-    ("pgx_ic_destroy", None, [_H]),
-    ("pgx_ic_last_error", C.c_char_p, [_H]),
     ("pgx_ic_num_dofs", C.c_int, [_H, c_int64_p]),
-    ("pgx_ic_set_state", C.c_int, [_H, c_double_p]),
-    ("pgx_ic_get_state", C.c_int, [_H, c_double_p]),
-    ("pgx_ic_set_prev", C.c_int, [_H, c_double_p]),
-    ("pgx_ic_get_prev", C.c_int, [_H, c_double_p]),
-    ("pgx_ic_advance_prev", C.c_int, [_H]),
-    ("pgx_ic_set_alpha", C.c_int, [_H, C.c_double]),
     ("pgx_ic_set_phi", C.c_int, [_H, c_double_p]),
-    ("pgx_ic_residual", C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
-    ("pgx_ic_jacobian_fill", C.c_int, [_H, c_double_p]),
-    ("pgx_ic_csr_export", C.c_int, [_H, c_int64_p, c_int64_p, c_int32_p, c_int32_p, c_double_p]),
-    ("pgx_ic_spmv", C.c_int, [_H, c_double_p, c_double_p]),
-    ("pgx_ic_newton_solve", C.c_int,
-     [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pgx_ic_l2_increment", C.c_int, [_H, c_double_p]),
-    ("pgx_ic_profile", C.c_int, [_H, C.c_int, c_double_p]),
 ]
+# the entry points the four mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
+_MIXED_COMMON = [
+    ("destroy", None, [_H]),
+    ("last_error", C.c_char_p, [_H]),
+    ("set_state", C.c_int, [_H, c_double_p]),
+    ("get_state", C.c_int, [_H, c_double_p]),
+    ("set_prev", C.c_int, [_H, c_double_p]),
+    ("get_prev", C.c_int, [_H, c_double_p]),
+    ("advance_prev", C.c_int, [_H]),
+    ("set_alpha", C.c_int, [_H, C.c_double]),
+    ("residual", C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
+    ("jacobian_fill", C.c_int, [_H, c_double_p]),
+    ("csr_export", C.c_int, [_H, c_int64_p, c_int64_p, c_int32_p, c_int32_p, c_double_p]),
+    ("spmv", C.c_int, [_H, c_double_p, c_double_p]),
+    ("newton_solve", C.c_int, [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("profile", C.c_int, [_H, C.c_int, c_double_p]),
+]
+SYMBOLS += [(f"{prefix}_{suffix}", res, args) for prefix in ("pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic") for suffix, res, args in _MIXED_COMMON]
 
 _lib = None
 _forwarded: dict = {}

@@ -23,7 +23,6 @@ static thread_local std::string g_gc_error;
 struct pgx_gc_handle : MixedBase {
   int nv = 0, nc = 0, n2 = 0;
   GcQuad Q{};
-  double alpha = 1.0;
   double *coords = nullptr, *phi = nullptr, *f = nullptr, *gbc = nullptr;
   int32_t* cdofs = nullptr;
   uint8_t* mask = nullptr;
@@ -37,6 +36,7 @@ struct pgx_gc_handle : MixedBase {
   int gen = 0, NU = 6, NP = 3;
   int32_t *cdofs_p = nullptr, *cells3 = nullptr;  // latent cell dofs; vertex triples (affine geometry)
   double *tNu = nullptr, *tdNu = nullptr, *tNp = nullptr;
+  pgx_gc_handle() : MixedBase("pgx_gc") {}
   void residual_dev(const double* xin, double* Fout) override;
   void jacobian_dev(const double* xin) override;
 };
@@ -484,11 +484,7 @@ static GcgArgs gcg_args(const pgx_gc_handle* h);
 // ------------------------------------------------------------------------------------------------------------------
 // host: pattern, destination tables, create
 // ------------------------------------------------------------------------------------------------------------------
-extern "C" void pgx_gc_destroy(pgx_gc_handle* h) {
-  if (!h) return;
-  mx_release(h);
-  delete h;
-}
+extern "C" void pgx_gc_destroy(pgx_gc_handle* h) { mx_destroy(h); }
 
 static int gc_create_impl(pgx_gc_handle* h, const pgx_mesh* m, const pgx_gc_problem* p, pgx_comm* comm) {
   h->comm = comm;
@@ -974,25 +970,7 @@ extern "C" int pgx_gc_create_general(const pgx_gc_spaces* sp, const pgx_gc_probl
     g_gc_error = "pgx_gc_create_general: bad arguments";
     return PGX_EINVAL;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    g_gc_error = "pgx_gc_create_general: no usable GPU (there is no CPU fallback)";
-    return PGX_ENODEV;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    g_gc_error = "hipSetDevice failed";
-    return PGX_EHIP;
-  }
-  pgx_gc_handle* h = new pgx_gc_handle();
-  h->device = device;
-  int rc = gcg_create_impl(h, sp, p, nullptr);
-  if (rc) {
-    g_gc_error = h->err;
-    pgx_gc_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return PGX_OK;
+  return mx_create("pgx_gc_create_general", g_gc_error, device, out, [&](pgx_gc_handle* h) { return gcg_create_impl(h, sp, p, nullptr); });
 }
 
 static int gc_create(const pgx_mesh* m, const pgx_gc_problem* p, pgx_comm* comm, int device, pgx_gc_handle** out) {
@@ -1001,25 +979,7 @@ static int gc_create(const pgx_mesh* m, const pgx_gc_problem* p, pgx_comm* comm,
     g_gc_error = "pgx_gc_create: bad arguments";
     return PGX_EINVAL;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    g_gc_error = "pgx_gc_create: no usable GPU (there is no CPU fallback)";
-    return PGX_ENODEV;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    g_gc_error = "hipSetDevice failed";
-    return PGX_EHIP;
-  }
-  pgx_gc_handle* h = new pgx_gc_handle();
-  h->device = device;
-  int rc = gc_create_impl(h, m, p, comm);
-  if (rc) {
-    g_gc_error = h->err;
-    pgx_gc_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return PGX_OK;
+  return mx_create("pgx_gc_create", g_gc_error, device, out, [&](pgx_gc_handle* h) { return gc_create_impl(h, m, p, comm); });
 }
 
 extern "C" int pgx_gc_create(const pgx_mesh* m, const pgx_gc_problem* p, int device, pgx_gc_handle** out) {
@@ -1035,49 +995,17 @@ extern "C" int pgx_gc_create_dist(const pgx_mesh* m, const pgx_gc_problem* p, pg
 extern "C" int pgx_gc_lu_stats(const pgx_gc_handle* h, pgx_nd_stats* st) { return h ? pgx_nd_get_stats(h->lu, st) : PGX_EINVAL; }
 extern "C" int pgx_gc_lu_is_symmetric(const pgx_gc_handle* h) { return h ? pgx_nd_is_symmetric(h->lu) : 0; }
 
-#define GCNEED(h)                  \
-  if (!(h)) return PGX_EINVAL;     \
-  if (hipSetDevice((h)->device) != hipSuccess) return PGX_EHIP
-
 extern "C" int pgx_gc_num_dofs(const pgx_gc_handle* h, int64_t* ntot) {
   if (!h || !ntot) return PGX_EINVAL;
   *ntot = h->ntot;
   return PGX_OK;
 }
-static int gc_in(pgx_gc_handle* h, double* dst, const double* src) { return mx_in(h, dst, src); }
-static int gc_out(pgx_gc_handle* h, double* dst, const double* src) { return mx_out(h, dst, src); }
-extern "C" int pgx_gc_set_state(pgx_gc_handle* h, const double* x) {
-  GCNEED(h);
-  return gc_in(h, h->x, x);
-}
-extern "C" int pgx_gc_get_state(pgx_gc_handle* h, double* x) {
-  GCNEED(h);
-  return gc_out(h, x, h->x);
-}
-extern "C" int pgx_gc_set_prev(pgx_gc_handle* h, const double* x) {
-  GCNEED(h);
-  return gc_in(h, h->xk, x);
-}
-extern "C" int pgx_gc_get_prev(pgx_gc_handle* h, double* x) {
-  GCNEED(h);
-  return gc_out(h, x, h->xk);
-}
-extern "C" int pgx_gc_advance_prev(pgx_gc_handle* h) {
-  GCNEED(h);
-  GCHIP(hipMemcpyAsync(h->xk, h->x, sizeof(double) * h->ntot, hipMemcpyDeviceToDevice, h->st));
-  GCHIP(hipStreamSynchronize(h->st));
-  return PGX_OK;
-}
-extern "C" int pgx_gc_set_alpha(pgx_gc_handle* h, double a) {
-  GCNEED(h);
-  if (!(a > 0.0) || !std::isfinite(a)) {
-    h->err = "alpha must be positive and finite";
-    return PGX_EINVAL;
-  }
-  h->alpha = a;
-  h->jac_valid = false;
-  return PGX_OK;
-}
+extern "C" int pgx_gc_set_state(pgx_gc_handle* h, const double* x) { return mx_set_state(h, x); }
+extern "C" int pgx_gc_get_state(pgx_gc_handle* h, double* x) { return mx_get_state(h, x); }
+extern "C" int pgx_gc_set_prev(pgx_gc_handle* h, const double* x) { return mx_set_prev(h, x); }
+extern "C" int pgx_gc_get_prev(pgx_gc_handle* h, double* x) { return mx_get_prev(h, x); }
+extern "C" int pgx_gc_advance_prev(pgx_gc_handle* h) { return mx_advance_prev(h); }
+extern "C" int pgx_gc_set_alpha(pgx_gc_handle* h, double a) { return mx_set_alpha(h, a); }
 
 void pgx_gc_handle::residual_dev(const double* xin, double* Fout) {
   pgx_gc_handle* h = this;
@@ -1112,100 +1040,27 @@ void pgx_gc_handle::jacobian_dev(const double* xin) {
   pgx_scatter_run(h->st, h->sc_N, h->stash, -1.0, 1, h->Jv);  // the latent block is -N(psi)
   h->jac_valid = true;
 }
-static void gc_residual_dev(pgx_gc_handle* h, const double* x, double* F) { h->residual_dev(x, F); }
-static void gc_jacobian_dev(pgx_gc_handle* h, const double* x) { h->jacobian_dev(x); }
-static void gc_spmv_dev(pgx_gc_handle* h, const double* x, double* y) { mx_spmv_dev(h, x, y); }
-static int gc_norm(pgx_gc_handle* h, const double* v, double* out) { return mx_norm(h, v, out); }
-
-extern "C" int pgx_gc_residual(pgx_gc_handle* h, const double* x, double* F, double* fnorm) {
-  GCNEED(h);
-  const double* xd = h->x;
-  if (x) {
-    int rc = gc_in(h, h->xw, x);
-    if (rc) return rc;
-    xd = h->xw;
-  }
-  gc_residual_dev(h, xd, h->F);
-  if (fnorm) {
-    int rc = gc_norm(h, h->F, fnorm);
-    if (rc) return rc;
-  }
-  if (F) return gc_out(h, F, h->F);
-  GCHIP(hipStreamSynchronize(h->st));
-  return PGX_OK;
-}
-
-extern "C" int pgx_gc_jacobian_fill(pgx_gc_handle* h, const double* x) {
-  GCNEED(h);
-  const double* xd = h->x;
-  if (x) {
-    int rc = gc_in(h, h->xw, x);
-    if (rc) return rc;
-    xd = h->xw;
-  }
-  gc_jacobian_dev(h, xd);
-  GCHIP(hipStreamSynchronize(h->st));
-  GCHIP(hipGetLastError());
-  return PGX_OK;
-}
-
+extern "C" int pgx_gc_residual(pgx_gc_handle* h, const double* x, double* F, double* fnorm) { return mx_residual(h, x, F, fnorm); }
+extern "C" int pgx_gc_jacobian_fill(pgx_gc_handle* h, const double* x) { return mx_jacobian_fill(h, x); }
 extern "C" int pgx_gc_csr_export(pgx_gc_handle* h, int64_t* nrows, int64_t* nnz, int32_t* rowptr, int32_t* col,
                                  double* vals) {
-  GCNEED(h);
-  if (nrows) *nrows = h->ntot;
-  if (nnz) *nnz = h->nnz;
-  if (rowptr) std::copy(h->h_rowptr.begin(), h->h_rowptr.end(), rowptr);
-  if (col) std::copy(h->h_col.begin(), h->h_col.end(), col);
-  if (vals) {
-    if (!h->jac_valid) {
-      h->err = "pgx_gc_csr_export: no Jacobian has been filled";
-      return PGX_ESTATE;
-    }
-    GCHIP(hipMemcpy(vals, h->Jv, sizeof(double) * h->nnz, hipMemcpyDeviceToHost));
-  }
-  return PGX_OK;
+  return mx_csr_export(h, nrows, nnz, rowptr, col, vals);
 }
-
-extern "C" int pgx_gc_spmv(pgx_gc_handle* h, const double* x, double* y) {
-  GCNEED(h);
-  if (!x || !y) return PGX_EINVAL;
-  if (!h->jac_valid) {
-    h->err = "pgx_gc_spmv: no Jacobian has been filled";
-    return PGX_ESTATE;
-  }
-  int rc = gc_in(h, h->r, x);
-  if (rc) return rc;
-  gc_spmv_dev(h, h->r, h->z);
-  return gc_out(h, y, h->z);
-}
+extern "C" int pgx_gc_spmv(pgx_gc_handle* h, const double* x, double* y) { return mx_spmv(h, x, y); }
 
 extern "C" int pgx_gc_l2_increment(pgx_gc_handle* h, double* out) {
-  GCNEED(h);
+  MXNEED(h);
   if (!out) return PGX_EINVAL;
   if (h->gen)
     hipLaunchKernelGGL(k_gcg_l2, dim3(GC_RED), dim3(256), 0, h->st, gcg_args(h), h->x, h->xk, h->partials);
   else
     hipLaunchKernelGGL(k_gc_l2, dim3(GC_RED), dim3(256), 0, h->st, h->nc, h->cdofs, h->coords, h->x, h->xk, h->Q, h->partials);
-  hipLaunchKernelGGL(k_mx_final, dim3(1), dim3(256), 0, h->st, GC_RED, h->partials, h->d_out);
-  {
-    const int rcs = mx_sync_scalar(h);  // distributed handles: the loop's stopping test must agree on every rank
-    if (rcs) return rcs;
-  }
-  GCHIP(hipMemcpyAsync(h->h_out, h->d_out, sizeof(double), hipMemcpyDeviceToHost, h->st));
-  GCHIP(hipStreamSynchronize(h->st));
-  *out = std::sqrt(std::max(h->h_out[0], 0.0));
-  return PGX_OK;
+  return mx_partials_sqrt(h, out);
 }
 
-extern "C" int pgx_gc_profile(pgx_gc_handle* h, int enable, double ms[6]) {
-  GCNEED(h);
-  pgx_nd_timing(h->lu, enable, nullptr, nullptr);
-  return mx_profile(h, enable, ms);
-}
+extern "C" int pgx_gc_profile(pgx_gc_handle* h, int enable, double ms[6]) { return mx_profile(h, enable, ms); }
 
+// linesearch 1: bt; every other value (2 included): plain Newton
 extern "C" int pgx_gc_newton_solve(pgx_gc_handle* h, const pgx_snes_opts* opts, int* reason, int* its_out, int* lin_out) {
-  GCNEED(h);
-  if (!opts) return PGX_EINVAL;
-  return opts->linesearch == 1 ? mx_newton_solve_bt(h, opts, reason, its_out, lin_out)
-                               : mx_newton_solve(h, opts, reason, its_out, lin_out);
+  return mx_newton(h, opts, reason, its_out, lin_out, false);
 }

@@ -21,9 +21,10 @@ static thread_local std::string g_ic_error;
 struct pgx_ic_handle : MixedBase {
   int nv = 0, nc = 0;
   IcQuad Q{};
-  double alpha = 1.0, c = 0.0;
+  double c = 0.0;
   double *xc = nullptr, *phi0_q = nullptr, *phi_q = nullptr;
   uint8_t* mask = nullptr;
+  pgx_ic_handle() : MixedBase("pgx_ic") {}
   void residual_dev(const double* xin, double* Fout) override;
   void jacobian_dev(const double* xin) override;
 };
@@ -148,11 +149,7 @@ __global__ __launch_bounds__(256) void k_ic_l2(int nc, const double* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-extern "C" void pgx_ic_destroy(pgx_ic_handle* h) {
-  if (!h) return;
-  mx_release(h);
-  delete h;
-}
+extern "C" void pgx_ic_destroy(pgx_ic_handle* h) { mx_destroy(h); }
 
 void pgx_ic_handle::residual_dev(const double* xin, double* Fout) {
   pgx_ic_handle* h = this;
@@ -257,151 +254,39 @@ extern "C" int pgx_ic_create(const pgx_ic_problem* p, int device, pgx_ic_handle*
     g_ic_error = "pgx_ic_create: bad arguments";
     return PGX_EINVAL;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    g_ic_error = "pgx_ic_create: no usable GPU (there is no CPU fallback)";
-    return PGX_ENODEV;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    g_ic_error = "hipSetDevice failed";
-    return PGX_EHIP;
-  }
-  pgx_ic_handle* h = new pgx_ic_handle();
-  h->device = device;
-  int rc = ic_create_impl(h, p);
-  if (rc) {
-    g_ic_error = h->err;
-    pgx_ic_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return PGX_OK;
+  return mx_create("pgx_ic_create", g_ic_error, device, out, [&](pgx_ic_handle* h) { return ic_create_impl(h, p); });
 }
-
-#define ICNEED(h)              \
-  if (!(h)) return PGX_EINVAL; \
-  if (hipSetDevice((h)->device) != hipSuccess) return PGX_EHIP
 
 extern "C" int pgx_ic_num_dofs(const pgx_ic_handle* h, int64_t* ntot) {
   if (!h || !ntot) return PGX_EINVAL;
   *ntot = h->ntot;
   return PGX_OK;
 }
-extern "C" int pgx_ic_set_state(pgx_ic_handle* h, const double* x) {
-  ICNEED(h);
-  return mx_in(h, h->x, x);
-}
-extern "C" int pgx_ic_get_state(pgx_ic_handle* h, double* x) {
-  ICNEED(h);
-  return mx_out(h, x, h->x);
-}
-extern "C" int pgx_ic_set_prev(pgx_ic_handle* h, const double* x) {
-  ICNEED(h);
-  return mx_in(h, h->xk, x);
-}
-extern "C" int pgx_ic_get_prev(pgx_ic_handle* h, double* x) {
-  ICNEED(h);
-  return mx_out(h, x, h->xk);
-}
-extern "C" int pgx_ic_advance_prev(pgx_ic_handle* h) {
-  ICNEED(h);
-  MXHIP(hipMemcpyAsync(h->xk, h->x, sizeof(double) * h->ntot, hipMemcpyDeviceToDevice, h->st));
-  MXHIP(hipStreamSynchronize(h->st));
-  return PGX_OK;
-}
-extern "C" int pgx_ic_set_alpha(pgx_ic_handle* h, double a) {
-  ICNEED(h);
-  if (!(a > 0.0) || !std::isfinite(a)) {
-    h->err = "alpha must be positive and finite";
-    return PGX_EINVAL;
-  }
-  h->alpha = a;
-  h->jac_valid = false;
-  return PGX_OK;
-}
+extern "C" int pgx_ic_set_state(pgx_ic_handle* h, const double* x) { return mx_set_state(h, x); }
+extern "C" int pgx_ic_get_state(pgx_ic_handle* h, double* x) { return mx_get_state(h, x); }
+extern "C" int pgx_ic_set_prev(pgx_ic_handle* h, const double* x) { return mx_set_prev(h, x); }
+extern "C" int pgx_ic_get_prev(pgx_ic_handle* h, double* x) { return mx_get_prev(h, x); }
+extern "C" int pgx_ic_advance_prev(pgx_ic_handle* h) { return mx_advance_prev(h); }
+extern "C" int pgx_ic_set_alpha(pgx_ic_handle* h, double a) { return mx_set_alpha(h, a); }
 extern "C" int pgx_ic_set_phi(pgx_ic_handle* h, const double* phi_q) {
-  ICNEED(h);
+  MXNEED(h);
   h->jac_valid = false;
   return mx_in(h, h->phi_q, phi_q, (int64_t)h->nc * h->Q.nq);
 }
-extern "C" int pgx_ic_residual(pgx_ic_handle* h, const double* x, double* F, double* fnorm) {
-  ICNEED(h);
-  const double* xd = h->x;
-  if (x) {
-    int rc = mx_in(h, h->xw, x);
-    if (rc) return rc;
-    xd = h->xw;
-  }
-  h->residual_dev(xd, h->F);
-  if (fnorm) {
-    int rc = mx_norm(h, h->F, fnorm);
-    if (rc) return rc;
-  }
-  if (F) return mx_out(h, F, h->F);
-  MXHIP(hipStreamSynchronize(h->st));
-  return PGX_OK;
-}
-extern "C" int pgx_ic_jacobian_fill(pgx_ic_handle* h, const double* x) {
-  ICNEED(h);
-  const double* xd = h->x;
-  if (x) {
-    int rc = mx_in(h, h->xw, x);
-    if (rc) return rc;
-    xd = h->xw;
-  }
-  h->jacobian_dev(xd);
-  MXHIP(hipStreamSynchronize(h->st));
-  MXHIP(hipGetLastError());
-  return PGX_OK;
-}
+extern "C" int pgx_ic_residual(pgx_ic_handle* h, const double* x, double* F, double* fnorm) { return mx_residual(h, x, F, fnorm); }
+extern "C" int pgx_ic_jacobian_fill(pgx_ic_handle* h, const double* x) { return mx_jacobian_fill(h, x); }
 extern "C" int pgx_ic_csr_export(pgx_ic_handle* h, int64_t* nrows, int64_t* nnz, int32_t* rowptr, int32_t* col, double* vals) {
-  ICNEED(h);
-  if (nrows) *nrows = h->ntot;
-  if (nnz) *nnz = h->nnz;
-  if (rowptr) std::copy(h->h_rowptr.begin(), h->h_rowptr.end(), rowptr);
-  if (col) std::copy(h->h_col.begin(), h->h_col.end(), col);
-  if (vals) {
-    if (!h->jac_valid) {
-      h->err = "pgx_ic_csr_export: no Jacobian has been filled";
-      return PGX_ESTATE;
-    }
-    MXHIP(hipMemcpy(vals, h->Jv, sizeof(double) * h->nnz, hipMemcpyDeviceToHost));
-  }
-  return PGX_OK;
+  return mx_csr_export(h, nrows, nnz, rowptr, col, vals);
 }
-extern "C" int pgx_ic_spmv(pgx_ic_handle* h, const double* x, double* y) {
-  ICNEED(h);
-  if (!x || !y) return PGX_EINVAL;
-  if (!h->jac_valid) {
-    h->err = "pgx_ic_spmv: no Jacobian has been filled";
-    return PGX_ESTATE;
-  }
-  int rc = mx_in(h, h->r, x);
-  if (rc) return rc;
-  mx_spmv_dev(h, h->r, h->z);
-  return mx_out(h, y, h->z);
-}
+extern "C" int pgx_ic_spmv(pgx_ic_handle* h, const double* x, double* y) { return mx_spmv(h, x, y); }
+// linesearch 2 / 1 / other: l2 / bt / plain Newton
 extern "C" int pgx_ic_newton_solve(pgx_ic_handle* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its) {
-  ICNEED(h);
-  if (!opts) return PGX_EINVAL;
-  switch (opts->linesearch) {
-    case 2: return mx_newton_solve_l2(h, opts, reason, its, lin_its);
-    case 1: return mx_newton_solve_bt(h, opts, reason, its, lin_its);
-    default: return mx_newton_solve(h, opts, reason, its, lin_its);
-  }
+  return mx_newton(h, opts, reason, its, lin_its, true);
 }
 extern "C" int pgx_ic_l2_increment(pgx_ic_handle* h, double* out) {
-  ICNEED(h);
+  MXNEED(h);
   if (!out) return PGX_EINVAL;
   hipLaunchKernelGGL(k_ic_l2, dim3(MX_RED), dim3(256), 0, h->st, h->nc, h->xc, h->x, h->xk, h->Q, h->partials);
-  hipLaunchKernelGGL(k_mx_final, dim3(1), dim3(256), 0, h->st, MX_RED, h->partials, h->d_out);
-  MXHIP(hipMemcpyAsync(h->h_out, h->d_out, sizeof(double), hipMemcpyDeviceToHost, h->st));
-  MXHIP(hipStreamSynchronize(h->st));
-  *out = std::sqrt(std::max(h->h_out[0], 0.0));
-  return PGX_OK;
+  return mx_partials_sqrt(h, out);
 }
-extern "C" int pgx_ic_profile(pgx_ic_handle* h, int enable, double ms[6]) {
-  ICNEED(h);
-  pgx_nd_timing(h->lu, enable, nullptr, nullptr);
-  return mx_profile(h, enable, ms);
-}
+extern "C" int pgx_ic_profile(pgx_ic_handle* h, int enable, double ms[6]) { return mx_profile(h, enable, ms); }

@@ -20,7 +20,7 @@ static thread_local std::string g_qvi_error;
 struct pgx_qvi_handle : MixedBase {
   int nv = 0, nc = 0;
   QvQuad Q{};
-  double alpha = 1.0, beta = 1.0, f = 25.0, knee = 0.01, eps_mod = 1e-10;
+  double beta = 1.0, f = 25.0, knee = 0.01, eps_mod = 1e-10;
   double* coords = nullptr;
   int32_t* cells = nullptr;
   // deterministic assembly (pgx_scatter.h): element kernels park [slot * nc + cell]; one thread per destination sums
@@ -28,6 +28,7 @@ struct pgx_qvi_handle : MixedBase {
   double* stash = nullptr;    // [18 * nc]
   uint8_t *mask = nullptr, *kind = nullptr;
   double* Jc = nullptr;
+  pgx_qvi_handle() : MixedBase("pgx_qvi") {}
   void residual_dev(const double* xin, double* Fout) override;
   void jacobian_dev(const double* xin) override;
 };
@@ -215,11 +216,7 @@ __global__ __launch_bounds__(256) void k_qv_h1(int nc, const int32_t* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-extern "C" void pgx_qvi_destroy(pgx_qvi_handle* h) {
-  if (!h) return;
-  mx_release(h);
-  delete h;
-}
+extern "C" void pgx_qvi_destroy(pgx_qvi_handle* h) { mx_destroy(h); }
 
 void pgx_qvi_handle::residual_dev(const double* xin, double* Fout) {
   pgx_qvi_handle* h = this;
@@ -425,143 +422,35 @@ extern "C" int pgx_qvi_create(const pgx_mesh* m, const pgx_qvi_problem* p, int d
     g_qvi_error = "pgx_qvi_create: bad arguments";
     return PGX_EINVAL;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    g_qvi_error = "pgx_qvi_create: no usable GPU (there is no CPU fallback)";
-    return PGX_ENODEV;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    g_qvi_error = "hipSetDevice failed";
-    return PGX_EHIP;
-  }
-  pgx_qvi_handle* h = new pgx_qvi_handle();
-  h->device = device;
-  int rc = qvi_create_impl(h, m, p);
-  if (rc) {
-    g_qvi_error = h->err;
-    pgx_qvi_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return PGX_OK;
+  return mx_create("pgx_qvi_create", g_qvi_error, device, out, [&](pgx_qvi_handle* h) { return qvi_create_impl(h, m, p); });
 }
-
-#define QVNEED(h)              \
-  if (!(h)) return PGX_EINVAL; \
-  if (hipSetDevice((h)->device) != hipSuccess) return PGX_EHIP
 
 extern "C" int pgx_qvi_num_dofs(const pgx_qvi_handle* h, int64_t* ntot) {
   if (!h || !ntot) return PGX_EINVAL;
   *ntot = h->ntot;
   return PGX_OK;
 }
-extern "C" int pgx_qvi_set_state(pgx_qvi_handle* h, const double* x) {
-  QVNEED(h);
-  return mx_in(h, h->x, x);
-}
-extern "C" int pgx_qvi_get_state(pgx_qvi_handle* h, double* x) {
-  QVNEED(h);
-  return mx_out(h, x, h->x);
-}
-extern "C" int pgx_qvi_set_prev(pgx_qvi_handle* h, const double* x) {
-  QVNEED(h);
-  return mx_in(h, h->xk, x);
-}
-extern "C" int pgx_qvi_get_prev(pgx_qvi_handle* h, double* x) {
-  QVNEED(h);
-  return mx_out(h, x, h->xk);
-}
-extern "C" int pgx_qvi_advance_prev(pgx_qvi_handle* h) {
-  QVNEED(h);
-  MXHIP(hipMemcpyAsync(h->xk, h->x, sizeof(double) * h->ntot, hipMemcpyDeviceToDevice, h->st));
-  MXHIP(hipStreamSynchronize(h->st));
-  return PGX_OK;
-}
-extern "C" int pgx_qvi_set_alpha(pgx_qvi_handle* h, double a) {
-  QVNEED(h);
-  if (!(a > 0.0) || !std::isfinite(a)) {
-    h->err = "alpha must be positive and finite";
-    return PGX_EINVAL;
-  }
-  h->alpha = a;
-  h->jac_valid = false;
-  return PGX_OK;
-}
-extern "C" int pgx_qvi_residual(pgx_qvi_handle* h, const double* x, double* F, double* fnorm) {
-  QVNEED(h);
-  const double* xd = h->x;
-  if (x) {
-    int rc = mx_in(h, h->xw, x);
-    if (rc) return rc;
-    xd = h->xw;
-  }
-  h->residual_dev(xd, h->F);
-  if (fnorm) {
-    int rc = mx_norm(h, h->F, fnorm);
-    if (rc) return rc;
-  }
-  if (F) return mx_out(h, F, h->F);
-  MXHIP(hipStreamSynchronize(h->st));
-  return PGX_OK;
-}
-extern "C" int pgx_qvi_jacobian_fill(pgx_qvi_handle* h, const double* x) {
-  QVNEED(h);
-  const double* xd = h->x;
-  if (x) {
-    int rc = mx_in(h, h->xw, x);
-    if (rc) return rc;
-    xd = h->xw;
-  }
-  h->jacobian_dev(xd);
-  MXHIP(hipStreamSynchronize(h->st));
-  MXHIP(hipGetLastError());
-  return PGX_OK;
-}
+extern "C" int pgx_qvi_set_state(pgx_qvi_handle* h, const double* x) { return mx_set_state(h, x); }
+extern "C" int pgx_qvi_get_state(pgx_qvi_handle* h, double* x) { return mx_get_state(h, x); }
+extern "C" int pgx_qvi_set_prev(pgx_qvi_handle* h, const double* x) { return mx_set_prev(h, x); }
+extern "C" int pgx_qvi_get_prev(pgx_qvi_handle* h, double* x) { return mx_get_prev(h, x); }
+extern "C" int pgx_qvi_advance_prev(pgx_qvi_handle* h) { return mx_advance_prev(h); }
+extern "C" int pgx_qvi_set_alpha(pgx_qvi_handle* h, double a) { return mx_set_alpha(h, a); }
+extern "C" int pgx_qvi_residual(pgx_qvi_handle* h, const double* x, double* F, double* fnorm) { return mx_residual(h, x, F, fnorm); }
+extern "C" int pgx_qvi_jacobian_fill(pgx_qvi_handle* h, const double* x) { return mx_jacobian_fill(h, x); }
 extern "C" int pgx_qvi_csr_export(pgx_qvi_handle* h, int64_t* nrows, int64_t* nnz, int32_t* rowptr, int32_t* col,
                                   double* vals) {
-  QVNEED(h);
-  if (nrows) *nrows = h->ntot;
-  if (nnz) *nnz = h->nnz;
-  if (rowptr) std::copy(h->h_rowptr.begin(), h->h_rowptr.end(), rowptr);
-  if (col) std::copy(h->h_col.begin(), h->h_col.end(), col);
-  if (vals) {
-    if (!h->jac_valid) {
-      h->err = "pgx_qvi_csr_export: no Jacobian has been filled";
-      return PGX_ESTATE;
-    }
-    MXHIP(hipMemcpy(vals, h->Jv, sizeof(double) * h->nnz, hipMemcpyDeviceToHost));
-  }
-  return PGX_OK;
+  return mx_csr_export(h, nrows, nnz, rowptr, col, vals);
 }
-extern "C" int pgx_qvi_spmv(pgx_qvi_handle* h, const double* x, double* y) {
-  QVNEED(h);
-  if (!x || !y) return PGX_EINVAL;
-  if (!h->jac_valid) {
-    h->err = "pgx_qvi_spmv: no Jacobian has been filled";
-    return PGX_ESTATE;
-  }
-  int rc = mx_in(h, h->r, x);
-  if (rc) return rc;
-  mx_spmv_dev(h, h->r, h->z);
-  return mx_out(h, y, h->z);
-}
+extern "C" int pgx_qvi_spmv(pgx_qvi_handle* h, const double* x, double* y) { return mx_spmv(h, x, y); }
+// linesearch 1: bt; every other value (2 included): plain Newton
 extern "C" int pgx_qvi_newton_solve(pgx_qvi_handle* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its) {
-  QVNEED(h);
-  if (!opts) return PGX_EINVAL;
-  return opts->linesearch == 1 ? mx_newton_solve_bt(h, opts, reason, its, lin_its) : mx_newton_solve(h, opts, reason, its, lin_its);
+  return mx_newton(h, opts, reason, its, lin_its, false);
 }
 extern "C" int pgx_qvi_h1_increment(pgx_qvi_handle* h, double* out) {
-  QVNEED(h);
+  MXNEED(h);
   if (!out) return PGX_EINVAL;
   hipLaunchKernelGGL(k_qv_h1, dim3(MX_RED), dim3(256), 0, h->st, h->nc, h->cells, h->coords, h->x, h->xk, h->Q, h->partials);
-  hipLaunchKernelGGL(k_mx_final, dim3(1), dim3(256), 0, h->st, MX_RED, h->partials, h->d_out);
-  MXHIP(hipMemcpyAsync(h->h_out, h->d_out, sizeof(double), hipMemcpyDeviceToHost, h->st));
-  MXHIP(hipStreamSynchronize(h->st));
-  *out = std::sqrt(std::max(h->h_out[0], 0.0));
-  return PGX_OK;
+  return mx_partials_sqrt(h, out);
 }
-extern "C" int pgx_qvi_profile(pgx_qvi_handle* h, int enable, double ms[6]) {
-  QVNEED(h);
-  pgx_nd_timing(h->lu, enable, nullptr, nullptr);
-  return mx_profile(h, enable, ms);
-}
+extern "C" int pgx_qvi_profile(pgx_qvi_handle* h, int enable, double ms[6]) { return mx_profile(h, enable, ms); }

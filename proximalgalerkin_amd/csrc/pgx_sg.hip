@@ -28,7 +28,7 @@ struct pgx_sg_handle : MixedBase {
   int nv = 0, nc = 0, nf = 0, npsi = 0;  // nv = number of NODES (degree 2: vertices + edge midpoints)
   int npc = 4, npf = 3;                  // nodes per cell / per contact facet: 4 / 3 (degree 1), 10 / 6 (degree 2)
   SgQuad Q{};
-  double alpha = 1.0, gap = 0.0, mu = 0.0, lmbda = 0.0;
+  double gap = 0.0, mu = 0.0, lmbda = 0.0;
   double *coords = nullptr, *gbc = nullptr, *bg = nullptr;
   double* fgeo = nullptr;  // order-2 geometry (pgx_sg_create_curved): [facet][point][2] = surface element, z of the curved facet; else nullptr
   int32_t *facets = nullptr, *fpsi = nullptr;
@@ -40,6 +40,7 @@ struct pgx_sg_handle : MixedBase {
   std::vector<int32_t> cverts;
   bool partitioned = false;  // distributed handle: this rank assembled the elasticity blocks of its slab of cells only
   int nc_owned = 0;
+  pgx_sg_handle() : MixedBase("pgx_sg") {}
   void residual_dev(const double* xin, double* Fout) override;
   void jacobian_dev(const double* xin) override;
 };
@@ -356,11 +357,7 @@ __global__ __launch_bounds__(256) void k_sg_resid_rows(int64_t ntot, int nu, con
 // ------------------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------------------
-extern "C" void pgx_sg_destroy(pgx_sg_handle* h) {
-  if (!h) return;
-  mx_release(h);
-  delete h;
-}
+extern "C" void pgx_sg_destroy(pgx_sg_handle* h) { mx_destroy(h); }
 
 void pgx_sg_handle::residual_dev(const double* xin, double* Fout) {
   pgx_sg_handle* h = this;
@@ -677,7 +674,7 @@ static int sg_create_impl(pgx_sg_handle* h, const pgx_sg_mesh* m, const pgx_sg_p
     return rc;
   }
   // [[alpha A, M_G^T], [-M_G, D(psi)]] with the rows of the latent block negated is the symmetric [[alpha A, M_G^T], [M_G, -D]]
-  // (the Dirichlet rows AND columns of u are identity / zero): the LU takes it at half the flops (pgx_mixed.h lu_flip_from, pgx_nd.h);
+  // (the Dirichlet rows AND columns of u are identity / zero): the LU takes it at half the flops (pgx_mixed.hip mx_lu_factor, pgx_nd.h);
   // PGX_SG_SYM=0 keeps the general LU of the matrix as UFL's derivative gives it (A/B)
   {
     const char* e = pgx_tune("PGX_SG_SYM");
@@ -836,29 +833,10 @@ static int sg_create(const pgx_sg_mesh* m, const pgx_sg_problem* p, pgx_comm* co
     g_sg_error = "pgx_sg_create: bad arguments";
     return PGX_EINVAL;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    g_sg_error = "pgx_sg_create: no usable GPU (there is no CPU fallback)";
-    return PGX_ENODEV;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    g_sg_error = "hipSetDevice failed";
-    return PGX_EHIP;
-  }
-  pgx_sg_handle* h = new pgx_sg_handle();
-  h->device = device;
-  int rc;
-  if (m->cell_type == 1)
-    rc = (m->degree == 2) ? sg_create_impl<27, 9>(h, m, p, comm) : sg_create_impl<8, 4>(h, m, p, comm);
-  else
-    rc = (m->degree == 2) ? sg_create_impl<10, 6>(h, m, p, comm) : sg_create_impl<4, 3>(h, m, p, comm);
-  if (rc) {
-    g_sg_error = h->err;
-    pgx_sg_destroy(h);
-    return rc;
-  }
-  *out = h;
-  return PGX_OK;
+  return mx_create("pgx_sg_create", g_sg_error, device, out, [&](pgx_sg_handle* h) {
+    if (m->cell_type == 1) return (m->degree == 2) ? sg_create_impl<27, 9>(h, m, p, comm) : sg_create_impl<8, 4>(h, m, p, comm);
+    return (m->degree == 2) ? sg_create_impl<10, 6>(h, m, p, comm) : sg_create_impl<4, 3>(h, m, p, comm);
+  });
 }
 
 extern "C" int pgx_sg_create(const pgx_sg_mesh* m, const pgx_sg_problem* p, int device, pgx_sg_handle** out) {
@@ -894,10 +872,6 @@ extern "C" int pgx_sg_create_dist(const pgx_sg_mesh* m, const pgx_sg_problem* p,
   return sg_create(m, p, comm, device, out);
 }
 
-#define SGNEED(h)              \
-  if (!(h)) return PGX_EINVAL; \
-  if (hipSetDevice((h)->device) != hipSuccess) return PGX_EHIP
-
 extern "C" int pgx_sg_num_dofs(const pgx_sg_handle* h, int64_t* ntot, int64_t* npsi) {
   if (!h) return PGX_EINVAL;
   if (ntot) *ntot = h->ntot;
@@ -909,110 +883,28 @@ extern "C" int pgx_sg_contact_vertices(const pgx_sg_handle* h, int32_t* verts) {
   std::copy(h->cverts.begin(), h->cverts.end(), verts);
   return PGX_OK;
 }
-extern "C" int pgx_sg_set_state(pgx_sg_handle* h, const double* x) {
-  SGNEED(h);
-  return mx_in(h, h->x, x);
-}
-extern "C" int pgx_sg_get_state(pgx_sg_handle* h, double* x) {
-  SGNEED(h);
-  return mx_out(h, x, h->x);
-}
-extern "C" int pgx_sg_set_prev(pgx_sg_handle* h, const double* x) {
-  SGNEED(h);
-  return mx_in(h, h->xk, x);
-}
-extern "C" int pgx_sg_get_prev(pgx_sg_handle* h, double* x) {
-  SGNEED(h);
-  return mx_out(h, x, h->xk);
-}
-extern "C" int pgx_sg_advance_prev(pgx_sg_handle* h) {
-  SGNEED(h);
-  MXHIP(hipMemcpyAsync(h->xk, h->x, sizeof(double) * h->ntot, hipMemcpyDeviceToDevice, h->st));
-  MXHIP(hipStreamSynchronize(h->st));
-  return PGX_OK;
-}
-extern "C" int pgx_sg_set_alpha(pgx_sg_handle* h, double a) {
-  SGNEED(h);
-  if (!(a > 0.0) || !std::isfinite(a)) {
-    h->err = "alpha must be positive and finite";
-    return PGX_EINVAL;
-  }
-  h->alpha = a;
-  h->jac_valid = false;
-  return PGX_OK;
-}
-extern "C" int pgx_sg_residual(pgx_sg_handle* h, const double* x, double* F, double* fnorm) {
-  SGNEED(h);
-  const double* xd = h->x;
-  if (x) {
-    int rc = mx_in(h, h->xw, x);
-    if (rc) return rc;
-    xd = h->xw;
-  }
-  h->residual_dev(xd, h->F);
-  if (fnorm) {
-    int rc = mx_norm(h, h->F, fnorm);
-    if (rc) return rc;
-  }
-  if (F) return mx_out(h, F, h->F);
-  MXHIP(hipStreamSynchronize(h->st));
-  return PGX_OK;
-}
-extern "C" int pgx_sg_jacobian_fill(pgx_sg_handle* h, const double* x) {
-  SGNEED(h);
-  const double* xd = h->x;
-  if (x) {
-    int rc = mx_in(h, h->xw, x);
-    if (rc) return rc;
-    xd = h->xw;
-  }
-  h->jacobian_dev(xd);
-  MXHIP(hipStreamSynchronize(h->st));
-  MXHIP(hipGetLastError());
-  return PGX_OK;
-}
+extern "C" int pgx_sg_set_state(pgx_sg_handle* h, const double* x) { return mx_set_state(h, x); }
+extern "C" int pgx_sg_get_state(pgx_sg_handle* h, double* x) { return mx_get_state(h, x); }
+extern "C" int pgx_sg_set_prev(pgx_sg_handle* h, const double* x) { return mx_set_prev(h, x); }
+extern "C" int pgx_sg_get_prev(pgx_sg_handle* h, double* x) { return mx_get_prev(h, x); }
+extern "C" int pgx_sg_advance_prev(pgx_sg_handle* h) { return mx_advance_prev(h); }
+extern "C" int pgx_sg_set_alpha(pgx_sg_handle* h, double a) { return mx_set_alpha(h, a); }
+extern "C" int pgx_sg_residual(pgx_sg_handle* h, const double* x, double* F, double* fnorm) { return mx_residual(h, x, F, fnorm); }
+extern "C" int pgx_sg_jacobian_fill(pgx_sg_handle* h, const double* x) { return mx_jacobian_fill(h, x); }
 extern "C" int pgx_sg_csr_export(pgx_sg_handle* h, int64_t* nrows, int64_t* nnz, int32_t* rowptr, int32_t* col,
                                  double* vals) {
-  SGNEED(h);
-  if (nrows) *nrows = h->ntot;
-  if (nnz) *nnz = h->nnz;
-  if (rowptr) std::copy(h->h_rowptr.begin(), h->h_rowptr.end(), rowptr);
-  if (col) std::copy(h->h_col.begin(), h->h_col.end(), col);
-  if (vals) {
-    if (!h->jac_valid) {
-      h->err = "pgx_sg_csr_export: no Jacobian has been filled";
-      return PGX_ESTATE;
-    }
-    MXHIP(hipMemcpy(vals, h->Jv, sizeof(double) * h->nnz, hipMemcpyDeviceToHost));
-  }
-  return PGX_OK;
+  return mx_csr_export(h, nrows, nnz, rowptr, col, vals);
 }
-extern "C" int pgx_sg_spmv(pgx_sg_handle* h, const double* x, double* y) {
-  SGNEED(h);
-  if (!x || !y) return PGX_EINVAL;
-  if (!h->jac_valid) {
-    h->err = "pgx_sg_spmv: no Jacobian has been filled";
-    return PGX_ESTATE;
-  }
-  int rc = mx_in(h, h->r, x);
-  if (rc) return rc;
-  mx_spmv_dev(h, h->r, h->z);
-  return mx_out(h, y, h->z);
-}
+extern "C" int pgx_sg_spmv(pgx_sg_handle* h, const double* x, double* y) { return mx_spmv(h, x, y); }
+// linesearch 1: bt; every other value (2 included): plain Newton
 extern "C" int pgx_sg_newton_solve(pgx_sg_handle* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its) {
-  SGNEED(h);
-  if (!opts) return PGX_EINVAL;
-  return opts->linesearch == 1 ? mx_newton_solve_bt(h, opts, reason, its, lin_its) : mx_newton_solve(h, opts, reason, its, lin_its);
+  return mx_newton(h, opts, reason, its, lin_its, false);
 }
 extern "C" int pgx_sg_u_increment(pgx_sg_handle* h, double* out) {
-  SGNEED(h);
+  MXNEED(h);
   if (!out) return PGX_EINVAL;
   mx_axpby(h, 1.0, h->x, 0.0, h->r);
   mx_axpby(h, -1.0, h->xk, 1.0, h->r);
   return mx_norm(h, h->r, out, 3 * (int64_t)h->nv);
 }
-extern "C" int pgx_sg_profile(pgx_sg_handle* h, int enable, double ms[6]) {
-  SGNEED(h);
-  pgx_nd_timing(h->lu, enable, nullptr, nullptr);
-  return mx_profile(h, enable, ms);
-}
+extern "C" int pgx_sg_profile(pgx_sg_handle* h, int enable, double ms[6]) { return mx_profile(h, enable, ms); }

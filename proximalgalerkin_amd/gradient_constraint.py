@@ -16,7 +16,8 @@ from typing import Callable, Literal
 import numpy as np
 
 from . import _lib, fem
-from .problem import ConvergenceError, _SNES
+from ._mixed import _MixedHandle
+from .problem import _SNES
 
 AlphaScheme = Literal["constant", "linear", "doubling"]
 
@@ -35,10 +36,12 @@ def f_default(x):
     return 15 * np.sin(np.pi * x[0]) * np.sin(np.pi * x[0])  # :296-297
 
 
-class GradientConstraintProblem:
+class GradientConstraintProblem(_MixedHandle):
     """Mixed space [P_k, (P_(k-1))^2] on `mesh` (k = `degree`, 2 by default as in the reference, up to 8); state layout
     x = [u (primal dofs) | psi_x | psi_y].  k = 2 runs the specialised kernels of include/pgx_gc.h, k >= 3 (or `general=True`) the
     table-driven ones (pgx_gc_create_general) with the Lagrange tables of proximalgalerkin_amd/lagrange.py."""
+
+    _prefix = "pgx_gc"
 
     def __init__(self, mesh: fem.Mesh, phi_func: Callable, f_func: Callable, petsc_options: dict | None = None,
                  quadrature_degree: int = 10, device: int = 0, comm=None, degree: int = 2, general: bool = False):
@@ -133,50 +136,10 @@ class GradientConstraintProblem:
                 raise NotImplementedError(f"snes_type {v}")
         self._opts.ksp_max_it = 6
         self.solver = _SNES(self._opts)
-        self.alpha = 1.0
-
-    def _check(self, rc, what):
-        if rc:
-            msg = self._lib.pgx_gc_last_error(self._h)
-            raise _lib.PgxError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-    # -- state -------------------------------------------------------------------------------------------------
-    def get_state(self):
-        x = np.empty(self.ndofs)
-        self._check(self._lib.pgx_gc_get_state(self._h, _lib.dptr(x)), "pgx_gc_get_state")
-        return x
-
-    def set_state(self, x):
-        self._check(self._lib.pgx_gc_set_state(self._h, _lib.dptr(np.ascontiguousarray(x, dtype=np.float64))), "set_state")
-
-    def set_prev(self, x):
-        self._check(self._lib.pgx_gc_set_prev(self._h, _lib.dptr(np.ascontiguousarray(x, dtype=np.float64))), "set_prev")
-
-    def advance_prev(self):
-        """w0.x.array[:] = sol.x.array (:205), on the device"""
-        self._check(self._lib.pgx_gc_advance_prev(self._h), "pgx_gc_advance_prev")
-
-    def set_alpha(self, a):
-        self.alpha = float(a)
-        self._check(self._lib.pgx_gc_set_alpha(self._h, float(a)), "pgx_gc_set_alpha")
-
-    # -- the call the script makes once per proximal step (:179) ------------------------------------------------------
-    def solve(self):
-        reason, its, lin = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._check(self._lib.pgx_gc_newton_solve(self._h, C.byref(self._opts), C.byref(reason), C.byref(its),
-                                                  C.byref(lin)), "pgx_gc_newton_solve")
-        s = self.solver
-        s._reason, s._its = reason.value, its.value
-        s.ksp._its, s.ksp._reason = lin.value, (-3 if reason.value == -3 else 4)
-        if reason.value <= 0 and self._flags["snes_error_if_not_converged"]:
-            raise ConvergenceError(f"SNES did not converge: reason {reason.value} after {its.value} iterations")
-        return reason.value, its.value
 
     def l2_increment(self):
         """sqrt(assemble_scalar(dot(u - u0, u - u0) dx)) (:164-166,184-186)"""
-        out = C.c_double(0)
-        self._check(self._lib.pgx_gc_l2_increment(self._h, C.byref(out)), "pgx_gc_l2_increment")
-        return out.value
+        return self._scalar("l2_increment")
 
     def warm_start(self, device: int = 0):
         """The reference's --warm_start (:72-96): u <- solution of the Poisson problem (grad p, grad q) = (f, q), u = 0 on the
@@ -208,54 +171,12 @@ class GradientConstraintProblem:
         self.set_state(x0)
         return x0
 
-    # -- fine-grained probes (tests) -----------------------------------------------------------------------------------
-    def residual(self, x=None):
-        out = np.empty(self.ndofs)
-        nrm = C.c_double(0)
-        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
-        self._check(self._lib.pgx_gc_residual(self._h, _lib.dptr(xx), _lib.dptr(out), C.byref(nrm)), "pgx_gc_residual")
-        return out, nrm.value
-
-    def jacobian(self, x=None):
-        import scipy.sparse as sp
-
-        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
-        self._check(self._lib.pgx_gc_jacobian_fill(self._h, _lib.dptr(xx)), "pgx_gc_jacobian_fill")
-        nr, nnz = C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.pgx_gc_csr_export(self._h, C.byref(nr), C.byref(nnz), None, None, None), "csr_export")
-        rp, col, val = np.empty(nr.value + 1, np.int32), np.empty(nnz.value, np.int32), np.empty(nnz.value)
-        self._check(self._lib.pgx_gc_csr_export(self._h, None, None, _lib.iptr(rp), _lib.iptr(col), _lib.dptr(val)),
-                    "csr_export")
-        return sp.csr_matrix((val, col, rp), shape=(nr.value, nr.value))
-
-    def spmv(self, x):
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        y = np.empty_like(x)
-        self._check(self._lib.pgx_gc_spmv(self._h, _lib.dptr(x), _lib.dptr(y)), "pgx_gc_spmv")
-        return y
-
     def lu_stats(self) -> dict:
         st = _lib.pgx_nd_stats()
-        self._check(self._lib.pgx_gc_lu_stats(self._h, C.byref(st)), "pgx_gc_lu_stats")
+        self._call("lu_stats", C.byref(st))
         out = {k: getattr(st, k) for k, _ in st._fields_}
         out["symmetric"] = bool(self._lib.pgx_gc_lu_is_symmetric(self._h))  # L D L^T in LU clothing: about half of `flops` executed
         return out
-
-    def profile(self, enable=True):
-        ms = (C.c_double * 6)()
-        self._check(self._lib.pgx_gc_profile(self._h, int(enable), ms), "pgx_gc_profile")
-        return dict(zip(("residual", "jacobian", "lu_factor", "lu_solve", "spmv", "newton_total"), ms))
-
-    def close(self):
-        if self._h:
-            self._lib.pgx_gc_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def solve_problem(N: int, M: int, primal_space: str = "Lagrange", primal_degree: int = 2, cell_type: str = "triangle",

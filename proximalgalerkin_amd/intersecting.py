@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, fem
+from ._mixed import _MixedHandle
 from .problem import _SNES
 
 # the reference's solver parameters (:66-79)
@@ -41,8 +42,10 @@ def phi_bound(phic):
     return lambda x: np.where(x[0] <= 0.2, float(phic), np.where(x[0] > 0.8, float(phic), 100.0))
 
 
-class IntersectingProblem:
+class IntersectingProblem(_MixedHandle):
     """x = [u | psi0 | psi], each P1 on the interval `mesh`; phi0 / phi: callables of x (shape (1, npts))."""
+
+    _prefix = "pgx_ic"
 
     def __init__(self, mesh: fem.IntervalMesh, phi0, phi, c=0.0, petsc_options: dict | None = None, quadrature_degree=6,
                  bc_dofs=None, device=0):
@@ -90,94 +93,15 @@ class IntersectingProblem:
         v = np.asarray(fn(self.xq.reshape(1, -1)), dtype=np.float64)
         return np.ascontiguousarray(np.broadcast_to(v, (self.xq.size,)).reshape(self.xq.shape))
 
-    def _check(self, rc, what):
-        if rc:
-            msg = self._lib.pgx_ic_last_error(self._h)
-            raise _lib.PgxError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-    def get_state(self):
-        x = np.empty(self.ndofs)
-        self._check(self._lib.pgx_ic_get_state(self._h, _lib.dptr(x)), "pgx_ic_get_state")
-        return x
-
-    def set_state(self, x):
-        self._check(self._lib.pgx_ic_set_state(self._h, _lib.dptr(np.ascontiguousarray(x, dtype=np.float64))), "pgx_ic_set_state")
-
-    def get_prev(self):
-        x = np.empty(self.ndofs)
-        self._check(self._lib.pgx_ic_get_prev(self._h, _lib.dptr(x)), "pgx_ic_get_prev")
-        return x
-
-    def set_prev(self, x):
-        self._check(self._lib.pgx_ic_set_prev(self._h, _lib.dptr(np.ascontiguousarray(x, dtype=np.float64))), "pgx_ic_set_prev")
-
-    def advance_prev(self):
-        self._check(self._lib.pgx_ic_advance_prev(self._h), "pgx_ic_advance_prev")
-
-    def set_alpha(self, a):
-        self._check(self._lib.pgx_ic_set_alpha(self._h, float(a)), "pgx_ic_set_alpha")
-
     def set_phi(self, phi):
         """the gradient bound changed (`phic.value = phi_`, :116): re-sample it; uploaded only if a value moved"""
         q = self._sample(phi)
         if not np.array_equal(q, self._phi_q):
-            self._check(self._lib.pgx_ic_set_phi(self._h, _lib.dptr(q)), "pgx_ic_set_phi")
+            self._call("set_phi", _lib.dptr(q))
             self._phi_q = q
 
-    def solve(self):
-        reason, its, lin = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._check(self._lib.pgx_ic_newton_solve(self._h, C.byref(self._opts), C.byref(reason), C.byref(its), C.byref(lin)),
-                    "pgx_ic_newton_solve")
-        s = self.solver
-        s._reason, s._its = reason.value, its.value
-        s.ksp._its, s.ksp._reason = lin.value, (-3 if reason.value == -3 else 4)
-        return reason.value, its.value
-
     def l2_increment(self):
-        out = C.c_double(0)
-        self._check(self._lib.pgx_ic_l2_increment(self._h, C.byref(out)), "pgx_ic_l2_increment")
-        return out.value
-
-    def residual(self, x=None):
-        out = np.empty(self.ndofs)
-        nrm = C.c_double(0)
-        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
-        self._check(self._lib.pgx_ic_residual(self._h, _lib.dptr(xx), _lib.dptr(out), C.byref(nrm)), "pgx_ic_residual")
-        return out, nrm.value
-
-    def jacobian(self, x=None):
-        import scipy.sparse as sp
-
-        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
-        self._check(self._lib.pgx_ic_jacobian_fill(self._h, _lib.dptr(xx)), "pgx_ic_jacobian_fill")
-        nr, nnz = C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.pgx_ic_csr_export(self._h, C.byref(nr), C.byref(nnz), None, None, None), "pgx_ic_csr_export")
-        rp, col, val = np.empty(nr.value + 1, np.int32), np.empty(nnz.value, np.int32), np.empty(nnz.value)
-        self._check(self._lib.pgx_ic_csr_export(self._h, None, None, _lib.iptr(rp), _lib.iptr(col), _lib.dptr(val)),
-                    "pgx_ic_csr_export")
-        return sp.csr_matrix((val, col, rp), shape=(nr.value, nr.value))
-
-    def spmv(self, x):
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        y = np.empty_like(x)
-        self._check(self._lib.pgx_ic_spmv(self._h, _lib.dptr(x), _lib.dptr(y)), "pgx_ic_spmv")
-        return y
-
-    def profile(self, enable=True):
-        ms = (C.c_double * 6)()
-        self._check(self._lib.pgx_ic_profile(self._h, int(enable), ms), "pgx_ic_profile")
-        return dict(zip(("residual", "jacobian", "lu_factor", "lu_solve", "spmv", "newton_total"), ms))
-
-    def close(self):
-        if self._h:
-            self._lib.pgx_ic_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._scalar("l2_increment")
 
 
 def solve_problem(n: int = 1001, phis=PHICS, tol: float = 1.0e-4, nfail_max: int = NFAIL_MAX, verbose: bool = True, device: int = 0):

@@ -19,7 +19,8 @@ from typing import Literal
 import numpy as np
 
 from . import _lib, fem
-from .problem import ConvergenceError, _SNES
+from ._mixed import _MixedHandle
+from .problem import _SNES
 
 AlphaScheme = Literal["constant", "linear", "doubling"]
 
@@ -239,8 +240,10 @@ def curved_tables(node_coords, cells10, facets6, cell_qpts, facet_qpts):
     return cgeo, np.ascontiguousarray(np.stack([ds, zq], axis=2))
 
 
-class SignoriniProblem:
+class SignoriniProblem(_MixedHandle):
     """x = [u_x | u_y | u_z | psi (contact vertices ordered by vertex id)]."""
+
+    _prefix = "pgx_sg"
 
     def __init__(self, mesh: TetMesh, contact_facets, bc_vertices, E, nu, gap, disp, quadrature_degree=4, device=0, comm=None, degree=1,
                  bc_facets=None, cell_quadrature_degree=None):
@@ -322,99 +325,22 @@ class SignoriniProblem:
         self._flags = {"snes_error_if_not_converged": True}  # :278
         self.solver = _SNES(self._opts)
 
-    def _check(self, rc, what):
-        if rc:
-            msg = self._lib.pgx_sg_last_error(self._h)
-            raise _lib.PgxError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-    def get_state(self):
-        x = np.empty(self.ndofs)
-        self._check(self._lib.pgx_sg_get_state(self._h, _lib.dptr(x)), "pgx_sg_get_state")
-        return x
-
-    def set_state(self, x):
-        self._check(self._lib.pgx_sg_set_state(self._h, _lib.dptr(np.ascontiguousarray(x, dtype=np.float64))), "set_state")
-
-    def set_prev(self, x):
-        self._check(self._lib.pgx_sg_set_prev(self._h, _lib.dptr(np.ascontiguousarray(x, dtype=np.float64))), "set_prev")
-
-    def advance_prev(self):
-        """u_prev.x.array[:] = u.x.array; psi_k.x.array[:] = psi.x.array (:342-343), on the device"""
-        self._check(self._lib.pgx_sg_advance_prev(self._h), "pgx_sg_advance_prev")
-
-    def set_alpha(self, a):
-        self._check(self._lib.pgx_sg_set_alpha(self._h, float(a)), "pgx_sg_set_alpha")
-
-    def solve(self):
-        reason, its, lin = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._check(self._lib.pgx_sg_newton_solve(self._h, C.byref(self._opts), C.byref(reason), C.byref(its),
-                                                  C.byref(lin)), "pgx_sg_newton_solve")
-        s = self.solver
-        s._reason, s._its = reason.value, its.value
-        s.ksp._its, s.ksp._reason = lin.value, (-3 if reason.value == -3 else 4)
-        if reason.value <= 0 and self._flags["snes_error_if_not_converged"]:
-            raise ConvergenceError(f"SNES did not converge: reason {reason.value} after {its.value} iterations")
-        return reason.value, its.value
-
     def u_increment(self):
-        out = C.c_double(0)
-        self._check(self._lib.pgx_sg_u_increment(self._h, C.byref(out)), "pgx_sg_u_increment")
-        return out.value
-
-    def residual(self, x=None):
-        out = np.empty(self.ndofs)
-        nrm = C.c_double(0)
-        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
-        self._check(self._lib.pgx_sg_residual(self._h, _lib.dptr(xx), _lib.dptr(out), C.byref(nrm)), "pgx_sg_residual")
-        return out, nrm.value
-
-    def jacobian(self, x=None):
-        import scipy.sparse as sp
-
-        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
-        self._check(self._lib.pgx_sg_jacobian_fill(self._h, _lib.dptr(xx)), "pgx_sg_jacobian_fill")
-        nr, nnz = C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.pgx_sg_csr_export(self._h, C.byref(nr), C.byref(nnz), None, None, None), "csr_export")
-        rp, col, val = np.empty(nr.value + 1, np.int32), np.empty(nnz.value, np.int32), np.empty(nnz.value)
-        self._check(self._lib.pgx_sg_csr_export(self._h, None, None, _lib.iptr(rp), _lib.iptr(col), _lib.dptr(val)),
-                    "csr_export")
-        return sp.csr_matrix((val, col, rp), shape=(nr.value, nr.value))
-
-    def spmv(self, x):
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        y = np.empty_like(x)
-        self._check(self._lib.pgx_sg_spmv(self._h, _lib.dptr(x), _lib.dptr(y)), "pgx_sg_spmv")
-        return y
+        return self._scalar("u_increment")
 
     def partition_info(self):
         """(cells whose element matrices this rank assembled, cells of the mesh): equal on a single handle; a distributed handle
         assembles its slab only (include/pgx_sg.h: pgx_sg_create_dist)."""
         a, b = C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.pgx_sg_partition_info(self._h, C.byref(a), C.byref(b)), "pgx_sg_partition_info")
+        self._call("partition_info", C.byref(a), C.byref(b))
         return a.value, b.value
 
     def lu_stats(self) -> dict:
         st = _lib.pgx_nd_stats()
-        self._check(self._lib.pgx_sg_lu_stats(self._h, C.byref(st)), "pgx_sg_lu_stats")
+        self._call("lu_stats", C.byref(st))
         out = {k: getattr(st, k) for k, _ in st._fields_}
         out["symmetric"] = bool(self._lib.pgx_sg_lu_is_symmetric(self._h))  # L D L^T in LU clothing: about half of `flops` executed
         return out
-
-    def profile(self, enable=True):
-        ms = (C.c_double * 6)()
-        self._check(self._lib.pgx_sg_profile(self._h, int(enable), ms), "pgx_sg_profile")
-        return dict(zip(("residual", "jacobian", "lu_factor", "lu_solve", "spmv", "newton_total"), ms))
-
-    def close(self):
-        if self._h:
-            self._lib.pgx_sg_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def solve_contact_problem(mesh: TetMesh, facet_tag: MeshTags, boundary_conditions: dict, degree: int = 1, E: float = 2.0e4,

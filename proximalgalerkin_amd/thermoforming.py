@@ -11,15 +11,18 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, fem
-from .problem import ConvergenceError, _SNES
+from ._mixed import _MixedHandle
+from .problem import _SNES
 
 # the reference's solver parameters (:102-113)
 SP = {"snes_type": "newtonls", "snes_linesearch_type": "bt", "pc_type": "lu", "snes_atol": 1e-5, "snes_rtol": 1e-5,
       "snes_stol": 10 * np.finfo(np.float64).eps, "snes_linesearch_order": 2}
 
 
-class ThermoformingProblem:
+class ThermoformingProblem(_MixedHandle):
     """x = [u | T | psi], each P1 on `mesh`."""
+
+    _prefix = "pgx_qvi"
 
     def __init__(self, mesh: fem.Mesh, petsc_options: dict | None = None, beta=1.0, f=25.0, knee=0.01, eps_mod=1.0e-10,
                  quadrature_degree=6, device=0):
@@ -58,82 +61,8 @@ class ThermoformingProblem:
         self._opts.ksp_max_it = 6
         self.solver = _SNES(self._opts)
 
-    def _check(self, rc, what):
-        if rc:
-            msg = self._lib.pgx_qvi_last_error(self._h)
-            raise _lib.PgxError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-    def get_state(self):
-        x = np.empty(self.ndofs)
-        self._check(self._lib.pgx_qvi_get_state(self._h, _lib.dptr(x)), "pgx_qvi_get_state")
-        return x
-
-    def set_state(self, x):
-        self._check(self._lib.pgx_qvi_set_state(self._h, _lib.dptr(np.ascontiguousarray(x, dtype=np.float64))), "set_state")
-
-    def set_prev(self, x):
-        self._check(self._lib.pgx_qvi_set_prev(self._h, _lib.dptr(np.ascontiguousarray(x, dtype=np.float64))), "set_prev")
-
-    def advance_prev(self):
-        self._check(self._lib.pgx_qvi_advance_prev(self._h), "pgx_qvi_advance_prev")
-
-    def set_alpha(self, a):
-        self._check(self._lib.pgx_qvi_set_alpha(self._h, float(a)), "pgx_qvi_set_alpha")
-
-    def solve(self):
-        reason, its, lin = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._check(self._lib.pgx_qvi_newton_solve(self._h, C.byref(self._opts), C.byref(reason), C.byref(its),
-                                                   C.byref(lin)), "pgx_qvi_newton_solve")
-        s = self.solver
-        s._reason, s._its = reason.value, its.value
-        s.ksp._its, s.ksp._reason = lin.value, (-3 if reason.value == -3 else 4)
-        return reason.value, its.value
-
     def h1_increment(self):
-        out = C.c_double(0)
-        self._check(self._lib.pgx_qvi_h1_increment(self._h, C.byref(out)), "pgx_qvi_h1_increment")
-        return out.value
-
-    def residual(self, x=None):
-        out = np.empty(self.ndofs)
-        nrm = C.c_double(0)
-        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
-        self._check(self._lib.pgx_qvi_residual(self._h, _lib.dptr(xx), _lib.dptr(out), C.byref(nrm)), "pgx_qvi_residual")
-        return out, nrm.value
-
-    def jacobian(self, x=None):
-        import scipy.sparse as sp
-
-        xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
-        self._check(self._lib.pgx_qvi_jacobian_fill(self._h, _lib.dptr(xx)), "pgx_qvi_jacobian_fill")
-        nr, nnz = C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.pgx_qvi_csr_export(self._h, C.byref(nr), C.byref(nnz), None, None, None), "csr_export")
-        rp, col, val = np.empty(nr.value + 1, np.int32), np.empty(nnz.value, np.int32), np.empty(nnz.value)
-        self._check(self._lib.pgx_qvi_csr_export(self._h, None, None, _lib.iptr(rp), _lib.iptr(col), _lib.dptr(val)),
-                    "csr_export")
-        return sp.csr_matrix((val, col, rp), shape=(nr.value, nr.value))
-
-    def spmv(self, x):
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        y = np.empty_like(x)
-        self._check(self._lib.pgx_qvi_spmv(self._h, _lib.dptr(x), _lib.dptr(y)), "pgx_qvi_spmv")
-        return y
-
-    def profile(self, enable=True):
-        ms = (C.c_double * 6)()
-        self._check(self._lib.pgx_qvi_profile(self._h, int(enable), ms), "pgx_qvi_profile")
-        return dict(zip(("residual", "jacobian", "lu_factor", "lu_solve", "spmv", "newton_total"), ms))
-
-    def close(self):
-        if self._h:
-            self._lib.pgx_qvi_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._scalar("h1_increment")
 
 
 def solve_problem(M: int = 150, alpha_0: float = 2.0**-6, alpha_max: float = 2.0**14, termination_tol: float = 1e-9,

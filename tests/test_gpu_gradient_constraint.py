@@ -134,7 +134,7 @@ def test_hip_reproduces_golden_fixture(require_gpu):
 
 def test_gmres_safeguard_of_the_linear_solve(require_gpu, monkeypatch):
     """Where LU + refinement cannot reach a true relative residual of 1e-7 (seen at 2048^2, alpha = 1024) the same LU
-    preconditions a GMRES on the exact operator (pgx_mixed.h::mx_gmres_lu).  Forced here: no refinement steps, GMRES polishes
+    preconditions a GMRES on the exact operator (pgx_mixed.hip::mx_gmres_lu).  Forced here: no refinement steps, GMRES polishes
     every solve to 1e-12 - the LVPP run must not change."""
     from proximalgalerkin_amd import fem
     from proximalgalerkin_amd.gradient_constraint import GradientConstraintProblem, f_default, phi_default

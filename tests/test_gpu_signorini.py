@@ -267,7 +267,7 @@ def test_hexahedra_kernels_and_full_run_match_oracle(require_gpu, n, degree):
 
 def test_symmetrised_lu_agrees_with_the_general_lu(require_gpu, monkeypatch):
     """Round 5: the Newton matrix [[alpha A, M_G^T], [-M_G, D]] enters the sparse LU with the rows of its latent block negated - a
-    symmetric matrix, factorised as L D L^T at half the flops (csrc/pgx_mixed.h lu_flip_from, pgx_nd_set_symmetric).  PGX_SG_SYM=0 keeps
+    symmetric matrix, factorised as L D L^T at half the flops (csrc/pgx_mixed.hip mx_lu_factor / lu_flip_from, pgx_nd_set_symmetric).  PGX_SG_SYM=0 keeps
     the general LU of the matrix as assembled: same Newton counts, same solution to the accuracy of the refined solves."""
     from proximalgalerkin_amd import signorini as G
 
