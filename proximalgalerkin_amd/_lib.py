@@ -194,6 +194,16 @@ class pgx_ic_problem(C.Structure):  # include/pgx_ic.h
     ]
 
 
+class pgx_mp_problem(C.Structure):  # include/pgx_mp.h
+    _fields_ = [
+        ("nq", C.c_int32),
+        ("qpts", c_double_p),
+        ("qwts", c_double_p),
+        ("tau", C.c_double),
+        ("eps", C.c_double),
+    ]
+
+
 class pgx_partition(C.Structure):
     _fields_ = [
         ("rank", C.c_int32),
@@ -305,8 +315,18 @@ SYMBOLS = [
     ("pgx_ic_num_dofs", C.c_int, [_H, c_int64_p]),
     ("pgx_ic_set_phi", C.c_int, [_H, c_double_p]),
     ("pgx_ic_l2_increment", C.c_int, [_H, c_double_p]),
+    # example 04: four-phase Cahn-Hilliard gradient flow (include/pgx_mp.h)
+    ("pgx_mp_create", C.c_int, [C.POINTER(pgx_mesh), C.POINTER(pgx_mp_problem), C.c_int, C.POINTER(_H)]),
+    ("pgx_mp_num_dofs", C.c_int, [_H, c_int64_p]),
+    ("pgx_mp_set_uprev", C.c_int, [_H, c_double_p]),
+    ("pgx_mp_get_uprev", C.c_int, [_H, c_double_p]),
+    ("pgx_mp_begin_step", C.c_int, [_H]),
+    ("pgx_mp_end_step", C.c_int, [_H]),
+    ("pgx_mp_l2_increment", C.c_int, [_H, c_double_p]),
+    ("pgx_mp_species_mass", C.c_int, [_H, c_double_p]),
+    ("pgx_mp_lu_stats", C.c_int, [_H, C.POINTER(pgx_nd_stats)]),
 ]
-# the entry points the four mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
+# the entry points the five mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
 _MIXED_COMMON = [
     ("destroy", None, [_H]),
     ("last_error", C.c_char_p, [_H]),
@@ -323,7 +343,7 @@ _MIXED_COMMON = [
     ("newton_solve", C.c_int, [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("profile", C.c_int, [_H, C.c_int, c_double_p]),
 ]
-SYMBOLS += [(f"{prefix}_{suffix}", res, args) for prefix in ("pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic") for suffix, res, args in _MIXED_COMMON]
+SYMBOLS += [(f"{prefix}_{suffix}", res, args) for prefix in ("pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic", "pgx_mp") for suffix, res, args in _MIXED_COMMON]
 
 _lib = None
 _forwarded: dict = {}

@@ -1,5 +1,5 @@
-// pgx_mixed.h - what the four mixed-matrix families share (examples 06 / 02 / 05 / 08: pgx_gc.hip, pgx_sg.hip, pgx_qvi.hip,
-// pgx_ic.hip): the handle base with its mixed CSR Newton matrix on the device and state vectors, the allocation / error / timing
+// pgx_mixed.h - what the mixed-matrix families share (examples 06 / 02 / 05 / 08 / 04: pgx_gc.hip, pgx_sg.hip, pgx_qvi.hip,
+// pgx_ic.hip, pgx_mp.hip): the handle base with its mixed CSR Newton matrix on the device and state vectors, the allocation / error / timing
 // helpers, and the prototypes of the shared driver in pgx_mixed.hip - fixed-shape reductions, the SNES-mirroring Newton drivers
 // (newtonls with linesearch none / bt / l2), their linear solve = sparse LU (pgx_nd) + iterative refinement on the exact
 // operator, and the C entry points every family forwards to.  A family keeps only its assembly kernels and its create path.
@@ -141,7 +141,8 @@ int mx_residual(MixedBase* h, const double* x, double* F, double* fnorm);
 int mx_jacobian_fill(MixedBase* h, const double* x);
 int mx_csr_export(MixedBase* h, int64_t* nrows, int64_t* nnz, int32_t* rowptr, int32_t* col, double* vals);
 int mx_spmv(MixedBase* h, const double* x, double* y);
-// opts->linesearch 1: bt; 2: l2 if the family takes it (with_l2), else plain Newton like every other value
+// opts->linesearch 1: bt of order 2; 3: bt of order 3 (cubic); 2: l2 if the family takes it (with_l2), else plain Newton like
+// every other value
 int mx_newton(MixedBase* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its, bool with_l2);
 int mx_profile(MixedBase* h, int enable, double ms[6]);
 #pragma GCC visibility pop

@@ -555,7 +555,15 @@ static int mx_gmres_lu(MixedBase* h, const double* b, double* dx, double bnorm, 
 // steptol 1e-12, at most 40 backtracking steps; a non-finite trial residual counts as "no sufficient decrease" and
 // shrinks lambda tenfold.  The Jacobian may be a MODIFIED one (J != dF/dx, thermoforming_dolfinx.py:69-71): the initial
 // slope uses the same matrix the direction was computed with, as PETSc's MatMult(jac, Y, W) does.
-static int mx_newton_solve_bt(MixedBase* h, const pgx_snes_opts* opts, int* reason, int* its_out, int* lin_out) {
+// order 3 (cubic, PETSc's default order of bt; example 04): lambda = 1, then the same one quadratic fit, then cubic fits
+// through the last two trial points (lambda, |F|^2) and (lambda_prev, |F_prev|^2):
+//   t1 = (g - f) / 2 - lambda s0, t2 = (g_prev - f) / 2 - lambda_prev s0,
+//   a = (t1 / lambda^2 - t2 / lambda_prev^2) / (lambda - lambda_prev), b = (-lambda_prev t1 / lambda^2 + lambda t2 / lambda_prev^2) / (lambda - lambda_prev),
+//   d = max(b^2 - 3 a s0, 0), lambda_t = (-b + sqrt(d)) / (3 a)  (-s0 / (2 b) when a = 0), clamped to [0.1 lambda, 0.5 lambda].
+// This too is recalled from SNESLineSearchApply_BT, not checked against PETSc's source; tests/multiphase_reference.py::newton_bt
+// restates it from the same recollection.  A non-finite trial residual is never a fit point: it shrinks lambda tenfold and the
+// last finite pair stays.  Order 2 is the loop of the quadratic fit alone, unchanged.
+static int mx_newton_solve_bt(MixedBase* h, const pgx_snes_opts* opts, int* reason, int* its_out, int* lin_out, int order) {
   if (!opts || !reason) return PGX_EINVAL;
   PgxSolveScope scope(h->st, h->prof, nullptr);
   PgxRange range("pgx:newton_solve");
@@ -638,6 +646,8 @@ static int mx_newton_solve_bt(MixedBase* h, const pgx_snes_opts* opts, int* reas
     bool ok = true;
     if ((rc = trial(lam))) return rc;
     if (!(std::isfinite(g) && 0.5 * g <= 0.5 * f + lam * 1e-4 * initslope)) {
+      double lam_prev = lam, g_prev = g;  // order 3: the last finite trial point
+      bool have_prev = std::isfinite(g);
       lam = shrink(lam, true);
       if ((rc = trial(lam))) return rc;
       if (!(std::isfinite(g) && 0.5 * g < 0.5 * f + lam * 1e-4 * initslope)) {
@@ -647,7 +657,28 @@ static int mx_newton_solve_bt(MixedBase* h, const pgx_snes_opts* opts, int* reas
             ok = false;
             break;
           }
-          lam = shrink(lam, false);
+          if (order != 3) {
+            lam = shrink(lam, false);
+          } else {
+            double lt;
+            if (!std::isfinite(g)) {
+              lt = 0.1 * lam;
+            } else {
+              if (have_prev) {
+                const double t1 = 0.5 * (g - f) - lam * initslope, t2 = 0.5 * (g_prev - f) - lam_prev * initslope;
+                const double a = (t1 / (lam * lam) - t2 / (lam_prev * lam_prev)) / (lam - lam_prev);
+                const double b = (-lam_prev * t1 / (lam * lam) + lam * t2 / (lam_prev * lam_prev)) / (lam - lam_prev);
+                const double d = std::max(b * b - 3.0 * a * initslope, 0.0);
+                lt = a == 0.0 ? -initslope / (2.0 * b) : (-b + std::sqrt(d)) / (3.0 * a);
+              } else {
+                lt = -initslope / (g - f - 2.0 * lam * initslope);
+              }
+              lt = std::min(lt, 0.5 * lam);
+              if (lt <= 0.1 * lam) lt = 0.1 * lam;
+              lam_prev = lam, g_prev = g, have_prev = true;
+            }
+            lam = lt;
+          }
           if ((rc = trial(lam))) return rc;
           if (std::isfinite(g) && 0.5 * g < 0.5 * f + lam * 1e-4 * initslope) break;
           if (++count > 40) {
@@ -934,7 +965,8 @@ int mx_newton(MixedBase* h, const pgx_snes_opts* opts, int* reason, int* its, in
   MXNEED(h);
   if (!opts) return PGX_EINVAL;
   if (opts->linesearch == 2 && with_l2) return mx_newton_solve_l2(h, opts, reason, its, lin_its);
-  if (opts->linesearch == 1) return mx_newton_solve_bt(h, opts, reason, its, lin_its);
+  if (opts->linesearch == 1) return mx_newton_solve_bt(h, opts, reason, its, lin_its, 2);
+  if (opts->linesearch == 3) return mx_newton_solve_bt(h, opts, reason, its, lin_its, 3);
   return mx_newton_solve(h, opts, reason, its, lin_its);
 }
 

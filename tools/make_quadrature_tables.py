@@ -23,6 +23,11 @@ tri_deg10_gj36 : collapsed (Duffy) Gauss-Jacobi rule, 6 x 6 = 36 points, exact t
               (parity with FEniCSx unpinned, oracle <-> HIP exact by construction).  Nodes are roots of the Jacobi /
               Legendre polynomials refined with mpmath, weights from the moment equations, 50 digits.
 
+tri_deg7_gj16 : the same collapsed Gauss-Jacobi family with 4 x 4 = 16 points, exact to degree 7: the degree UFL estimates
+              for the softmax term of example 04 (the reference's multiphase_dolfinx.py:82-89, no
+              quadrature metadata).  Basix's default for degree 7 is a Xiao-Gimbutas table that cannot be derived offline;
+              the choice affects only that term (every other term of the form is of degree <= 2).
+
 The reference fixes quadrature_degree=6 for every integral of example 01
 (/root/reference/examples/01_obstacle_problem/obstacle_pg.py:106,115).  Basix's default table for
 that degree is not available offline => parity with a real FEniCSx run is
@@ -215,6 +220,24 @@ def main():
                   "40 digits by tools/make_quadrature_tables.py",
         "points": [[float(x), float(y)] for (x, y) in pts_b],
         "weights": [float(w) for w in wts_b],
+    }
+    # example 04 (multiphase_dolfinx.py): the form carries no quadrature metadata and UFL estimates degree 7 for the softmax
+    # term exp(psi_m) / sum_n exp(psi_n) tested with P1 (exp: +2, a quotient adds the degrees); every other term is of degree
+    # <= 2.  Basix's default for degree 7 is a Xiao-Gimbutas table that cannot be derived offline, hence the derivable
+    # collapsed rule with m = 4 points per direction (exact to degree 7); only the softmax term sees the difference.
+    pts7, wts7 = collapsed_rule(4)
+    worst7 = mp.mpf(0)
+    for p in range(8):
+        for q in range(8 - p):
+            s = sum(w * x**p * y**q for (x, y), w in zip(pts7, wts7))
+            worst7 = max(worst7, abs(s - moments_exact(p, q)))
+    assert worst7 < mp.mpf(10) ** (-35), worst7
+    table["tri_deg7_gj16"] = {
+        "cell": "triangle",
+        "degree": 7,
+        "source": "collapsed Gauss-Jacobi(1,0) x Gauss-Legendre, 4 x 4 points (exact to degree 7); tools/make_quadrature_tables.py",
+        "points": [[float(x), float(y)] for (x, y) in pts7],
+        "weights": [float(w) for w in wts7],
     }
     out = pathlib.Path(__file__).resolve().parents[1] / "proximalgalerkin_amd" / "tables" / "quadrature.json"
     out.write_text(json.dumps(table, indent=1) + "\n")
