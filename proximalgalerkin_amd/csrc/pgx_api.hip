@@ -71,6 +71,7 @@ struct pgx_handle {
   double* geoq = nullptr;  // order-2 geometry (pgx_create_curved): [cell][quadrature point][5] = |det J|, J^-1; nullptr = affine cells
   float2* zf_out = nullptr;  // FGMRES: the level-0 single-precision cycle leaves its result HERE as float2 (no fp64 copy); see fgmres
   int z_f32 = 1;             // PGX_Z_F32=0: the Z_j of the Krylov method in fp64 (A/B)
+  int f32_dbf16 = 1;         // PGX_F32_DBF16=0: the single-precision cycle's D(psi) stencil as float4 (A/B); default: packed bf16, 8 B
   bool dv_lean = false;  // the interior rows of the CSR D values are stale (residual_dev(with_d = 2)); a full fill clears it
   // operator of the solution space (aliases the P1 arrays above for degree 1)
   int32_t *s_rowptr = nullptr, *s_colm = nullptr;
@@ -967,12 +968,21 @@ static int setup_f32(pgx_handle* h) {
   for (int l = 0; l + 1 < nl; ++l) {
     GridLevel& L = h->lev[l];
     if (!L.uniform || L.n < std::max(h->f32_min, h->fused_min) || (h->tail_start > 0 && l >= h->tail_start)) continue;
-    DALLOC(L.Dq, L.n);
+    L.dbf16 = h->f32_dbf16 ? 1 : 0;
+    if (L.dbf16) {
+      uint2* q = nullptr;
+      DALLOC(q, L.n);
+      L.Dq = q;
+    } else {
+      float4* q = nullptr;
+      DALLOC(q, L.n);
+      L.Dq = q;
+    }
     DALLOC(L.xf, L.n);
     DALLOC(L.xf2, L.n);
     DALLOC(L.bf, L.n);
     for (float2* p : {L.xf, L.xf2, L.bf}) HIPCHK(hipMemsetAsync(p, 0, sizeof(float2) * L.n, h->st));
-    HIPCHK(hipMemsetAsync(L.Dq, 0, sizeof(float4) * L.n, h->st));
+    HIPCHK(hipMemsetAsync(L.Dq, 0, (L.dbf16 ? sizeof(uint2) : sizeof(float4)) * L.n, h->st));
     L.f32 = 1;
   }
   return PGX_OK;
@@ -1227,6 +1237,7 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_HOST_POLL")) h->host_poll = atoi(e);
   if (const char* e = pgx_tune("PGX_LAZY_NORM")) h->lazy_norm = atoi(e);
   if (const char* e = pgx_tune("PGX_Z_F32")) h->z_f32 = atoi(e);
+  if (const char* e = pgx_tune("PGX_F32_DBF16")) h->f32_dbf16 = atoi(e);
   if (const char* e = pgx_tune("PGX_SPMV_D4")) h->spmv_d4 = atoi(e);
   if (const char* e = pgx_tune("PGX_LEAN_D")) h->lean_d = atoi(e);
   if (const char* e = pgx_tune("PGX_MG_F32")) h->mg_f32 = atoi(e);
@@ -2986,7 +2997,7 @@ extern "C" int pgx_smoother_bench(pgx_handle* h, int reps, double* avg_ms, doubl
   HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
   *avg_ms = (double)ms / reps;
   if (bytes)  // D stencil + right-hand side + iterate + coarse correction + result
-    *bytes = f32 ? (16.0 * n + 8.0 * n + 8.0 * n + (C.f32 ? 8.0 : 16.0) * C.n + 8.0 * n) : 8.0 * (4.0 * n + 2.0 * n + 2.0 * n + 2.0 * C.n + 2.0 * n);
+    *bytes = f32 ? ((L.dbf16 ? 8.0 : 16.0) * n + 8.0 * n + 8.0 * n + (C.f32 ? 8.0 : 16.0) * C.n + 8.0 * n) : 8.0 * (4.0 * n + 2.0 * n + 2.0 * n + 2.0 * C.n + 2.0 * n);
   return PGX_OK;
 }
 

@@ -64,12 +64,16 @@ struct GridLevel {
   double *ru, *rp;           // residual scratch
   // Single-precision V-cycle (pgx_mg32.hip; round 4).  On a level with f32 != 0 the cycle reads the D(psi) stencil as ONE float4 per
   // vertex - (D(0,0), D(+1,0), D(0,+1), D(+1,+1)), repacked from Dh with every Jacobian - and keeps its vectors as interleaved
-  // (u, psi) float2: 40 B per vertex and smoother launch instead of 84.  The cycle is a preconditioner inside FGMRES (flexible);
+  // (u, psi) float2: 40 B (32 B with the bf16 form of Dq below) per vertex and smoother launch instead of 84.  The cycle is a preconditioner inside FGMRES (flexible);
   // the operator apply, the residuals and the Krylov space stay fp64.
   int f32;
   double4* Dd4;  // finest level only (else nullptr): the fp64 D stencil as ONE double4 per vertex for the matrix-free operator apply
                  // (two 16-byte loads per vertex instead of four 8-byte ones from four arrays); repacked with every Jacobian
-  float4* Dq;
+  // Dq: float4 per vertex, or (dbf16 != 0, the default: PGX_F32_DBF16) ONE 8-byte word - the same four values in the same order as
+  // two packed bf16 pairs, rounded to nearest even by k_f_pack_d.  The cycle is a preconditioner and does not use the low 16 bits
+  // of D: identical Krylov counts on the numpy twin (tools/mg32_study.py), 8 B per vertex less in every launch.
+  void* Dq;
+  int dbf16;
   float2 *xf, *xf2, *bf;
 };
 

@@ -3,11 +3,12 @@
 // run without tests on scalar K / M stencils, boundary tiles (scheduled first) through the general per-point code - but on HALF
 // the bytes: what the level-0 launches of the fp64 cycle wait for is the unique bytes of their coefficient and vector streams
 // (cycle stamps + timing experiments), not instructions, LDS or occupancy.  Here
-//   * D(psi) is ONE float4 per vertex (centre + the three forward links): one 16-byte load instead of four 8-byte loads from four
-//     arrays; the three mirrored links still come from the neighbours (DPP lane shift, LDS row hand-over);
+//   * D(psi) is ONE word per vertex (centre + the three forward links) - a float4, or by default (GridLevel::dbf16) two packed
+//     bf16 pairs in 8 bytes, widened to float once per launch - instead of four 8-byte loads from four arrays; the three mirrored
+//     links still come from the neighbours as floats (DPP lane shift, LDS row hand-over);
 //   * the cycle's vectors are interleaved (u, psi) float2: one 8-byte load / store per vertex and vector;
 //   * arithmetic in float: 20 registers of coefficients per image row instead of 36, LDS images of 8 B per vertex.
-// 40 B per vertex and smoother launch instead of 84.  The V-cycle is a preconditioner inside FGMRES, which is flexible; the operator
+// 32 B (bf16 D; 40 B with the float4 form) per vertex and smoother launch instead of 84.  The V-cycle is a preconditioner inside FGMRES, which is flexible; the operator
 // apply, the true residual that decides convergence and the Krylov space stay fp64, so the accuracy of the Newton steps is
 // untouched (tools/mg32_study.py: identical Krylov counts with a float32 cycle on the numpy twin).
 // The fp64 ends of the cycle: the first launch on the finest level reads the Krylov vector (fp64) and leaves its float2 copy for
@@ -37,15 +38,39 @@ __device__ __forceinline__ float lane_shr1f(float x) {  // the value of lane - 1
   return __int_as_float(v);
 }
 
-__global__ void __launch_bounds__(256) k_f_pack_d(int n, const dsten_t* __restrict__ Dh, float4* __restrict__ Dq) {
+// The storage of D(psi) on a single-precision level is a template parameter DT of every reader: float4, or uint2 = two packed bf16
+// pairs (x: D(0,0) low half, D(+1,0) high half; y: D(0,+1), D(+1,+1)).  Packing rounds to nearest even (v_cvt_pk_bf16_f32), so an
+// exact zero stays an exact zero; unpacking is one shift or mask per value.  From f_unpack_d on the readers work on a float4.
+typedef float f_v2f __attribute__((ext_vector_type(2)));
+typedef __bf16 f_v2bf __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t f_pack_bf16x2(float lo, float hi) {
+  const f_v2f f = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, f_v2bf));
+}
+__device__ __forceinline__ void f_pack_d(float4 q, float4& out) { out = q; }
+__device__ __forceinline__ void f_pack_d(float4 q, uint2& out) { out = make_uint2(f_pack_bf16x2(q.x, q.y), f_pack_bf16x2(q.z, q.w)); }
+__device__ __forceinline__ float4 f_unpack_d(float4 q) { return q; }
+__device__ __forceinline__ float4 f_unpack_d(uint2 w) {
+  return make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
+                     __uint_as_float(w.y & 0xffff0000u));
+}
+__device__ __forceinline__ void f_zero_d(float4& q) { q = make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ void f_zero_d(uint2& w) { w = make_uint2(0u, 0u); }
+
+template <class DT>
+__global__ void __launch_bounds__(256) k_f_pack_d(int n, const dsten_t* __restrict__ Dh, DT* __restrict__ Dq) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n) return;
   const float big = 1e30f;
-  Dq[v] = make_float4(fminf((float)Dh[v], big), fminf((float)Dh[(size_t)n + v], big), fminf((float)Dh[2 * (size_t)n + v], big),
-                      fminf((float)Dh[3 * (size_t)n + v], big));
+  f_pack_d(make_float4(fminf((float)Dh[v], big), fminf((float)Dh[(size_t)n + v], big), fminf((float)Dh[2 * (size_t)n + v], big),
+                       fminf((float)Dh[3 * (size_t)n + v], big)),
+           Dq[v]);
 }
 void pgxk_f_pack_d(hipStream_t st, const GridLevel& L) {
-  hipLaunchKernelGGL(k_f_pack_d, dim3((L.n + 255) / 256), dim3(256), 0, st, L.n, L.Dh, L.Dq);
+  if (L.dbf16)
+    hipLaunchKernelGGL(k_f_pack_d<uint2>, dim3((L.n + 255) / 256), dim3(256), 0, st, L.n, L.Dh, (uint2*)L.Dq);
+  else
+    hipLaunchKernelGGL(k_f_pack_d<float4>, dim3((L.n + 255) / 256), dim3(256), 0, st, L.n, L.Dh, (float4*)L.Dq);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -81,8 +106,9 @@ static inline FConst make_fconst(const GridLevel& L, double alpha) {
   return c;
 }
 // Stencil slots: 0:(0,0) 1:(+1,0) 2:(-1,0) 3:(0,+1) 4:(0,-1) 5:(+1,+1) 6:(-1,-1).  Links that leave the grid hold 0 in K, M and Dq.
+template <class DT>
 __device__ __forceinline__ void f_load_coef(int v, int i, int j, int nx, int ny, int n, const double* __restrict__ K,
-                                            const double* __restrict__ M, const float4* __restrict__ Dq, const FConst& sc,
+                                            const double* __restrict__ M, const DT* __restrict__ Dq, const FConst& sc,
                                             const uint8_t* __restrict__ mask, float alpha, FCoef& c) {
   const int sx = nx + 1;
   if (sc.uniform && i > 0 && i < nx && j > 0 && j < ny) {
@@ -98,14 +124,14 @@ __device__ __forceinline__ void f_load_coef(int v, int i, int j, int nx, int ny,
       c.mv[s] = (float)M[(size_t)s * n + v];
     }
   }
-  const float4 q = Dq[v];
+  const float4 q = f_unpack_d(Dq[v]);
   c.dv[0] = q.x;
   c.dv[1] = q.y;
   c.dv[3] = q.z;
   c.dv[5] = q.w;
-  c.dv[2] = (i > 0) ? Dq[v - 1].y : 0.f;
-  c.dv[4] = (j > 0) ? Dq[v - sx].z : 0.f;
-  c.dv[6] = (i > 0 && j > 0) ? Dq[v - sx - 1].w : 0.f;
+  c.dv[2] = (i > 0) ? f_unpack_d(Dq[v - 1]).y : 0.f;
+  c.dv[4] = (j > 0) ? f_unpack_d(Dq[v - sx]).z : 0.f;
+  c.dv[6] = (i > 0 && j > 0) ? f_unpack_d(Dq[v - sx - 1]).w : 0.f;
   c.rowbc = mask[v];
 }
 
@@ -166,7 +192,8 @@ struct FSmoothArgs {
   int nx, ny, n, nbnd, nxc, nyc, remap;
   RowmapGrid g;
   const double *K, *M;  // boundary rows only
-  const float4* Dq;
+  const void* Dq;  // DT of the kernel
+  int dbf16;
   const uint8_t *mask, *mask_c;
   const float2 *xf, *cf, *bf;
   const double *cdu, *cdp, *b64u, *b64p;
@@ -177,7 +204,7 @@ struct FSmoothArgs {
   FConst sc;
 };
 
-template <int TY, int K, bool FIRST, int IO, int CADD, int RR>
+template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR>
 __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float2* img0, float2* img1, float2* exch) {
   constexpr int W = 64, HALO = K + (RR ? 2 : 0), TX = W - 2 * HALO, H0 = TY + 2 * HALO, NW = F32_BLOCK / 64, R = (H0 + NW - 1) / NW;
   const int sx = A.nx + 1;
@@ -190,6 +217,8 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
   const float k0 = A.sc.k0, k1 = A.sc.k1, k3 = A.sc.k3, k5 = A.sc.k5, m0 = A.sc.m0, m1 = A.sc.m1, m3 = A.sc.m3, m5 = A.sc.m5;
   // A wave owns the SAME image rows in every sweep (lj = wave + NW k): their D links and right-hand side are loaded once, all
   // loads in flight together, and stay in registers for the K sweeps.
+  const DT* const Dq = static_cast<const DT*>(A.Dq);
+  DT dw[R];
   float4 dq[R];
   float2 rb[R];
 #pragma unroll
@@ -197,7 +226,7 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
     const int lj = wave + NW * k;
     if (lj < H0 - 1) {  // rows 1 .. H0-2 are updated; row 0 only hands its upward links to row 1
       const unsigned v = (unsigned)((j0 + lj) * sx + gi);
-      dq[k] = A.Dq[v];
+      dw[k] = Dq[v];
       if (lj >= 1) rb[k] = (IO == 1) ? make_float2((float)(A.b64u[v] * A.bscale), (float)(A.b64p[v] * A.bscale)) : A.bf[v];
     }
   }
@@ -220,7 +249,10 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
 #pragma unroll
   for (int k = 0; k < R; ++k) {
     const int lj = wave + NW * k;
-    if (lj < H0 - 1) exch[lj * W + lane] = make_float2(dq[k].z, dq[k].w);
+    if (lj < H0 - 1) {
+      dq[k] = f_unpack_d(dw[k]);  // once per launch, after the batch of loads
+      exch[lj * W + lane] = make_float2(dq[k].z, dq[k].w);
+    }
   }
   __syncthreads();
   // omega * inverse of the vertex block [[aK0, M0], [M0, -D0]] (det < 0: k0 > 0, d0 >= 0, m0 > 0): kept per row for the K sweeps,
@@ -336,7 +368,7 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
 // K sweeps; the mirrored D links come from the neighbours (out-of-grid entries are loaded as 0, and a link that leaves the grid is
 // stored as 0, so no per-link test is left); the 2x2 vertex block is inverted once per launch.  With TB = 2 an image has
 // 2 + 2K <= 8 rows: one row per wave.
-template <int TY, int TB, int K, bool FIRST, int IO, int CADD, int RR>
+template <class DT, int TY, int TB, int K, bool FIRST, int IO, int CADD, int RR>
 __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2* img0, float2* img1, float2* exch) {
   constexpr int W = 64, HALO = K + (RR ? 2 : 0), TX = W - 2 * HALO, H0 = TB + 2 * HALO, NSUB = TY / TB, NW = F32_BLOCK / 64,
                 R = (H0 + NW - 1) / NW;
@@ -364,6 +396,8 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int gi = i0 + lane;
   const bool own_lane = lane >= HALO && lane < W - HALO;
+  const DT* const Dq = static_cast<const DT*>(A.Dq);
+  DT dw[R];
   float4 dq[R];
   float2 rb[R], xa[R];
   float kv[R][7], mv[R][7];
@@ -373,7 +407,7 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
     const int lj = wave + NW * k, gj = j0 + lj;
     in[k] = lj < H0 && gi >= 0 && gi <= nx && gj >= 0 && gj <= ny;
     bc[k] = false;
-    dq[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    f_zero_d(dw[k]);
     rb[k] = xa[k] = make_float2(0.f, 0.f);
 #pragma unroll
     for (int t = 0; t < 7; ++t) {
@@ -382,7 +416,7 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
     }
     if (in[k]) {
       const int v = gj * sx + gi;
-      dq[k] = A.Dq[v];
+      dw[k] = Dq[v];
       bc[k] = A.mask[v] != 0;
       if (lj >= 1 && lj < H0 - 1) rb[k] = (IO == 1) ? make_float2((float)(A.b64u[v] * A.bscale), (float)(A.b64p[v] * A.bscale)) : A.bf[v];
       if (!FIRST) xa[k] = f_add_coarse<CADD>(A.xf[v], gi, gj, A.nxc, A.cf, A.cdu, A.cdp);
@@ -398,6 +432,7 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
 #pragma unroll
   for (int k = 0; k < R; ++k) {
     const int lj = wave + NW * k;
+    dq[k] = f_unpack_d(dw[k]);
     if (lj < H0) {
       if (!FIRST) img0[lj * W + lane] = make_float2(bc[k] ? 0.f : xa[k].x, xa[k].y);  // pre-masked: Dirichlet u reads as 0
       exch[lj * W + lane] = make_float2(dq[k].z, dq[k].w);
@@ -515,22 +550,22 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
 
 // ONE launch per smoother call: blocks [0, nbnd) are the boundary sub-tiles - they start first, so their long dependent-load
 // chains overlap with the interior tiles that follow - blocks [nbnd, nbnd + nfast) the interior tiles.
-template <int TY, int K, bool FIRST, int IO, int CADD, int RR>
+template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR>
 __global__ void __launch_bounds__(F32_BLOCK, RR ? 2 : F32_WAVES_EU) k_f_smooth(const FSmoothArgs A) {
   constexpr int W = 64, H0 = TY + 2 * (K + (RR ? 2 : 0)), PAD = W + 1;
   __shared__ float2 img_[3][H0 * W + 2 * PAD];  // guard bands: inactive edge lanes read (and discard) one entry outside a row;
                                                  // [2]: the (D(0,+1), D(+1,+1)) links every image row hands to the row above it
   const int blk = blockIdx.x;
   if (blk < A.nbnd)
-    f_smooth_bnd<TY, F32_TB, K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+    f_smooth_bnd<DT, TY, F32_TB, K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
   else
-    f_smooth_fast<TY, K, FIRST, IO, CADD, RR>(xcd_block(blk - A.nbnd, gridDim.x - A.nbnd, A.remap), A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+    f_smooth_fast<DT, TY, K, FIRST, IO, CADD, RR>(xcd_block(blk - A.nbnd, gridDim.x - A.nbnd, A.remap), A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
 }
 
 // last pre-smoothing launch + residual + restriction (no coarse correction, float2 result); TY >= 8: the first interior tile's
 // image (K + 2 halo rows) must start inside the grid
-template <int TY, int K>
-static void launch_f_smooth_rr(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
+template <class DT, int TY, int K>
+static void launch_f_smooth_rr_t(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
   const int rr = A.cbf ? 1 : 2;
   A.g = rowmap_grid<TY, K + 2>(A.nx, A.ny, fast_ok);
   const int nfast = A.g.nfx * A.g.nfy;
@@ -539,52 +574,68 @@ static void launch_f_smooth_rr(hipStream_t st, int first, FSmoothArgs& A, int fa
   if (first) {
     if (A.b64u) {
       if (rr == 1)
-        hipLaunchKernelGGL((k_f_smooth<TY, K, true, 1, 0, 1>), grid, block, 0, st, A);
+        hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 1, 0, 1>), grid, block, 0, st, A);
       else
-        hipLaunchKernelGGL((k_f_smooth<TY, K, true, 1, 0, 2>), grid, block, 0, st, A);
+        hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 1, 0, 2>), grid, block, 0, st, A);
     } else {
       if (rr == 1)
-        hipLaunchKernelGGL((k_f_smooth<TY, K, true, 0, 0, 1>), grid, block, 0, st, A);
+        hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 0, 0, 1>), grid, block, 0, st, A);
       else
-        hipLaunchKernelGGL((k_f_smooth<TY, K, true, 0, 0, 2>), grid, block, 0, st, A);
+        hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 0, 0, 2>), grid, block, 0, st, A);
     }
   } else {
     if (rr == 1)
-      hipLaunchKernelGGL((k_f_smooth<TY, K, false, 0, 0, 1>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 0, 0, 1>), grid, block, 0, st, A);
     else
-      hipLaunchKernelGGL((k_f_smooth<TY, K, false, 0, 0, 2>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 0, 0, 2>), grid, block, 0, st, A);
   }
 }
 
 template <int TY, int K>
-static void launch_f_smooth(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
+static void launch_f_smooth_rr(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
+  if (A.dbf16)
+    launch_f_smooth_rr_t<uint2, TY, K>(st, first, A, fast_ok);
+  else
+    launch_f_smooth_rr_t<float4, TY, K>(st, first, A, fast_ok);
+}
+
+template <class DT, int TY, int K>
+static void launch_f_smooth_t(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
   A.g = rowmap_grid<TY, K>(A.nx, A.ny, fast_ok);
   const int nfast = A.g.nfx * A.g.nfy;
   A.nbnd = (A.g.ntx * A.g.nty - nfast) * (TY / F32_TB);  // boundary tiles: sub-tiles of F32_TB rows
   const dim3 grid(A.nbnd + nfast), block(F32_BLOCK);
   if (first) {
     if (A.b64u)
-      hipLaunchKernelGGL((k_f_smooth<TY, K, true, 1, 0, 0>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 1, 0, 0>), grid, block, 0, st, A);
     else
-      hipLaunchKernelGGL((k_f_smooth<TY, K, true, 0, 0, 0>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 0, 0, 0>), grid, block, 0, st, A);
     return;
   }
   const int cadd = A.cf ? 1 : (A.cdu ? 2 : 0);
   if (A.y64u) {
     if (cadd == 0)
-      hipLaunchKernelGGL((k_f_smooth<TY, K, false, 2, 0, 0>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 2, 0, 0>), grid, block, 0, st, A);
     else if (cadd == 1)
-      hipLaunchKernelGGL((k_f_smooth<TY, K, false, 2, 1, 0>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 2, 1, 0>), grid, block, 0, st, A);
     else
-      hipLaunchKernelGGL((k_f_smooth<TY, K, false, 2, 2, 0>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 2, 2, 0>), grid, block, 0, st, A);
   } else {
     if (cadd == 0)
-      hipLaunchKernelGGL((k_f_smooth<TY, K, false, 0, 0, 0>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 0, 0, 0>), grid, block, 0, st, A);
     else if (cadd == 1)
-      hipLaunchKernelGGL((k_f_smooth<TY, K, false, 0, 1, 0>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 0, 1, 0>), grid, block, 0, st, A);
     else
-      hipLaunchKernelGGL((k_f_smooth<TY, K, false, 0, 2, 0>), grid, block, 0, st, A);
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 0, 2, 0>), grid, block, 0, st, A);
   }
+}
+
+template <int TY, int K>
+static void launch_f_smooth(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
+  if (A.dbf16)
+    launch_f_smooth_t<uint2, TY, K>(st, first, A, fast_ok);
+  else
+    launch_f_smooth_t<float4, TY, K>(st, first, A, fast_ok);
 }
 
 static int f32_tile_rows(const GridLevel& L) {
@@ -612,6 +663,7 @@ void pgxk_f_smooth(hipStream_t st, int K, int first, const GridLevel& L, double 
   A.K = L.K;
   A.M = L.M;
   A.Dq = L.Dq;
+  A.dbf16 = L.dbf16;
   A.mask = L.mask;
   A.xf = first ? nullptr : xf;
   A.cf = first ? nullptr : cf;
@@ -675,7 +727,8 @@ struct FRrArgs {
   int nx, ny, n, nbnd, nxc, nyc, remap;
   RrGrid g;
   const double *K, *M;
-  const float4* Dq;
+  const void* Dq;  // DT of the kernel
+  int dbf16;
   const uint8_t *mask, *mask_c;
   const float2 *xf, *bf;
   float2* cbf;
@@ -684,7 +737,7 @@ struct FRrArgs {
   FConst sc;
 };
 
-template <bool CB64>
+template <class DT, bool CB64>
 __device__ __forceinline__ void f_rr_fast(int tx, int ty, const FRrArgs& A, float2* ximg, float2* rimg, float2* exch) {
   constexpr int W = 64, CX = 30, CY = 8, HX = 2 * CY + 3, HR = 2 * CY + 1, NW = F32_BLOCK / 64, R = (HX + NW - 1) / NW;
   const int sx = A.nx + 1, sxc = A.nxc + 1;
@@ -695,7 +748,9 @@ __device__ __forceinline__ void f_rr_fast(int tx, int ty, const FRrArgs& A, floa
   const int gi = i0 + lane;
   const bool act = lane >= 1 && lane < W - 1;
   // every global load of the wave's (up to three) rows in flight before the first LDS store
+  const DT* const Dq = static_cast<const DT*>(A.Dq);
   float2 xa[R], rb[R];
+  DT dw[R];
   float4 dq[R];
 #pragma unroll
   for (int k = 0; k < R; ++k) {
@@ -703,7 +758,7 @@ __device__ __forceinline__ void f_rr_fast(int tx, int ty, const FRrArgs& A, floa
     if (lj < HX) {
       const unsigned v = (unsigned)((j0 + lj) * sx + gi);
       xa[k] = A.xf[v];
-      if (lj <= HR) dq[k] = A.Dq[v];
+      if (lj <= HR) dw[k] = Dq[v];
       if (lj >= 1 && lj <= HR) rb[k] = A.bf[v];
     }
   }
@@ -711,7 +766,10 @@ __device__ __forceinline__ void f_rr_fast(int tx, int ty, const FRrArgs& A, floa
   for (int k = 0; k < R; ++k) {
     const int lj = wave + NW * k;
     if (lj < HX) ximg[lj * W + lane] = xa[k];
-    if (lj <= HR) exch[lj * W + lane] = make_float2(dq[k].z, dq[k].w);
+    if (lj <= HR) {
+      dq[k] = f_unpack_d(dw[k]);
+      exch[lj * W + lane] = make_float2(dq[k].z, dq[k].w);
+    }
   }
   __syncthreads();
   const float k0 = A.sc.k0, k1 = A.sc.k1, k3 = A.sc.k3, k5 = A.sc.k5, m0 = A.sc.m0, m1 = A.sc.m1, m3 = A.sc.m3, m5 = A.sc.m5;
@@ -751,7 +809,7 @@ __device__ __forceinline__ void f_rr_fast(int tx, int ty, const FRrArgs& A, floa
 
 // boundary tiles, cut into sub-tiles of CYB = 2 coarse rows (x image of 7 fine rows: one per wave), register-resident like the
 // boundary tiles of the smoother (f_smooth_bnd): one batch of loads, no dependent chains
-template <bool CB64>
+template <class DT, bool CB64>
 __device__ __forceinline__ void f_rr_bnd(int tx, int ty, int sub, const FRrArgs& A, float2* ximg, float2* rimg, float2* exch) {
   constexpr int W = 64, CX = 30, CY = 8, CYB = F32_RR_CYB, HX = 2 * CYB + 3, HR = 2 * CYB + 1, NW = F32_BLOCK / 64;
   static_assert(HX <= NW && CY % CYB == 0, "one image row per wave");
@@ -763,7 +821,8 @@ __device__ __forceinline__ void f_rr_bnd(int tx, int ty, int sub, const FRrArgs&
   const int gi = i0 + lane, lj = wave, gj = j0 + lj;
   const bool in = lj < HX && gi >= 0 && gi <= nx && gj >= 0 && gj <= ny;
   const bool act = lane >= 1 && lane < W - 1;
-  float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
+  DT dw;
+  f_zero_d(dw);
   float2 rb = make_float2(0.f, 0.f), xa = make_float2(0.f, 0.f);
   float kv[7], mv[7];
   bool bc = false;
@@ -776,7 +835,7 @@ __device__ __forceinline__ void f_rr_bnd(int tx, int ty, int sub, const FRrArgs&
     const int v = gj * sx + gi;
     xa = A.xf[v];
     bc = A.mask[v] != 0;
-    if (lj <= HR) dq = A.Dq[v];
+    if (lj <= HR) dw = static_cast<const DT*>(A.Dq)[v];
     if (lj >= 1 && lj <= HR) {
       rb = A.bf[v];
       if (!(A.sc.uniform && gi > 0 && gi < nx && gj > 0 && gj < ny)) {
@@ -788,6 +847,7 @@ __device__ __forceinline__ void f_rr_bnd(int tx, int ty, int sub, const FRrArgs&
       }
     }
   }
+  const float4 dq = f_unpack_d(dw);
   if (lj < HX) {
     ximg[lj * W + lane] = make_float2(bc ? 0.f : xa.x, xa.y);  // pre-masked image
     exch[lj * W + lane] = make_float2(dq.z, dq.w);
@@ -826,7 +886,7 @@ __device__ __forceinline__ void f_rr_bnd(int tx, int ty, int sub, const FRrArgs&
   }
 }
 
-template <bool CB64>
+template <class DT, bool CB64>
 __global__ void __launch_bounds__(F32_BLOCK) k_f_resid_restrict(const FRrArgs A) {
   constexpr int W = 64, CY = 8, HX = 2 * CY + 3, HR = 2 * CY + 1, PAD = W + 1;
   __shared__ float2 ximg_[HX * W + 2 * PAD], rimg_[HR * W + 2 * PAD], exch_[HX * W + 2 * PAD];
@@ -850,10 +910,10 @@ __global__ void __launch_bounds__(F32_BLOCK) k_f_resid_restrict(const FRrArgs A)
       ty = g.nfy + 1 + b / g.ntx;
       tx = b % g.ntx;
     }
-    f_rr_bnd<CB64>(tx, ty, sub, A, ximg_ + PAD, rimg_ + PAD, exch_ + PAD);
+    f_rr_bnd<DT, CB64>(tx, ty, sub, A, ximg_ + PAD, rimg_ + PAD, exch_ + PAD);
   } else {
     b = xcd_block(b - A.nbnd, gridDim.x - A.nbnd, A.remap);
-    f_rr_fast<CB64>(1 + b % A.g.nfx, 1 + b / A.g.nfx, A, ximg_ + PAD, rimg_ + PAD, exch_ + PAD);
+    f_rr_fast<DT, CB64>(1 + b % A.g.nfx, 1 + b / A.g.nfx, A, ximg_ + PAD, rimg_ + PAD, exch_ + PAD);
   }
 }
 
@@ -870,6 +930,7 @@ void pgxk_f_resid_restrict(hipStream_t st, const GridLevel& L, double alpha, con
   A.K = L.K;
   A.M = L.M;
   A.Dq = L.Dq;
+  A.dbf16 = L.dbf16;
   A.mask = L.mask;
   A.mask_c = C.mask;
   A.xf = xf;
@@ -892,8 +953,15 @@ void pgxk_f_resid_restrict(hipStream_t st, const GridLevel& L, double alpha, con
   const int nfast = g.nfx * g.nfy;
   A.nbnd = (g.ntx * g.nty - nfast) * (CY / F32_RR_CYB);  // boundary tiles: sub-tiles of F32_RR_CYB coarse rows
   const dim3 grid(A.nbnd + nfast), block(F32_BLOCK);
-  if (cb64u)
-    hipLaunchKernelGGL(k_f_resid_restrict<true>, grid, block, 0, st, A);
-  else
-    hipLaunchKernelGGL(k_f_resid_restrict<false>, grid, block, 0, st, A);
+  if (L.dbf16) {
+    if (cb64u)
+      hipLaunchKernelGGL((k_f_resid_restrict<uint2, true>), grid, block, 0, st, A);
+    else
+      hipLaunchKernelGGL((k_f_resid_restrict<uint2, false>), grid, block, 0, st, A);
+  } else {
+    if (cb64u)
+      hipLaunchKernelGGL((k_f_resid_restrict<float4, true>), grid, block, 0, st, A);
+    else
+      hipLaunchKernelGGL((k_f_resid_restrict<float4, false>), grid, block, 0, st, A);
+  }
 }

@@ -32,10 +32,11 @@ for what in "$@"; do
       rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_pwrite -o w -- python3 tools/p2_spmv_bench.py 2048 > $OUT/pmc_pwrite.log 2>&1 || exit 1
       python3 tools/pmc_summary.py --kernel "k_p2st_apply_lds<double" --traffic --cells 2048 --algorithmic-bytes 2074284400 \
         --out $OUT/p2stspmv_pmc_traffic.json $OUT/pmc_pfetch $OUT/pmc_pwrite > /dev/null || exit 1 ;;
-    fsmooth)  # the time-dominant kernel: the finest level's single-precision smoother launch, 40 B x 2049^2 vertices (+ coarse correction)
-      rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_ffetch -o f -- python3 tools/smoother_bench.py 2048 > $OUT/pmc_ffetch.log 2>&1 || exit 1
-      rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fwrite -o w -- python3 tools/smoother_bench.py 2048 > $OUT/pmc_fwrite.log 2>&1 || exit 1
-      python3 tools/pmc_summary.py --kernel "k_f_smooth<16, 3, false, 0, 1, 0>" --traffic --cells 2048 --algorithmic-bytes 176341040 \
+    fsmooth)  # the time-dominant kernel: the finest level's single-precision smoother launch, 32 B x 2049^2 vertices (bf16 D stencil;
+              # + 8 B x 1025^2 coarse correction); counters only, no tracing in these passes
+      rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_ffetch -o f -- python3 tools/smoother_bench.py 2048 > $OUT/pmc_ffetch.log 2>&1 || exit 1
+      rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_fwrite -o w -- python3 tools/smoother_bench.py 2048 > $OUT/pmc_fwrite.log 2>&1 || exit 1
+      python3 tools/pmc_summary.py --kernel "2u>, 16, 3, false, 0, 1, 0>" --traffic --cells 2048 --algorithmic-bytes 142753832 \
         --out $OUT/fsmooth_pmc_traffic.json $OUT/pmc_ffetch $OUT/pmc_fwrite > /dev/null || exit 1 ;;
     smoother)
       rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_LDS GRBM_GUI_ACTIVE \
