@@ -20,6 +20,7 @@
  *                         (lvpp twin: src/lvpp/problem.py:54-77,110)
  *   pgx_gc_newton_solve   problem.solve() (:179) with SNES reason / iteration count (:180-183)
  *   pgx_gc_l2_increment   assemble_scalar(dot(diff, diff) dx) + allreduce + sqrt (:164-166,184-186)
+ *   pgx_gc_eval_cells     the DG0 active-set indicators and the DG_(k-1) output fields grad(u), phi psi/sqrt(1+|psi|^2), phi (:134-165,193-204)
  * Conventions as in pgx.h: 0 or a negative PGX_E* code; caller owns host buffers; handle owns device memory; synchronous.
  * The Newton linear systems are solved by the sparse direct solver of pgx_nd.h (the reference's pc_type lu) with
  * iterative refinement on the exact operator.  There is no CPU fallback.
@@ -99,6 +100,21 @@ int pgx_gc_spmv(pgx_gc_handle* h, const double* x, double* y);
 /* opts: snes_* and ksp_rtol (true relative residual of the refined LU solve; 0 = 1e-10, the target of example 01's Newton solves; 1e-12 until round 5), ksp_max_it (refinement steps) */
 int pgx_gc_newton_solve(pgx_gc_handle* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its);
 int pgx_gc_l2_increment(pgx_gc_handle* h, double* out); /* || u - u_prev ||_L2 */
+/* Evaluation of the device state h->x at points of every cell: one pass, no handle state changes.  On a handle of pgx_gc_create_dist
+ * it runs on the rank's replica of the iterate without communication (untested on more than one rank). */
+typedef struct {
+  int32_t npts;          /* evaluation points per cell, 1..64 */
+  const double* pts;     /* [npts][2] reference coordinates; used by handles of pgx_gc_create / pgx_gc_create_dist (built-in P2/P1) */
+  const double* tab_Nu;  /* [npts][nu]    } required by handles of pgx_gc_create_general (the library does not know the basis), */
+  const double* tab_dNu; /* [npts][nu][2] } the layout of pgx_gc_spaces' tables; NULL otherwise                                 */
+  const double* tab_Np;  /* [npts][np]    }                                                                                     */
+} pgx_gc_points;
+/* per cell and point: grad u, the feasible gradient phi psi/sqrt(1+|psi|^2), phi (the P_k interpolant), and the flags
+ * active = (|grad u| - phi >= 0) (:136-137), feasible_active = (|feasible gradient| - phi > -1e-8) (:140-144).  Any output may be NULL.
+ * npts = 1 at the cell midpoint - (1/3, 1/3) on triangles, (1/2, 1/2) on quadrilaterals - is the DG0 interpolation of :134-146, the
+ * latent element's nodes the DG_(k-1) interpolation of :149-165. */
+int pgx_gc_eval_cells(pgx_gc_handle* h, const pgx_gc_points* p, double* grad_u /* [nc][npts][2] */, double* feas /* [nc][npts][2] */,
+                      double* phi /* [nc][npts] */, uint8_t* active /* [nc][npts] */, uint8_t* feasible_active /* [nc][npts] */);
 /* accumulated device ms since the last reset: [0] residual [1] jacobian [2] LU factor [3] LU solves [4] spmv [5] total */
 int pgx_gc_profile(pgx_gc_handle* h, int enable, double ms[6]);
 

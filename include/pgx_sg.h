@@ -20,6 +20,7 @@
  *   pgx_sg_newton_solve   solver.solve() (:333) with reason / iteration count (:334-335); tolerances as set by
  *                         solver.solver.setTolerances(atol=, rtol=) (:331-332)
  *   pgx_sg_u_increment    ||u - u_prev||_2 (vector 2-norm, :337-339)
+ *   pgx_sg_penetration / pgx_sg_violation / pgx_sg_von_mises   what the script reports about an iterate (:293-321, 346-350)
  * Conventions as in pgx.h.  Linear solves: sparse LU of pgx_nd.h + iterative refinement.  No CPU fallback.
  */
 #ifndef PGX_SG_H
@@ -111,6 +112,18 @@ int pgx_sg_csr_export(pgx_sg_handle* h, int64_t* nrows, int64_t* nnz, int32_t* r
 int pgx_sg_spmv(pgx_sg_handle* h, const double* x, double* y);
 int pgx_sg_newton_solve(pgx_sg_handle* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its);
 int pgx_sg_u_increment(pgx_sg_handle* h, double* out);
+/* Diagnostics of the device state h->x: one pass each, no handle state changes (a Jacobian filled before stays valid).  On a handle
+ * of pgx_sg_create_dist they run on the rank's replica of the iterate WITHOUT communication and so need not be called collectively
+ * (untested on more than one rank). */
+/* sqrt( int_Gamma max(u.n_g - g, 0)^2 ds ), n_g = -e_z, g = x_z - gap, with the facet rule of pgx_sg_problem (:307-314); curved handles:
+ * surface element and z from pgx_sg_curved.facet_geo.  Fixed-shape reduction: bitwise reproducible. */
+int pgx_sg_penetration(pgx_sg_handle* h, double* l2);
+/* u.n_g - g = -u_z - (z - gap) at every node (Expression at V's interpolation points, :307-308, 349) */
+int pgx_sg_violation(pgx_sg_handle* h, double* out /* [n_nodes] */);
+/* sqrt(3/2 s:s), s = sigma(u) - tr(sigma(u))/3 I, at the cell's own nodes = DG_degree interpolation (:296-302, 346).  Affine cells of all
+ * four element flavours.  LIMITATION: PGX_EINVAL on a handle of pgx_sg_create_curved - it holds the cell geometry at the quadrature
+ * points only, not at the nodes. */
+int pgx_sg_von_mises(pgx_sg_handle* h, double* out /* [n_cells][nodes per cell], the node order of pgx_sg_mesh.cells */);
 int pgx_sg_profile(pgx_sg_handle* h, int enable, double ms[6]);
 
 #ifdef __cplusplus

@@ -128,6 +128,16 @@ class pgx_gc_spaces(C.Structure):  # include/pgx_gc.h: general primal degree
     ]
 
 
+class pgx_gc_points(C.Structure):  # include/pgx_gc.h: evaluation points of pgx_gc_eval_cells
+    _fields_ = [
+        ("npts", C.c_int32),
+        ("pts", c_double_p),
+        ("tab_Nu", c_double_p),
+        ("tab_dNu", c_double_p),
+        ("tab_Np", c_double_p),
+    ]
+
+
 class pgx_sg_mesh(C.Structure):  # include/pgx_sg.h
     _fields_ = [
         ("n_vertices", C.c_int32),
@@ -296,6 +306,8 @@ SYMBOLS = [
     ("pgx_gc_lu_is_symmetric", C.c_int, [_H]),
     ("pgx_gc_num_dofs", C.c_int, [_H, c_int64_p]),
     ("pgx_gc_l2_increment", C.c_int, [_H, c_double_p]),
+    ("pgx_gc_eval_cells", C.c_int,
+     [_H, C.POINTER(pgx_gc_points), c_double_p, c_double_p, c_double_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     # example 02: Signorini contact (include/pgx_sg.h)
     ("pgx_sg_create", C.c_int, [C.POINTER(pgx_sg_mesh), C.POINTER(pgx_sg_problem), C.c_int, C.POINTER(_H)]),
     ("pgx_sg_create_dist", C.c_int, [C.POINTER(pgx_sg_mesh), C.POINTER(pgx_sg_problem), _COMM, C.c_int, C.POINTER(_H)]),
@@ -306,6 +318,9 @@ SYMBOLS = [
     ("pgx_sg_num_dofs", C.c_int, [_H, c_int64_p, c_int64_p]),
     ("pgx_sg_contact_vertices", C.c_int, [_H, c_int32_p]),
     ("pgx_sg_u_increment", C.c_int, [_H, c_double_p]),
+    ("pgx_sg_penetration", C.c_int, [_H, c_double_p]),
+    ("pgx_sg_violation", C.c_int, [_H, c_double_p]),
+    ("pgx_sg_von_mises", C.c_int, [_H, c_double_p]),
     # example 05: thermoforming QVI (include/pgx_qvi.h)
     ("pgx_qvi_create", C.c_int, [C.POINTER(pgx_mesh), C.POINTER(pgx_qvi_problem), C.c_int, C.POINTER(_H)]),
     ("pgx_qvi_num_dofs", C.c_int, [_H, c_int64_p]),

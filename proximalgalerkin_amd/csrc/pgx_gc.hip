@@ -36,6 +36,8 @@ struct pgx_gc_handle : MixedBase {
   int gen = 0, NU = 6, NP = 3;
   int32_t *cdofs_p = nullptr, *cells3 = nullptr;  // latent cell dofs; vertex triples (affine geometry)
   double *tNu = nullptr, *tdNu = nullptr, *tNp = nullptr;
+  void* ev = nullptr;  // pgx_gc_eval_cells: points / tables and the outputs, grown on demand
+  size_t ev_len = 0;
   pgx_gc_handle() : MixedBase("pgx_gc") {}
   void residual_dev(const double* xin, double* Fout) override;
   void jacobian_dev(const double* xin) override;
@@ -480,6 +482,80 @@ __global__ __launch_bounds__(256) void k_gcg_l2(GcgArgs A, const double* __restr
 }
 
 static GcgArgs gcg_args(const pgx_gc_handle* h);
+
+// ------------------------------------------------------------------------------------------------------------------
+// evaluation at points of every cell (pgx_gc_eval_cells; gradient_constraint_dolfinx.py:134-165): one thread per (cell, point), so that
+// every output array is written contiguously.  Any output pointer may be null.
+// ------------------------------------------------------------------------------------------------------------------
+struct GcEvalOut {
+  double *grad_u, *feas, *phi;
+  uint8_t *active, *feas_active;
+};
+
+__device__ inline void gc_eval_store(const GcEvalOut& o, int64_t i, double gux, double guy, double phq, double pxq, double pyq) {
+  // the reference's expressions as stated: phi psi / sqrt(1 + psi.psi); sqrt(v.v) - phi against 0 (>=) and -1e-8 (>)
+  const double s = sqrt(1.0 + (pxq * pxq + pyq * pyq));
+  const double fx = phq * pxq / s, fy = phq * pyq / s;
+  if (o.grad_u) reinterpret_cast<double2*>(o.grad_u)[i] = make_double2(gux, guy);
+  if (o.feas) reinterpret_cast<double2*>(o.feas)[i] = make_double2(fx, fy);
+  if (o.phi) o.phi[i] = phq;
+  if (o.active) o.active[i] = (sqrt(gux * gux + guy * guy) - phq >= 0.0) ? 1 : 0;
+  if (o.feas_active) o.feas_active[i] = (sqrt(fx * fx + fy * fy) - phq > -1e-8) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(128) void k_gc_eval(int nc, int n2, int nv, const int32_t* __restrict__ cdofs, const double* __restrict__ coords,
+                                                 const double* __restrict__ phi, const double* __restrict__ x, int npts,
+                                                 const double* __restrict__ pts, GcEvalOut o) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)nc * npts) return;
+  const int c = (int)(i / npts), p = (int)(i % npts);
+  const int32_t* cd = cdofs + 6 * (size_t)c;
+  const GcGeom g = gc_geom(coords, cd);
+  double l[3], N[6], G[6][2];
+  gc_tab(pts[2 * p], pts[2 * p + 1], g, l, N, G);
+  double gux = 0, guy = 0, phq = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    const double ua = x[cd[a]];
+    gux += ua * G[a][0];
+    guy += ua * G[a][1];
+    phq += phi[cd[a]] * N[a];
+  }
+  double pxq = 0, pyq = 0;
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    pxq += x[n2 + cd[b]] * l[b];
+    pyq += x[n2 + nv + cd[b]] * l[b];
+  }
+  gc_eval_store(o, i, gux, guy, phq, pxq, pyq);
+}
+
+// general degree: A.tNu / A.tdNu / A.tNp are the tables at the EVALUATION points here
+__global__ __launch_bounds__(128) void k_gcg_eval(GcgArgs A, const double* __restrict__ phi, const double* __restrict__ x, int npts,
+                                                  GcEvalOut o) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)A.nc * npts) return;
+  const int c = (int)(i / npts), p = (int)(i % npts);
+  const int NU = A.NU, NP = A.NP;
+  const GcGeom g = gcg_geom(A, c);
+  const int32_t* cu = A.cdu + (size_t)NU * c;
+  const int32_t* cp = A.cdp + (size_t)NP * c;
+  const double* Nu = A.tNu + (size_t)p * NU;
+  const double* dN = A.tdNu + (size_t)p * NU * 2;
+  const double* Np = A.tNp + (size_t)p * NP;
+  double gux = 0, guy = 0, phq = 0, pxq = 0, pyq = 0;
+  for (int a = 0; a < NU; ++a) {
+    const double ua = x[cu[a]];
+    gux += ua * (dN[2 * a] * g.inv[0][0] + dN[2 * a + 1] * g.inv[1][0]);
+    guy += ua * (dN[2 * a] * g.inv[0][1] + dN[2 * a + 1] * g.inv[1][1]);
+    phq += phi[cu[a]] * Nu[a];
+  }
+  for (int b = 0; b < NP; ++b) {
+    pxq += x[A.n2 + cp[b]] * Np[b];
+    pyq += x[A.n2 + A.nv + cp[b]] * Np[b];
+  }
+  gc_eval_store(o, i, gux, guy, phq, pxq, pyq);
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // host: pattern, destination tables, create
@@ -1056,6 +1132,64 @@ extern "C" int pgx_gc_l2_increment(pgx_gc_handle* h, double* out) {
   else
     hipLaunchKernelGGL(k_gc_l2, dim3(GC_RED), dim3(256), 0, h->st, h->nc, h->cdofs, h->coords, h->x, h->xk, h->Q, h->partials);
   return mx_partials_sqrt(h, out);
+}
+
+extern "C" int pgx_gc_eval_cells(pgx_gc_handle* h, const pgx_gc_points* p, double* grad_u, double* feas, double* phi, uint8_t* active,
+                                 uint8_t* feasible_active) {
+  MXNEED(h);
+  if (!p || p->npts < 1 || p->npts > 64 || (h->gen ? (!p->tab_Nu || !p->tab_dNu || !p->tab_Np) : !p->pts)) {
+    h->err = h->gen ? "pgx_gc_eval_cells: 1..64 points and the three basis tables at them (handle of pgx_gc_create_general)"
+                    : "pgx_gc_eval_cells: 1..64 points with their reference coordinates";
+    return PGX_EINVAL;
+  }
+  const int np = p->npts;
+  const size_t n = (size_t)h->nc * np;
+  // one buffer: [tables | grad_u | feas | phi | active | feasible_active], the outputs only where asked for
+  const size_t ntab = h->gen ? (size_t)np * (3 * (size_t)h->NU + h->NP) : 2 * (size_t)np;
+  size_t len = (sizeof(double) * ntab + 15) / 16 * 16;  // (the vector outputs are stored as double2)
+  const size_t o_gu = len;
+  len += grad_u ? sizeof(double) * 2 * n : 0;
+  const size_t o_fe = len;
+  len += feas ? sizeof(double) * 2 * n : 0;
+  const size_t o_ph = len;
+  len += phi ? sizeof(double) * n : 0;
+  const size_t o_ac = len;
+  len += active ? n : 0;
+  const size_t o_fa = len;
+  len += feasible_active ? n : 0;
+  if (len > h->ev_len) {
+    uint8_t* q = nullptr;
+    GCALLOC(q, len);
+    h->ev = q, h->ev_len = len;
+  }
+  uint8_t* base = (uint8_t*)h->ev;
+  double* tab = (double*)base;
+  GcEvalOut o{};
+  o.grad_u = grad_u ? (double*)(base + o_gu) : nullptr;
+  o.feas = feas ? (double*)(base + o_fe) : nullptr;
+  o.phi = phi ? (double*)(base + o_ph) : nullptr;
+  o.active = active ? base + o_ac : nullptr;
+  o.feas_active = feasible_active ? base + o_fa : nullptr;
+  const dim3 grid((unsigned)((n + 127) / 128)), block(128);
+  if (h->gen) {
+    const size_t nNu = (size_t)np * h->NU, nNp = (size_t)np * h->NP;
+    GCHIP(hipMemcpyAsync(tab, p->tab_Nu, sizeof(double) * nNu, hipMemcpyHostToDevice, h->st));
+    GCHIP(hipMemcpyAsync(tab + nNu, p->tab_dNu, sizeof(double) * 2 * nNu, hipMemcpyHostToDevice, h->st));
+    GCHIP(hipMemcpyAsync(tab + 3 * nNu, p->tab_Np, sizeof(double) * nNp, hipMemcpyHostToDevice, h->st));
+    GcgArgs A = gcg_args(h);
+    A.tNu = tab, A.tdNu = tab + nNu, A.tNp = tab + 3 * nNu;
+    hipLaunchKernelGGL(k_gcg_eval, grid, block, 0, h->st, A, h->phi, h->x, np, o);
+  } else {
+    GCHIP(hipMemcpyAsync(tab, p->pts, sizeof(double) * 2 * np, hipMemcpyHostToDevice, h->st));
+    hipLaunchKernelGGL(k_gc_eval, grid, block, 0, h->st, h->nc, h->n2, h->nv, h->cdofs, h->coords, h->phi, h->x, np, tab, o);
+  }
+  if (grad_u) GCHIP(hipMemcpyAsync(grad_u, o.grad_u, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, h->st));
+  if (feas) GCHIP(hipMemcpyAsync(feas, o.feas, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, h->st));
+  if (phi) GCHIP(hipMemcpyAsync(phi, o.phi, sizeof(double) * n, hipMemcpyDeviceToHost, h->st));
+  if (active) GCHIP(hipMemcpyAsync(active, o.active, n, hipMemcpyDeviceToHost, h->st));
+  if (feasible_active) GCHIP(hipMemcpyAsync(feasible_active, o.feas_active, n, hipMemcpyDeviceToHost, h->st));
+  GCHIP(hipStreamSynchronize(h->st));
+  return PGX_OK;
 }
 
 extern "C" int pgx_gc_profile(pgx_gc_handle* h, int enable, double ms[6]) { return mx_profile(h, enable, ms); }

@@ -127,7 +127,9 @@ int mx_alloc_state(MixedBase* h);  // state vectors, reduction scratch, events; 
 int mx_in(MixedBase* h, double* dst, const double* src, int64_t len = 0);  // host -> device, len = 0: ntot
 int mx_norm(MixedBase* h, const double* v, double* out, int64_t len = 0);   // 2-norm (rank 0's value on every rank)
 void mx_axpby(MixedBase* h, double a, const double* x, double b, double* y, int64_t len = 0);  // y = a x + b y on the stream
-int mx_partials_sqrt(MixedBase* h, double* out);  // sqrt(max(sum of h->partials, 0)): the tail of the families' increment norms
+// sqrt(max(sum of h->partials, 0)): the tail of the families' increment norms.  sync = false: no agreement on rank 0's value, i.e. no
+// communication on a distributed handle (the diagnostics of pgx_sg.h, evaluated on the replicated iterate)
+int mx_partials_sqrt(MixedBase* h, double* out, bool sync = true);
 // the entry points of every family: pgx_xx_destroy, set/get_state, set/get_prev, advance_prev, set_alpha, residual,
 // jacobian_fill, csr_export, spmv, newton_solve and profile
 void mx_destroy(MixedBase* h);

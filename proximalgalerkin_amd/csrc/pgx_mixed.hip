@@ -849,9 +849,9 @@ static int mx_newton_solve_l2(MixedBase* h, const pgx_snes_opts* opts, int* reas
 }
 
 // sqrt(max(sum of the MX_RED partials a family's reduction kernel left in h->partials, 0)), the same value on every rank
-int mx_partials_sqrt(MixedBase* h, double* out) {
+int mx_partials_sqrt(MixedBase* h, double* out, bool sync) {
   hipLaunchKernelGGL(k_mx_final, dim3(1), dim3(256), 0, h->st, MX_RED, h->partials, h->d_out);
-  {
+  if (sync) {
     const int rcs = mx_sync_scalar(h);  // distributed handles: the loop's stopping test must agree on every rank
     if (rcs) return rcs;
   }

@@ -40,6 +40,14 @@ struct pgx_sg_handle : MixedBase {
   std::vector<int32_t> cverts;
   bool partitioned = false;  // distributed handle: this rank assembled the elasticity blocks of its slab of cells only
   int nc_owned = 0;
+  // diagnostics (pgx_sg_penetration / violation / von_mises): ALL cells of the mesh, the reference gradients of the cell basis at the
+  // cell's own reference nodes [npc][npc][3], the four local nodes spanning the affine cell, and an output buffer grown on demand
+  int32_t* cells = nullptr;
+  double* vm_tab = nullptr;
+  int vm_g[4] = {0, 1, 2, 3};
+  bool curved = false;
+  double* diag = nullptr;
+  size_t diag_len = 0;
   pgx_sg_handle() : MixedBase("pgx_sg") {}
   void residual_dev(const double* xin, double* Fout) override;
   void jacobian_dev(const double* xin) override;
@@ -352,6 +360,124 @@ __global__ __launch_bounds__(256) void k_sg_resid_rows(int64_t ntot, int nu, con
     else
       F[row] = a - bg[row - nu];
   }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// diagnostics: what the reference script reports about an iterate (signorini_dolfinx.py:293-321,346-350).  Single passes over the
+// device state; they write their own buffers and the reduction scratch only.
+// ------------------------------------------------------------------------------------------------------------------
+// int_Gamma max(u.n_g - g, 0)^2 ds with the facet rule of the residual (:307-314): per-block partial sums over facets, no atomics
+template <int NPF>
+__global__ __launch_bounds__(256) void k_sg_penetration(int nf, int nv, const int32_t* __restrict__ facets, const double* __restrict__ coords,
+                                                        const double* __restrict__ x, double gap, SgQuad Q, const double* __restrict__ fgeo,
+                                                        double* __restrict__ partials) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (int f = blockIdx.x * 256 + threadIdx.x; f < nf; f += MX_RED * 256) {
+    const int32_t* fv = facets + NPF * (size_t)f;
+    double X[3][3];
+    for (int a = 0; a < 3; ++a)
+      for (int d = 0; d < 3; ++d) X[a][d] = coords[3 * (size_t)fv[Q.g[a]] + d];
+    const double e1[3] = {X[1][0] - X[0][0], X[1][1] - X[0][1], X[1][2] - X[0][2]};
+    const double e2[3] = {X[2][0] - X[0][0], X[2][1] - X[0][1], X[2][2] - X[0][2]};
+    const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+    const double area2 = sqrt(cx * cx + cy * cy + cz * cz);
+    double uz[NPF];
+#pragma unroll
+    for (int a = 0; a < NPF; ++a) uz[a] = x[2 * (size_t)nv + fv[a]];
+    for (int q = 0; q < Q.nq; ++q) {
+      const double wd = Q.w[q] * (fgeo ? fgeo[2 * ((size_t)f * Q.nq + q)] : area2);
+      const double zq = fgeo ? fgeo[2 * ((size_t)f * Q.nq + q) + 1] : Q.L[q][0] * X[0][2] + Q.L[q][1] * X[1][2] + Q.L[q][2] * X[2][2];
+      double uq = 0.0;
+#pragma unroll
+      for (int a = 0; a < NPF; ++a) uq += uz[a] * Q.N[q][a];
+      const double d = -uq - (zq - gap);  // u.n_g - g
+      const double pen = d > 0.0 ? d : 0.0;
+      s += wd * pen * pen;
+    }
+  }
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
+}
+
+// u.n_g - g at every node (:307-308, 349)
+__global__ __launch_bounds__(256) void k_sg_violation(int nv, const double* __restrict__ coords, const double* __restrict__ x, double gap,
+                                                      double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nv) return;
+  out[i] = -x[2 * (size_t)nv + i] - (coords[3 * (size_t)i + 2] - gap);
+}
+
+// sqrt(3/2 s:s), s = sigma(u) - tr(sigma(u))/3 I, at the cell's own nodes (:296-302).  One thread per affine cell; tab[n][a][3] = reference
+// gradient of basis function a at reference node n; the block's values go through LDS so that the [cell][node] array is written
+// in contiguous runs.
+template <int NPC>
+__global__ __launch_bounds__(64) void k_sg_von_mises(int nc, int nv, const int32_t* __restrict__ cells, const double* __restrict__ coords,
+                                                     const double* __restrict__ x, double mu, double lmbda, const double* __restrict__ tab,
+                                                     int g0, int g1, int g2, int g3, double* __restrict__ out) {
+  __shared__ double tile[64 * NPC];
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c < nc) {
+    const int32_t* cv = cells + NPC * (size_t)c;
+    const int gn[4] = {g0, g1, g2, g3};
+    double X[4][3];
+    for (int a = 0; a < 4; ++a)
+      for (int d = 0; d < 3; ++d) X[a][d] = coords[3 * (size_t)cv[gn[a]] + d];
+    double J[3][3];
+    for (int d = 0; d < 3; ++d)
+      for (int k = 0; k < 3; ++k) J[d][k] = X[k + 1][d] - X[0][d];
+    const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
+                       J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+    double inv[3][3];
+    inv[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) / det;
+    inv[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
+    inv[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) / det;
+    inv[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) / det;
+    inv[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) / det;
+    inv[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
+    inv[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) / det;
+    inv[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
+    inv[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) / det;
+    double u[NPC][3];  // indexed by unrolled loops only: registers
+#pragma unroll
+    for (int a = 0; a < NPC; ++a)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) u[a][i] = x[(size_t)i * nv + cv[a]];
+    for (int n = 0; n < NPC; ++n) {
+      const double* r = tab + (size_t)n * NPC * 3;
+      double H[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // d u_i / d xi_k
+#pragma unroll
+      for (int a = 0; a < NPC; ++a)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int k = 0; k < 3; ++k) H[i][k] += u[a][i] * r[3 * a + k];
+      double g[3][3];  // d u_i / d x_d
+      for (int i = 0; i < 3; ++i)
+        for (int d = 0; d < 3; ++d) g[i][d] = H[i][0] * inv[0][d] + H[i][1] * inv[1][d] + H[i][2] * inv[2][d];
+      const double tr = g[0][0] + g[1][1] + g[2][2];
+      double sg[3][3];
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) sg[i][j] = mu * (g[i][j] + g[j][i]) + (i == j ? lmbda * tr : 0.0);
+      const double m = (sg[0][0] + sg[1][1] + sg[2][2]) / 3.0;
+      double ss = 0.0;
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+          const double v = sg[i][j] - (i == j ? m : 0.0);
+          ss += v * v;
+        }
+      tile[threadIdx.x * NPC + n] = sqrt(1.5 * ss);
+    }
+  }
+  __syncthreads();
+  const size_t base = (size_t)blockIdx.x * 64 * NPC;
+  const int cnt = min(64, nc - (int)blockIdx.x * 64) * NPC;
+  for (int i = threadIdx.x; i < cnt; i += 64) out[base + i] = tile[i];
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -697,6 +823,49 @@ static int sg_create_impl(pgx_sg_handle* h, const pgx_sg_mesh* m, const pgx_sg_p
   MXALLOC(h->Jc, tot);
   MXALLOC(h->Jv, tot);
   if ((rc = mx_alloc_state(h))) return rc;
+  {  // diagnostics: every cell of the mesh (a distributed handle evaluates them on its replica of the iterate) and the reference
+     // gradients of the cell basis at the cell's own nodes
+    h->curved = g_sg_curved != nullptr;
+    MXALLOC(h->cells, NPC * (size_t)nc);
+    MXALLOC(h->vm_tab, (size_t)NPC * NPC * 3);
+    MXHIP(hipMemcpy(h->cells, m->cells, sizeof(int32_t) * NPC * (size_t)nc, hipMemcpyHostToDevice));
+    std::vector<double> tab((size_t)NPC * NPC * 3);
+    if (NPC == 4 || NPC == 10) {
+      static const double gref[4][3] = {{-1, -1, -1}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+      static const int ed[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
+      for (int n = 0; n < NPC; ++n) {
+        double L[4] = {0, 0, 0, 0};
+        if (n < 4)
+          L[n] = 1.0;
+        else
+          L[ed[n - 4][0]] = L[ed[n - 4][1]] = 0.5;
+        double* r = tab.data() + (size_t)n * NPC * 3;
+        for (int a = 0; a < 4; ++a)
+          for (int d = 0; d < 3; ++d) r[3 * a + d] = (NPC == 4 ? 1.0 : 4.0 * L[a] - 1.0) * gref[a][d];
+        for (int k = 0; k < (NPC == 10 ? 6 : 0); ++k)
+          for (int d = 0; d < 3; ++d) r[3 * (4 + k) + d] = 4.0 * (L[ed[k][0]] * gref[ed[k][1]][d] + L[ed[k][1]] * gref[ed[k][0]][d]);
+      }
+    } else {
+      const int d = NPC == 8 ? 1 : 2, n1 = d + 1;
+      h->vm_g[1] = d, h->vm_g[2] = d * n1, h->vm_g[3] = d * n1 * n1;
+      for (int nz = 0; nz < n1; ++nz)
+        for (int ny = 0; ny < n1; ++ny)
+          for (int nx = 0; nx < n1; ++nx) {
+            double lx[3], ly[3], lz[3], dx[3], dy[3], dz[3];
+            sg_lagrange1d(d, (double)nx / d, lx, dx);
+            sg_lagrange1d(d, (double)ny / d, ly, dy);
+            sg_lagrange1d(d, (double)nz / d, lz, dz);
+            double* r = tab.data() + (size_t)((nz * n1 + ny) * n1 + nx) * NPC * 3;
+            for (int iz = 0; iz < n1; ++iz)
+              for (int iy = 0; iy < n1; ++iy)
+                for (int ix = 0; ix < n1; ++ix) {
+                  double* ra = r + 3 * (size_t)((iz * n1 + iy) * n1 + ix);
+                  ra[0] = dx[ix] * ly[iy] * lz[iz], ra[1] = lx[ix] * dy[iy] * lz[iz], ra[2] = lx[ix] * ly[iy] * dz[iz];
+                }
+          }
+    }
+    MXHIP(hipMemcpy(h->vm_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+  }
   MXHIP(hipMemcpy(h->coords, m->coords, sizeof(double) * 3 * nv, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->facets, m->facets, sizeof(int32_t) * NPF * (size_t)nf, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->fpsi, fpsi.data(), sizeof(int32_t) * fpsi.size(), hipMemcpyHostToDevice));
@@ -906,5 +1075,64 @@ extern "C" int pgx_sg_u_increment(pgx_sg_handle* h, double* out) {
   mx_axpby(h, 1.0, h->x, 0.0, h->r);
   mx_axpby(h, -1.0, h->xk, 1.0, h->r);
   return mx_norm(h, h->r, out, 3 * (int64_t)h->nv);
+}
+
+// grows the diagnostics' output buffer (kept until the handle is destroyed)
+static int sg_diag_buffer(pgx_sg_handle* h, size_t len) {
+  if (len <= h->diag_len) return PGX_OK;
+  double* q = nullptr;
+  MXALLOC(q, len);
+  h->diag = q, h->diag_len = len;
+  return PGX_OK;
+}
+extern "C" int pgx_sg_penetration(pgx_sg_handle* h, double* l2) {
+  MXNEED(h);
+  if (!l2) return PGX_EINVAL;
+  const dim3 g(MX_RED), b(256);
+  if (h->npf == 6)
+    hipLaunchKernelGGL(k_sg_penetration<6>, g, b, 0, h->st, h->nf, h->nv, h->facets, h->coords, h->x, h->gap, h->Q, h->fgeo, h->partials);
+  else if (h->npf == 4)
+    hipLaunchKernelGGL(k_sg_penetration<4>, g, b, 0, h->st, h->nf, h->nv, h->facets, h->coords, h->x, h->gap, h->Q, h->fgeo, h->partials);
+  else if (h->npf == 9)
+    hipLaunchKernelGGL(k_sg_penetration<9>, g, b, 0, h->st, h->nf, h->nv, h->facets, h->coords, h->x, h->gap, h->Q, h->fgeo, h->partials);
+  else
+    hipLaunchKernelGGL(k_sg_penetration<3>, g, b, 0, h->st, h->nf, h->nv, h->facets, h->coords, h->x, h->gap, h->Q, h->fgeo, h->partials);
+  return mx_partials_sqrt(h, l2, false);  // local: the iterate is replicated
+}
+extern "C" int pgx_sg_violation(pgx_sg_handle* h, double* out) {
+  MXNEED(h);
+  if (!out) return PGX_EINVAL;
+  if (const int rc = sg_diag_buffer(h, (size_t)h->nv)) return rc;
+  hipLaunchKernelGGL(k_sg_violation, dim3((h->nv + 255) / 256), dim3(256), 0, h->st, h->nv, h->coords, h->x, h->gap, h->diag);
+  MXHIP(hipMemcpyAsync(out, h->diag, sizeof(double) * (size_t)h->nv, hipMemcpyDeviceToHost, h->st));
+  MXHIP(hipStreamSynchronize(h->st));
+  return PGX_OK;
+}
+extern "C" int pgx_sg_von_mises(pgx_sg_handle* h, double* out) {
+  MXNEED(h);
+  if (!out) return PGX_EINVAL;
+  if (h->curved) {
+    h->err = "pgx_sg_von_mises: a handle of pgx_sg_create_curved holds the cell geometry at the quadrature points only, not at the nodes";
+    return PGX_EINVAL;
+  }
+  const size_t len = (size_t)h->nc * h->npc;
+  if (const int rc = sg_diag_buffer(h, len)) return rc;
+  const dim3 g((h->nc + 63) / 64), b(64);
+  const int* vg = h->vm_g;
+  if (h->npc == 10)
+    hipLaunchKernelGGL(k_sg_von_mises<10>, g, b, 0, h->st, h->nc, h->nv, h->cells, h->coords, h->x, h->mu, h->lmbda, h->vm_tab, vg[0], vg[1],
+                       vg[2], vg[3], h->diag);
+  else if (h->npc == 8)
+    hipLaunchKernelGGL(k_sg_von_mises<8>, g, b, 0, h->st, h->nc, h->nv, h->cells, h->coords, h->x, h->mu, h->lmbda, h->vm_tab, vg[0], vg[1],
+                       vg[2], vg[3], h->diag);
+  else if (h->npc == 27)
+    hipLaunchKernelGGL(k_sg_von_mises<27>, g, b, 0, h->st, h->nc, h->nv, h->cells, h->coords, h->x, h->mu, h->lmbda, h->vm_tab, vg[0], vg[1],
+                       vg[2], vg[3], h->diag);
+  else
+    hipLaunchKernelGGL(k_sg_von_mises<4>, g, b, 0, h->st, h->nc, h->nv, h->cells, h->coords, h->x, h->mu, h->lmbda, h->vm_tab, vg[0], vg[1],
+                       vg[2], vg[3], h->diag);
+  MXHIP(hipMemcpyAsync(out, h->diag, sizeof(double) * len, hipMemcpyDeviceToHost, h->st));
+  MXHIP(hipStreamSynchronize(h->st));
+  return PGX_OK;
 }
 extern "C" int pgx_sg_profile(pgx_sg_handle* h, int enable, double ms[6]) { return mx_profile(h, enable, ms); }

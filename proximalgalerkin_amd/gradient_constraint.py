@@ -89,11 +89,17 @@ class GradientConstraintProblem(_MixedHandle):
             corners = mesh.cells
         self.dof_coords = xd
         self.ndofs = self.n2 + 2 * self.nv
+        self.general = bool(general or k != 2)
+        # the arrays the handle was built from: primal / latent cell dofs and the vertex triple spanning each affine cell
+        self.cell_dofs_u = cd
+        self.cell_dofs_p = cdp if self.general else np.ascontiguousarray(cd[:, :3])
+        self.corners = corners if self.general else mesh.cells
         # phi.interpolate(phi_func), f.interpolate(f_func) (:55-61); arrays of nodal values are taken as they are (forms front end)
         phi = np.ascontiguousarray(phi_func(xd.T.copy()) if callable(phi_func) else phi_func, dtype=np.float64)
         f = np.ascontiguousarray(f_func(xd.T.copy()) if callable(f_func) else f_func, dtype=np.float64)
         if phi.shape != (self.n2,) or f.shape != (self.n2,):
             raise ValueError("phi and f must be given in the collapsed primal space (one value per primal dof)")
+        self.phi_dofs = phi
         pp = _lib.pgx_gc_problem(len(wts), _lib.dptr(pts), _lib.dptr(wts), _lib.dptr(phi), _lib.dptr(f), len(bc),
                                  _lib.iptr(bc), None)
         if k == 2 and not general:
@@ -140,6 +146,54 @@ class GradientConstraintProblem(_MixedHandle):
     def l2_increment(self):
         """sqrt(assemble_scalar(dot(u - u0, u - u0) dx)) (:164-166,184-186)"""
         return self._scalar("l2_increment")
+
+    # -- the reference's output fields (gradient_constraint_dolfinx.py:134-165, 193-204), evaluated on the device state ---------------
+    def eval_cells(self, pts):
+        """At the reference points `pts` (npts, 2) of every cell: grad u (nc, npts, 2), the feasible gradient phi psi / sqrt(1 + |psi|^2)
+        (nc, npts, 2), phi (nc, npts) and the uint8 flags active = (|grad u| - phi >= 0), feasible_active = (|feasible gradient| - phi
+        > -1e-8), both (nc, npts) (include/pgx_gc.h: pgx_gc_eval_cells)."""
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
+        n, nc = len(pts), self.mesh.num_cells
+        keep = [pts]
+        if self.general:  # the library does not know the basis of a general handle: the tables at the points
+            from . import lagrange
+
+            quad = self.mesh.cell_name() == "quadrilateral"
+            tab = lagrange.tabulate_quad if quad else lagrange.tabulate
+            # (snap: at the latent element's own nodes the latent table is exactly the identity - the DG_(k-1) interpolant of psi copies
+            # its dofs, as the reference's interpolation does, instead of adding rounding noise times the LARGEST dof of the cell)
+            Nu, dNu = tab(self.degree, pts, snap=True)
+            Npl, _ = tab(self.degree - 1, pts, snap=True)
+            keep += [Nu, dNu, Npl]
+            p = _lib.pgx_gc_points(n, _lib.dptr(pts), _lib.dptr(Nu), _lib.dptr(dNu), _lib.dptr(Npl))
+        else:
+            p = _lib.pgx_gc_points(n, _lib.dptr(pts), None, None, None)
+        grad_u, feas, phi = np.empty((nc, n, 2)), np.empty((nc, n, 2)), np.empty((nc, n))
+        active, feasible_active = np.empty((nc, n), dtype=np.uint8), np.empty((nc, n), dtype=np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        self._call("eval_cells", C.byref(p), _lib.dptr(grad_u), _lib.dptr(feas), _lib.dptr(phi), active.ctypes.data_as(u8),
+                   feasible_active.ctypes.data_as(u8))
+        return grad_u, feas, phi, active, feasible_active
+
+    def latent_nodes(self):
+        """reference coordinates of the latent element's local nodes: the interpolation points of DG_(k-1) (:149-153)"""
+        from . import lagrange
+
+        k = self.degree - 1
+        if self.mesh.cell_name() == "quadrilateral":
+            t = np.arange(k + 1) / k
+            return np.ascontiguousarray([(x, y) for y in t for x in t])
+        return lagrange.lattice(k)
+
+    def active_sets(self):
+        """(active_set, global_feasible_active_set): the two DG0 indicators of :134-146, one uint8 per cell (cell midpoint)"""
+        mid = (0.5, 0.5) if self.mesh.cell_name() == "quadrilateral" else (1.0 / 3.0, 1.0 / 3.0)
+        _, _, _, a, fa = self.eval_cells([mid])
+        return a[:, 0].copy(), fa[:, 0].copy()
+
+    def dg_fields(self):
+        """(grad(u), Global feasible gradient, phi) in DG_(k-1): values at the latent nodes of every cell (:149-165)"""
+        return self.eval_cells(self.latent_nodes())[:3]
 
     def warm_start(self, device: int = 0):
         """The reference's --warm_start (:72-96): u <- solution of the Poisson problem (grad p, grad q) = (f, q), u = 0 on the
@@ -247,6 +301,24 @@ def solve_problem(N: int, M: int, primal_space: str = "Lagrange", primal_degree:
         if mesh.cell_name() != "quadrilateral":
             write_vtu(result_dir / "psi.vtu", mesh.geometry, mesh.cells,
                       {"psi": np.stack([xs[n2: n2 + nvert], xs[n2 + nv: n2 + nv + nvert]], axis=1)})
+        # active_set.xdmf and grad_u.bp of the reference (:134-165, 193-204): DG0 indicators as cell data; the DG_(k-1) fields on a
+        # discontinuous mesh - points duplicated per cell - at the cell corners
+        active, feasible_active = problem.active_sets()
+        quad = mesh.cell_name() == "quadrilateral"
+        ref = np.array([(0.0, 0.0), (1.0, 0.0), (1.0, 1.0), (0.0, 1.0)] if quad else [(0.0, 0.0), (1.0, 0.0), (0.0, 1.0)])
+        X = mesh.geometry[problem.corners]  # (nc, 3, 2): origin, +xi corner, +eta corner of the affine cell
+        pts = X[:, None, 0] + ref[None, :, :1] * (X[:, None, 1] - X[:, None, 0]) + ref[None, :, 1:] * (X[:, None, 2] - X[:, None, 0])
+        nc, k = pts.shape[:2]
+        conn = np.arange(nc * k, dtype=np.int32).reshape(nc, k)
+        gu, fe, ph = problem.eval_cells(ref)[:3]
+        if quad:  # two triangles per rectangle
+            conn, dup = np.concatenate([conn[:, [0, 1, 2]], conn[:, [0, 2, 3]]]), 2
+        else:
+            dup = 1
+        write_vtu(result_dir / "active_set.vtu", pts.reshape(-1, 2), conn,
+                  cell_data={"active_set": np.tile(active, dup), "global_feasible_active_set": np.tile(feasible_active, dup)})
+        write_vtu(result_dir / "grad_u.vtu", pts.reshape(-1, 2), conn,
+                  {"grad(u)": gu.reshape(-1, 2), "Global feasible gradient": fe.reshape(-1, 2), "phi": ph.ravel()})
     if return_solution:
         x = problem.get_state()
         problem.close()

@@ -42,21 +42,32 @@ def num_nodes(k: int) -> int:
     return (k + 1) * (k + 2) // 2
 
 
-def _factor(k, m, lam):
-    """P_m(lam) = prod_{a<m} (k lam - a) / (m - a) and its derivative with respect to lam; lam (npts,)"""
-    val = np.ones_like(lam)
-    der = np.zeros_like(lam)
+def _scaled(k, lam, snap):
+    """k lam; `snap`: a value within a few roundings of an integer IS that integer, so that a point given as the nearest doubles to a
+    lattice node sits on the node and the basis there is exactly the Kronecker delta (interpolation at the element's own nodes then
+    copies the dofs, as it does in exact arithmetic, whatever their size)"""
+    t = k * lam
+    if snap:
+        r = np.rint(t)
+        t = np.where(np.abs(t - r) <= 8 * np.finfo(float).eps * k, r, t)
+    return t
+
+
+def _factor(k, m, t):
+    """P_m(lam) = prod_{a<m} (k lam - a) / (m - a) and its derivative with respect to lam; t = k lam (npts,)"""
+    val = np.ones_like(t)
+    der = np.zeros_like(t)
     for a in range(m):
-        f = (k * lam - a) / (m - a)
+        f = (t - a) / (m - a)
         der = der * f + val * (k / (m - a))
         val = val * f
     return val, der
 
 
-def tabulate(k: int, pts) -> tuple[np.ndarray, np.ndarray]:
+def tabulate(k: int, pts, snap: bool = False) -> tuple[np.ndarray, np.ndarray]:
     """Values (npts, n) and reference gradients (npts, n, 2) of the Lagrange basis of degree k at reference points `pts`: the closed
     form on the equispaced lattice, N_(i,j,l) = P_i(l0) P_j(l1) P_l(l2) with barycentric coordinates l and P_m as in `_factor`
-    (nodal by construction, no Vandermonde inversion: accurate to rounding for every k)."""
+    (nodal by construction, no Vandermonde inversion: accurate to rounding for every k).  `snap`: see `_scaled`."""
     pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
     if k == 0:
         return np.ones((len(pts), 1)), np.zeros((len(pts), 1, 2))
@@ -64,7 +75,8 @@ def tabulate(k: int, pts) -> tuple[np.ndarray, np.ndarray]:
     dlam = np.array([[-1.0, -1.0], [1.0, 0.0], [0.0, 1.0]])
     nodes = lattice(k)
     idx = np.rint(np.stack([1.0 - nodes[:, 0] - nodes[:, 1], nodes[:, 0], nodes[:, 1]], axis=1) * k).astype(int)
-    P = {(c, m): _factor(k, m, lam[:, c]) for c in range(3) for m in range(k + 1)}
+    t = _scaled(k, lam, snap)
+    P = {(c, m): _factor(k, m, t[:, c]) for c in range(3) for m in range(k + 1)}
     V = np.empty((len(pts), len(nodes)))
     G = np.empty((len(pts), len(nodes), 2))
     for n, (i, j, l) in enumerate(idx):
@@ -127,11 +139,12 @@ def exterior_dofs(mesh, k: int, cell_dofs) -> np.ndarray:
 # vertex lattice, numbered row by row (x fastest); a cell's local nodes run over its (k+1) x (k+1) sub-lattice in the same order; the
 # basis is the product of the one-dimensional Lagrange bases on the equispaced nodes i/k.
 # ----------------------------------------------------------------------------------------------------------------------------------
-def _lagrange_1d(k: int, t):
+def _lagrange_1d(k: int, t, snap: bool = False):
     """values (npts, k+1) and derivatives of the 1-D Lagrange basis on the nodes i/k, from the linear factors (k t - a) / (i - a)"""
     t = np.ascontiguousarray(t, dtype=np.float64)
     if k == 0:
         return np.ones((len(t), 1)), np.zeros((len(t), 1))
+    kt = _scaled(k, t, snap)
     V = np.empty((len(t), k + 1))
     D = np.empty((len(t), k + 1))
     for i in range(k + 1):
@@ -140,7 +153,7 @@ def _lagrange_1d(k: int, t):
         for a in range(k + 1):
             if a == i:
                 continue
-            fac = (k * t - a) / (i - a)
+            fac = (kt - a) / (i - a)
             der = der * fac + val * (k / (i - a))
             val = val * fac
         V[:, i], D[:, i] = val, der
@@ -151,11 +164,11 @@ def num_nodes_quad(k: int) -> int:
     return (k + 1) * (k + 1)
 
 
-def tabulate_quad(k: int, pts) -> tuple[np.ndarray, np.ndarray]:
+def tabulate_quad(k: int, pts, snap: bool = False) -> tuple[np.ndarray, np.ndarray]:
     """Values (npts, (k+1)^2) and reference gradients (npts, (k+1)^2, 2) of the Q_k basis on the unit square at `pts`."""
     pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
-    Vx, Dx = _lagrange_1d(k, pts[:, 0])
-    Vy, Dy = _lagrange_1d(k, pts[:, 1])
+    Vx, Dx = _lagrange_1d(k, pts[:, 0], snap)
+    Vy, Dy = _lagrange_1d(k, pts[:, 1], snap)
     V = (Vy[:, :, None] * Vx[:, None, :]).reshape(len(pts), -1)  # node (iy, ix) -> iy (k+1) + ix
     G = np.stack([(Vy[:, :, None] * Dx[:, None, :]).reshape(len(pts), -1), (Dy[:, :, None] * Vx[:, None, :]).reshape(len(pts), -1)],
                  axis=2)

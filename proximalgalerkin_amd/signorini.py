@@ -282,6 +282,9 @@ class SignoriniProblem(_MixedHandle):
         else:
             raise NotImplementedError("HIP backend: degrees 1 and 2")
         self.node_coords = coords
+        self.cells, self.facets = cells, facets  # node ids, the orders of include/pgx_sg.h
+        self.E, self.nu, self.gap = float(E), float(nu), float(gap)
+        self.facet_quadrature = (pts, wts)
         nv = coords.shape[0]
         bc = np.ascontiguousarray(np.concatenate([bv, nv + bv, 2 * nv + bv]), dtype=np.int32)  # all components (:267)
         vals = np.ascontiguousarray(np.concatenate([np.zeros(len(bv)), np.zeros(len(bv)), np.full(len(bv), float(disp))]))
@@ -328,6 +331,24 @@ class SignoriniProblem(_MixedHandle):
     def u_increment(self):
         return self._scalar("u_increment")
 
+    # -- what the script reports about an iterate (signorini_dolfinx.py:293-321, 346-350), evaluated on the device state -------------
+    def penetration(self):
+        """|| max(u.n_g - g, 0) ||_L2(Gamma) with the facet rule of the residual (:307-314)"""
+        return self._scalar("penetration")
+
+    def violation(self):
+        """u.n_g - g at every node (:307-308, 349)"""
+        out = np.empty(self.nv)
+        self._call("violation", _lib.dptr(out))
+        return out
+
+    def von_mises(self):
+        """(n_cells, nodes per cell): the von-Mises stress at each cell's own nodes - its DG_degree interpolant (:296-302, 346).  Affine
+        cells only (include/pgx_sg.h)."""
+        out = np.empty(self.cells.shape)
+        self._call("von_mises", _lib.dptr(out))
+        return out
+
     def partition_info(self):
         """(cells whose element matrices this rank assembled, cells of the mesh): equal on a single handle; a distributed handle
         assembles its slab only (include/pgx_sg.h: pgx_sg_create_dist)."""
@@ -348,8 +369,10 @@ def solve_contact_problem(mesh: TetMesh, facet_tag: MeshTags, boundary_condition
                           newton_tol: float = 1e-6, max_iterations: int = 25, alpha_scheme: AlphaScheme = "doubling",
                           alpha_0: float = 1.0, alpha_c: float = 1.0, tol: float = 1e-6, output: Path | None = None,
                           quadrature_degree: int = 4, verbose: bool = True, return_solution: bool = False, device: int = 0,
-                          comm=None):
-    """signorini_dolfinx.solve_contact_problem (:156-360): returns (it, iterations) [, final state, problem data]."""
+                          comm=None, penetration_history: list | None = None):
+    """signorini_dolfinx.solve_contact_problem (:156-360): returns (it, iterations) [, final state, problem data].  A list given as
+    `penetration_history` receives the penetration norm the reference prints before every proximal step (:318-321); it is evaluated
+    only when printed (`verbose`) or collected."""
     if degree not in (1, 2):
         raise NotImplementedError("HIP backend: degrees 1 (BASELINE.json config 5) and 2 (the reference's default)")
     contact = np.concatenate([facet_tag.find(t) for t in boundary_conditions["contact"]])  # :186-189
@@ -361,8 +384,12 @@ def solve_contact_problem(mesh: TetMesh, facet_tag: MeshTags, boundary_condition
     normed_diff = -1.0
     it = 0
     for it in range(1, max_iterations + 1):
-        if verbose:
-            print(f"{it=}/{max_iterations} {normed_diff:.2e}")
+        if verbose or penetration_history is not None:
+            penetration = problem.penetration()  # :312-314
+            if penetration_history is not None:
+                penetration_history.append(penetration)
+            if verbose:
+                print(f"{it=}/{max_iterations} {normed_diff:.2e} Penetration L2(Gamma):", f" {penetration:.2e}")  # :318-321
         alpha = alpha_0
         if alpha_scheme == "linear":
             alpha = alpha_0 + alpha_c * it
@@ -391,15 +418,28 @@ def solve_contact_problem(mesh: TetMesh, facet_tag: MeshTags, boundary_condition
 
         xs = problem.get_state()
         nv = problem.nv
+        viol = problem.violation()  # the reference's `violation` Function next to u in uh.bp (:293-294, 349)
+        u3 = np.stack([xs[:nv], xs[nv:2 * nv], xs[2 * nv:3 * nv]], axis=1)
         if isinstance(mesh, HexMesh):  # all Q_d nodes as a point cloud of first-order cells on the refined lattice
             co, ce = mesh.lattice(degree)
             sub = HexMesh(degree * mesh.nx, degree * mesh.ny, degree * mesh.nz)
-            write_vtu(output / "uh.vtu", co, sub.cells[:, [0, 1, 3, 2, 4, 5, 7, 6]],
-                      {"displacement": np.stack([xs[:nv], xs[nv:2 * nv], xs[2 * nv:3 * nv]], axis=1)}, cell_type="hexahedron")
+            write_vtu(output / "uh.vtu", co, sub.cells[:, [0, 1, 3, 2, 4, 5, 7, 6]], {"displacement": u3, "violation": viol},
+                      cell_type="hexahedron")
+            n1 = degree + 1
+            corners = [0, degree, degree * n1 + degree, degree * n1]  # VTK corner order, bottom then top
+            corners += [c + degree * n1 * n1 for c in corners]
         else:
             nvert = mesh.geometry.shape[0]  # degree 2: the vertex values (the edge nodes follow them in every component)
-            write_vtu(output / "uh.vtu", mesh.geometry, mesh.cells,
-                      {"displacement": np.stack([xs[:nvert], xs[nv:nv + nvert], xs[2 * nv:2 * nv + nvert]], axis=1)})
+            write_vtu(output / "uh.vtu", mesh.geometry, mesh.cells, {"displacement": u3[:nvert], "violation": viol[:nvert]})
+            corners = [0, 1, 2, 3]
+        if not getattr(mesh, "curved", False):  # (von Mises needs affine cells: include/pgx_sg.h)
+            # von_mises.bp of the reference (:296-299, 346-348): DG fields on a discontinuous mesh - points duplicated per cell, the
+            # corner nodes of every cell as uh.vtu uses them
+            cn = problem.cells[:, corners]
+            nc, k = cn.shape
+            write_vtu(output / "von_mises.vtu", problem.node_coords[cn.ravel()], np.arange(nc * k, dtype=np.int32).reshape(nc, k),
+                      {"VonMises": problem.von_mises()[:, corners].ravel(), "u": u3[cn.ravel()]},
+                      cell_type="hexahedron" if isinstance(mesh, HexMesh) else None)
     if verbose:
         print(f"num_dofs_u={3 * problem.nv}, num_cells={mesh.cells.shape[0]}")
     if return_solution:
