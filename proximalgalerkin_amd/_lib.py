@@ -214,6 +214,23 @@ class pgx_mp_problem(C.Structure):  # include/pgx_mp.h
     ]
 
 
+class pgx_fr_problem(C.Structure):  # include/pgx_fr.h
+    _fields_ = [
+        ("nq", C.c_int32),
+        ("qpts", c_double_p),
+        ("qwts", c_double_p),
+        ("G", C.c_double),
+        ("Gc", C.c_double),
+        ("l", C.c_double),
+        ("eps", C.c_double),
+        ("reps", C.c_double),
+        ("n_minus", C.c_int32),
+        ("minus_dofs", c_int32_p),
+        ("n_plus", C.c_int32),
+        ("plus_dofs", c_int32_p),
+    ]
+
+
 class pgx_partition(C.Structure):
     _fields_ = [
         ("rank", C.c_int32),
@@ -340,8 +357,22 @@ SYMBOLS = [
     ("pgx_mp_l2_increment", C.c_int, [_H, c_double_p]),
     ("pgx_mp_species_mass", C.c_int, [_H, c_double_p]),
     ("pgx_mp_lu_stats", C.c_int, [_H, C.POINTER(pgx_nd_stats)]),
+    # example 03: phase-field fracture under load stepping (include/pgx_fr.h)
+    ("pgx_fr_create", C.c_int, [C.POINTER(pgx_mesh), C.POINTER(pgx_fr_problem), C.c_int, C.POINTER(_H)]),
+    ("pgx_fr_num_dofs", C.c_int, [_H, c_int64_p]),
+    ("pgx_fr_set_load", C.c_int, [_H, C.c_double]),
+    ("pgx_fr_set_zprev", C.c_int, [_H, c_double_p]),
+    ("pgx_fr_get_zprev", C.c_int, [_H, c_double_p]),
+    ("pgx_fr_zprev_from_state", C.c_int, [_H]),
+    ("pgx_fr_state_from_zprev", C.c_int, [_H]),
+    ("pgx_fr_state_from_prev", C.c_int, [_H]),
+    ("pgx_fr_l2_increment_c", C.c_int, [_H, c_double_p]),
+    ("pgx_fr_l2_distance_zprev", C.c_int, [_H, c_double_p]),
+    ("pgx_fr_conforming_damage", C.c_int, [_H, C.c_int32, c_double_p, c_double_p]),
+    ("pgx_fr_lu_stats", C.c_int, [_H, C.POINTER(pgx_nd_stats)]),
+    ("pgx_fr_lu_is_symmetric", C.c_int, [_H]),
 ]
-# the entry points the five mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
+# the entry points the six mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
 _MIXED_COMMON = [
     ("destroy", None, [_H]),
     ("last_error", C.c_char_p, [_H]),
@@ -358,7 +389,7 @@ _MIXED_COMMON = [
     ("newton_solve", C.c_int, [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("profile", C.c_int, [_H, C.c_int, c_double_p]),
 ]
-SYMBOLS += [(f"{prefix}_{suffix}", res, args) for prefix in ("pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic", "pgx_mp") for suffix, res, args in _MIXED_COMMON]
+SYMBOLS += [(f"{prefix}_{suffix}", res, args) for prefix in ("pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic", "pgx_mp", "pgx_fr") for suffix, res, args in _MIXED_COMMON]
 
 _lib = None
 _forwarded: dict = {}
