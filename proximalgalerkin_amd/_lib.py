@@ -231,6 +231,27 @@ class pgx_fr_problem(C.Structure):  # include/pgx_fr.h
     ]
 
 
+class pgx_ev_problem(C.Structure):  # include/pgx_ev.h
+    _fields_ = [
+        ("nx", C.c_int32),
+        ("ny", C.c_int32),
+        ("x0", C.c_double),
+        ("y0", C.c_double),
+        ("x1", C.c_double),
+        ("y1", C.c_double),
+        ("degree", C.c_int32),
+        ("nq", C.c_int32),
+        ("qpts", c_double_p),
+        ("qwts", c_double_p),
+        ("A", C.c_double),
+        ("C", C.c_double),
+        ("n_bc", C.c_int32),
+        ("bc_dofs", c_int32_p),
+        ("g1", c_double_p),
+        ("g2", c_double_p),
+    ]
+
+
 class pgx_partition(C.Structure):
     _fields_ = [
         ("rank", C.c_int32),
@@ -371,8 +392,16 @@ SYMBOLS = [
     ("pgx_fr_conforming_damage", C.c_int, [_H, C.c_int32, c_double_p, c_double_p]),
     ("pgx_fr_lu_stats", C.c_int, [_H, C.POINTER(pgx_nd_stats)]),
     ("pgx_fr_lu_is_symmetric", C.c_int, [_H]),
+    # example 07: eigenvalue-constrained Q-tensor (include/pgx_ev.h)
+    ("pgx_ev_create", C.c_int, [C.POINTER(pgx_ev_problem), C.c_int, C.POINTER(_H)]),
+    ("pgx_ev_num_dofs", C.c_int, [_H, c_int64_p]),
+    ("pgx_ev_state_from_prev", C.c_int, [_H]),
+    ("pgx_ev_l2_increment_q", C.c_int, [_H, c_double_p]),
+    ("pgx_ev_eval_nodes", C.c_int, [_H, c_double_p]),
+    ("pgx_ev_lu_stats", C.c_int, [_H, C.POINTER(pgx_nd_stats)]),
+    ("pgx_ev_lu_is_symmetric", C.c_int, [_H]),
 ]
-# the entry points the six mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
+# the entry points the seven mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
 _MIXED_COMMON = [
     ("destroy", None, [_H]),
     ("last_error", C.c_char_p, [_H]),
@@ -389,7 +418,7 @@ _MIXED_COMMON = [
     ("newton_solve", C.c_int, [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("profile", C.c_int, [_H, C.c_int, c_double_p]),
 ]
-SYMBOLS += [(f"{prefix}_{suffix}", res, args) for prefix in ("pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic", "pgx_mp", "pgx_fr") for suffix, res, args in _MIXED_COMMON]
+SYMBOLS += [(f"{prefix}_{suffix}", res, args) for prefix in ("pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic", "pgx_mp", "pgx_fr", "pgx_ev") for suffix, res, args in _MIXED_COMMON]
 
 _lib = None
 _forwarded: dict = {}
