@@ -131,6 +131,12 @@ struct pgx_handle {
   int lazy_norm = 1;        // PGX_LAZY_NORM=0: every new Krylov vector is normalised in place (one more pass over it per iteration)
   double rhs_scale = 1.0;   // factor the next level-0 V-cycle applies to its fp64 right-hand side as it reads it (lazy normalisation)
   int host_poll = 1;  // PGX_HOST_POLL=0: hipMemcpyAsync + hipStreamSynchronize for every small read-back (round 3)
+  // Krylov / Newton driver passes (single handles with host_poll; the last three only with the matrix-free P1 operator: krylov_lean())
+  int gs_wide = 16;       // PGX_GS_WIDE=8: Gram-Schmidt launches of at most 8 basis vectors (k_multidot / k_multiaxpy_norm; 16: one pass over w up to 16)
+  int fused_publish = 1;  // PGX_FUSED_PUBLISH=0: second reduction stage (k_reduce_rows / k_reduce_partials) and k_publish as two launches
+  int fused_resid = 1;    // PGX_FUSED_RESID=0: true residual of a restart cycle as operator apply + k_scale_copy(-1) + k_axpy(+b)
+  int lean_rhs = 1;       // PGX_LEAN_RHS=0: the Newton loop forms rhs = -F as a vector, fgmres zero-fills x and accumulates into it
+  int fused_step = 1;     // PGX_FUSED_STEP=0: xw += dx as k_axpy, |dx| and |xw| as two dev_norm calls with a read-back each
   // multigrid
   std::vector<GridLevel> lev;
   double *tmp_u = nullptr, *tmp_p = nullptr, *res_u = nullptr, *res_p = nullptr;  // level-0 scratch (each n)
@@ -1235,6 +1241,11 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_K6_MAX")) h->k6_max = atoi(e);
   if (const char* e = pgx_tune("PGX_SMOOTH_D32")) h->smooth_d32 = atoi(e);
   if (const char* e = pgx_tune("PGX_HOST_POLL")) h->host_poll = atoi(e);
+  if (const char* e = pgx_tune("PGX_GS_WIDE")) h->gs_wide = atoi(e) >= 16 ? 16 : 8;
+  if (const char* e = pgx_tune("PGX_FUSED_PUBLISH")) h->fused_publish = atoi(e);
+  if (const char* e = pgx_tune("PGX_FUSED_RESID")) h->fused_resid = atoi(e);
+  if (const char* e = pgx_tune("PGX_LEAN_RHS")) h->lean_rhs = atoi(e);
+  if (const char* e = pgx_tune("PGX_FUSED_STEP")) h->fused_step = atoi(e);
   if (const char* e = pgx_tune("PGX_LAZY_NORM")) h->lazy_norm = atoi(e);
   if (const char* e = pgx_tune("PGX_Z_F32")) h->z_f32 = atoi(e);
   if (const char* e = pgx_tune("PGX_F32_DBF16")) h->f32_dbf16 = atoi(e);
@@ -1700,6 +1711,7 @@ __global__ void __launch_bounds__(64) k_publish(int n, const double* __restrict_
   __threadfence_system();  // one wave: every lane's stores are ordered before lane 0's flag store below
   if (threadIdx.x == 0) __hip_atomic_store(seqp, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+static int wait_published(pgx_handle* h, unsigned long long seq);  // the bounded host poll on the sequence word
 // h_small[hoff .. hoff + n) <- dsrc[0 .. n) (and optionally a second range), blocking until the values have arrived
 static int fetch_small(pgx_handle* h, const double* dsrc, size_t n, size_t hoff = 0, const double* dsrc2 = nullptr, size_t n2 = 0,
                        size_t hoff2 = 0) {
@@ -1712,6 +1724,18 @@ static int fetch_small(pgx_handle* h, const double* dsrc, size_t n, size_t hoff 
   const unsigned long long seq = ++h->seq;
   hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->st, (int)n, dsrc, h->h_small_dev + hoff, (int)n2, dsrc2, h->h_small_dev + hoff2,
                      seq, h->h_seq_dev);
+  return wait_published(h, seq);
+}
+// the second stage of a reduction and its read-back in one launch (pgxk_reduce_publish): rows of nb partials -> dout[0 .. nrows) on
+// the device and h_small[hoff_r ..), and dsrc1[0 .. n1) -> h_small[hoff1 ..); blocks like fetch_small.  Callers: fused_readback(h)
+static bool fused_readback(const pgx_handle* h) { return h->fused_publish && h->host_poll && !h->dist.on && !h->lu_comm; }
+static int reduce_fetch(pgx_handle* h, int nb, const double* partials, int nrows, double* dout, size_t hoff_r, const double* dsrc1 = nullptr,
+                        size_t n1 = 0, size_t hoff1 = 0) {
+  const unsigned long long seq = ++h->seq;
+  pgxk_reduce_publish(h->st, nb, partials, nrows, dout, h->h_small_dev + hoff_r, (int)n1, dsrc1, h->h_small_dev + hoff1, seq, h->h_seq_dev);
+  return wait_published(h, seq);
+}
+static int wait_published(pgx_handle* h, unsigned long long seq) {
   // Bounded wait: a collective or a kernel ahead of k_publish that never completes leaves hipStreamQuery at NotReady
   // for ever - after PGX_COMM_TIMEOUT seconds (default 120; the transports' own limit) the call fails with PGX_ECOMM / PGX_EHIP and
   // a message instead of spinning.  The poll backs off: a pause per probe, and after ~50 us without an answer a yield per batch of
@@ -1750,6 +1774,14 @@ static int fetch_small(pgx_handle* h, const double* dsrc, size_t n, size_t hoff 
 }
 
 static int dev_norm(pgx_handle* h, const double* v, double* out, size_t len = 0) {
+  if (fused_readback(h)) {  // k_reduce_partials (nv = 1) + k_publish as one launch
+    const size_t l = len ? len : 2 * (size_t)h->nd;
+    pgxk_multidot(h->st, l, 1, v, 0, v, h->partials, nullptr);
+    const int rc = reduce_fetch(h, pgxk_multidot_blocks(l), h->partials, 1, h->d_small, 0);
+    if (rc) return rc;
+    *out = std::sqrt(h->h_small[0]);
+    return PGX_OK;
+  }
   pgxk_multidot(h->st, len ? len : 2 * (size_t)h->nd, 1, v, 0, v, h->partials, h->d_small);
   if (h->dist.on) {
     const int rc = allreduce_dev(h, h->d_small, 1);
@@ -2608,11 +2640,20 @@ static int precond(pgx_handle* h, const double* b, double* z, int nu, double ome
   return PGX_OK;
 }
 
+// Single handle on the matrix-free structured P1 operator (uniform level 0): where the lean driver passes apply - the operator kernel's
+// residual mode (PGX_FUSED_RESID), the signed right-hand side without a -F copy or a zero fill (PGX_LEAN_RHS), the fused Newton update
+// (PGX_FUSED_STEP).  Sharded, replicated-LU, P2 and general-mesh handles keep the plain sequence.
+static inline bool krylov_lean(const pgx_handle* h) {
+  return !h->dist.on && !h->lu_comm && !h->lu_active && h->degree == 1 && h->structured && h->spmv_stencil == 1 && !h->lev.empty() &&
+         h->lev[0].uniform;
+}
+
 // FGMRES(restart) on J dx = b, right-preconditioned by one V-cycle; CGS2 orthogonalisation with
 // batched device dot products; Givens rotations on the host (one small D2H copy + sync per iteration).
 // bnorm_known >= 0: the 2-norm of b, already on the host (the Newton driver's |F|: b = -F) - saves a reduction and its read-back
+// bsign = +-1: the system solved is J dx = bsign * b (the Newton driver hands in F itself with bsign = -1 instead of a copy -F)
 static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts* o, int* its_out, double* relres,
-                  double bnorm_known = -1.0) {
+                  double bnorm_known = -1.0, double bsign = 1.0) {
   const size_t n2 = 2 * (size_t)h->nd;
   // Sharded: the Krylov space lives on OWNED dofs (basis vectors V_j, b, residuals are owned-compact, length nk, so the
   // tuned vector kernels run unchanged and every dot product is "local partial + one all-reduce"); the operators work
@@ -2626,12 +2667,16 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
   double bnorm = bnorm_known;
   int rc = PGX_OK;
   if (!(bnorm_known >= 0.0) && (rc = dev_norm(h, b, &bnorm, nk))) return rc;
-  pgxk_set(h->st, n2, 0.0, x);
+  // lean: no zero fill - the first solution update starts its sums from 0.0 instead of reading zeros back (x_unset), and x = 0 is
+  // written only on the ways out that leave no update behind
+  const bool lean = krylov_lean(h);
+  bool x_unset = lean && h->lean_rhs;
+  if (!x_unset) pgxk_set(h->st, n2, 0.0, x);
   *its_out = 0;
   *relres = 0.0;
-  if (bnorm == 0.0) return PGX_OK;
-  if (!std::isfinite(bnorm)) {
-    *relres = bnorm;
+  if (bnorm == 0.0 || !std::isfinite(bnorm)) {
+    if (x_unset) pgxk_set(h->st, n2, 0.0, x);
+    if (bnorm != 0.0) *relres = bnorm;
     return PGX_OK;
   }
   const double target = o->ksp_rtol * bnorm;
@@ -2651,14 +2696,18 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
     if (first_cycle && its >= o->ksp_max_it) break;
     if (first_cycle) {
       beta = bnorm;
-      pgxk_scale_copy(h->st, nk, 1.0 / beta, b, h->V);
+      pgxk_scale_copy(h->st, nk, bsign * (1.0 / beta), b, h->V);  // (bsign = -1: bitwise (-b) / beta)
     } else {
-      // r = b - J x
+      // r = bsign b - J x
       PhaseTimer t(h, 3);
-      spmv_dev(h, x, h->w);
-      if (dist) gather_owned(h, h->w, wk);
-      pgxk_scale_copy(h->st, nk, -1.0, wk, wk);
-      pgxk_axpy(h->st, nk, 1.0, b, wk);
+      if (lean && h->fused_resid) {  // one pass: the operator kernel stores bsign b - J x
+        pgxk_st_spmv(h->st, h->lev[0], h->alpha, x, x + h->nd, h->xcd_remap ? 1 : 0, h->w, h->w + h->nd, nullptr, b, b + h->nd, bsign);
+      } else {
+        spmv_dev(h, x, h->w);
+        if (dist) gather_owned(h, h->w, wk);
+        pgxk_scale_copy(h->st, nk, -1.0, wk, wk);
+        pgxk_axpy(h->st, nk, bsign, b, wk);
+      }
       rc = dev_norm(h, wk, &beta, nk);
       if (rc) return rc;
       res = beta;
@@ -2727,16 +2776,22 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
         const PgxDotScale* const dsc = lazy ? &sc2 : nullptr;
         // pass 1: h1 = V^T w.  passes 2+3 fused: w' = w - V h1 and [h2; |w'|^2] in one sweep over the basis.
         // Sharded: each batch of partial dot products is completed by ONE packed all-reduce, enqueued on the stream.
-        pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h1, dsc);
+        pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h1, dsc, h->gs_wide);
         if (dist && (rc = allreduce_dev(h, d_h1, j + 1))) return rc;
         double wp2, h1h1 = 0.0, hh = 0.0;
         bool second;
         if (h->cgs_selective) {
           // lean second pass: w' = w - V h1 and |w'|^2; V^T w' (for the second projection) only if the test below asks for it
-          pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, d_h2 + j + 1);
-          if (dist && (rc = allreduce_dev(h, d_h2 + j + 1, 1))) return rc;
-          if ((rc = replica_agree(h, h->d_small, 2 * (size_t)(m + 2)))) return rc;
-          if ((rc = fetch_small(h, d_h1, (size_t)(j + 1), 0, d_h2 + j + 1, 1, (size_t)(m + 2) + j + 1))) return rc;
+          if (fused_readback(h)) {  // the norm's second stage and the read-back of [h1; |w'|^2] in one launch
+            pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, nullptr, h->gs_wide);
+            if ((rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_h2 + j + 1, (size_t)(m + 2) + j + 1, d_h1, (size_t)(j + 1), 0)))
+              return rc;
+          } else {
+            pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, d_h2 + j + 1, h->gs_wide);
+            if (dist && (rc = allreduce_dev(h, d_h2 + j + 1, 1))) return rc;
+            if ((rc = replica_agree(h, h->d_small, 2 * (size_t)(m + 2)))) return rc;
+            if ((rc = fetch_small(h, d_h1, (size_t)(j + 1), 0, d_h2 + j + 1, 1, (size_t)(m + 2) + j + 1))) return rc;
+          }
           for (int i = 0; i <= j; ++i) {
             h->h_small[i] /= sv[i];  // lazy: the device holds s_i^2 (W_i . w); the Hessenberg entry is s_i (W_i . w)
             h1h1 += h->h_small[i] * h->h_small[i];
@@ -2746,7 +2801,7 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
           // first one cancelled most of w, |w'| < eta |w| with |w|^2 = |w'|^2 + |h1|^2
           second = wp2 < h->cgs_eta2 * (wp2 + h1h1);
           if (second) {
-            pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h2, dsc);
+            pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h2, dsc, h->gs_wide);
             if (dist && (rc = allreduce_dev(h, d_h2, j + 1))) return rc;
             if ((rc = replica_agree(h, d_h2, (size_t)(j + 1)))) return rc;
             if ((rc = fetch_small(h, d_h2, (size_t)(j + 1), (size_t)(m + 2)))) return rc;
@@ -2809,6 +2864,7 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
       if (dist) ++h->dist.n_krylov;
       if (o->monitor > 1) printf("      ksp %3d  rnorm %.6e  rel %.3e\n", its, res, res / bnorm);
       if (!std::isfinite(res)) {
+        if (x_unset) pgxk_set(h->st, n2, 0.0, x);
         *its_out = its;
         *relres = res / bnorm;
         return PGX_OK;
@@ -2835,12 +2891,14 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
     for (int i = 0; i < j; ++i) h->h_small[i] = y[i];
     HIPCHK(hipMemcpyAsync(h->d_small, h->h_small, sizeof(double) * j, hipMemcpyHostToDevice, h->st));
     if (zf32)
-      pgxk_lincomb_f2(h->st, (size_t)h->nd, j, Zf, (size_t)h->nd, h->d_small, x, x + h->nd);
+      pgxk_lincomb_f2(h->st, (size_t)h->nd, j, Zf, (size_t)h->nd, h->d_small, x, x + h->nd, x_unset ? 0 : 1);
     else
-      pgxk_lincomb(h->st, n2, j, h->Z, n2, h->d_small, x, 1);
+      pgxk_lincomb(h->st, n2, j, h->Z, n2, h->d_small, x, x_unset ? 0 : 1);
+    x_unset = false;
     // (no synchronisation: the loop head recomputes the TRUE residual b - Jx - it decides convergence, not the Arnoldi estimate - and
     // its read-back is ordered behind the upload of y on the stream, so h_small is not touched again before that copy is done)
   }
+  if (x_unset) pgxk_set(h->st, n2, 0.0, x);  // ksp_max_it == 0: no cycle ran
   *its_out = its;
   *relres = res / bnorm;
   return PGX_OK;
@@ -3301,7 +3359,9 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
       if ((rc = lu_factor(h))) return rc;
       h->lu_active = true;
     }
-    pgxk_scale_copy(h->st, nk, -1.0, dist ? h->rhs : h->F, h->rhs);
+    // lean: fgmres takes F itself and the sign (V_0 = (-1 / beta) F, residuals -F - J x): no pass that forms rhs = -F
+    const bool lean_rhs = h->lean_rhs && !use_lu && !mg_first && krylov_lean(h);
+    if (!lean_rhs) pgxk_scale_copy(h->st, nk, -1.0, dist ? h->rhs : h->F, h->rhs);
     int kits = 0;
     double relres = 0;
     if (mg_first && !use_lu) {
@@ -3323,7 +3383,7 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
         if (rc) return rc;
       }
     } else {
-      rc = fgmres(h, h->rhs, h->dx, opts, &kits, &relres, fnorm);
+      rc = lean_rhs ? fgmres(h, h->F, h->dx, opts, &kits, &relres, fnorm, -1.0) : fgmres(h, h->rhs, h->dx, opts, &kits, &relres, fnorm);
       if (rc) return rc;
     }
     lin += kits;
@@ -3333,7 +3393,14 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
       rsn = PGX_SNES_DIVERGED_LINEAR_SOLVE;
       break;
     }
-    pgxk_axpy(h->st, n2, 1.0, h->dx, h->xw);
+    // xw += dx; fused: the same pass leaves the block sums of |dx|^2 and |xw|^2 (partials2: nothing else in the Newton loop uses
+    // it) for the step test below, which then needs one read-back and no further pass
+    const bool fstep = h->fused_step && fused_readback(h) && !use_lu && !mg_first && krylov_lean(h);
+    int step_nb = 0;
+    if (fstep)
+      step_nb = pgxk_axpy_norms(h->st, n2, h->dx, h->xw, h->partials2);
+    else
+      pgxk_axpy(h->st, n2, 1.0, h->dx, h->xw);
     if (dist && (rc = halo_solution(h, h->xw, h->xw + h->nd))) return rc;
     residual_dev(h, h->xw, h->F, with_d);
     if ((rc = replica_check(h, h->F, n2, "the residual"))) return rc;
@@ -3353,10 +3420,16 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
       rsn = PGX_SNES_CONVERGED_FNORM_RELATIVE;
     } else {
       double snorm, xnorm;
-      rc = owned_norm(h->dx, &snorm);
-      if (rc) return rc;
-      rc = owned_norm(h->xw, &xnorm);
-      if (rc) return rc;
+      if (fstep) {
+        if ((rc = reduce_fetch(h, step_nb, h->partials2, 2, h->d_small, 0))) return rc;
+        snorm = std::sqrt(h->h_small[0]);
+        xnorm = std::sqrt(h->h_small[1]);
+      } else {
+        rc = owned_norm(h->dx, &snorm);
+        if (rc) return rc;
+        rc = owned_norm(h->xw, &xnorm);
+        if (rc) return rc;
+      }
       if (snorm < opts->snes_stol * xnorm)
         rsn = PGX_SNES_CONVERGED_SNORM_RELATIVE;
       else if (fnorm > opts->snes_divtol * fnorm0)

@@ -134,8 +134,17 @@ void pgxk_to_float(hipStream_t st, size_t len, const double* x, float* y);
 struct PgxDotScale {
   double s[PGX_DOT_SCALE_MAX];
 };
+// wide: vectors per launch (8 or 16); out == nullptr: no second stage, partials[0 .. pgxk_multidot_blocks(len) * nv) stay for the caller
 void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
-                   double* out, const PgxDotScale* scale = nullptr);
+                   double* out, const PgxDotScale* scale = nullptr, int wide = 8);
+int pgxk_multidot_blocks(size_t len);
+int pgxk_stream_blocks(size_t len);  // grid of the streaming vector kernels (pgxk_multiaxpy_norm's partials)
+// out[r] = sum of row r of partials ([nrows][nb]) in the shape of k_reduce_rows, then out[0 .. nrows) -> hout and src1[0 .. n1) -> dst1
+// (mapped host memory) and the sequence word seq -> *seqp: second stage + read-back in one one-block launch
+void pgxk_reduce_publish(hipStream_t st, int nb, const double* partials, int nrows, double* out, double* hout, int n1, const double* src1,
+                         double* dst1, unsigned long long seq, unsigned long long* seqp);
+// y += x; partials <- the block sums of |x|^2 (row 0) and |y + x|^2 (row 1), rows of the returned length
+int pgxk_axpy_norms(hipStream_t st, size_t len, const double* x, double* y, double* partials);
 // w -= sum_i h[i] V_i   (h is a DEVICE pointer to nv doubles)
 void pgxk_multiaxpy(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w);
 // x = sum_i y[i] Z_i  (y device pointer); accumulate!=0 -> x += ...
@@ -163,8 +172,10 @@ void pgxk_st_smooth2(hipStream_t st, int post, const GridLevel& L, double alpha,
                      const GridLevel* C, const double* cu, const double* cp, const double* bu, const double* bp,
                      double omega, int remap, double* yu, double* yp);
 void pgxk_st_spmv(hipStream_t st, const GridLevel& L, double alpha, const double* xu, const double* xp, int remap, double* yu,
-                  double* yp, const float2* xf = nullptr /* the iterate as ONE interleaved (u, psi) float2 field instead of (xu, xp); uniform levels only */);
-void pgxk_lincomb_f2(hipStream_t st, size_t n, int nv, const float2* Zf, size_t ldz, const double* y, double* xu, double* xp);
+                  double* yp, const float2* xf = nullptr /* the iterate as ONE interleaved (u, psi) float2 field instead of (xu, xp); uniform levels only */,
+                  const double* bu = nullptr, const double* bp = nullptr, double s = 1.0 /* bu: y = s (bu, bp) - J x (uniform levels, xf == nullptr) */);
+void pgxk_lincomb_f2(hipStream_t st, size_t n, int nv, const float2* Zf, size_t ldz, const double* y, double* xu, double* xp,
+                     int accumulate = 1);
 void pgxk_pack_d4(hipStream_t st, const GridLevel& L);  // Dd4 <- Dh
 void pgxk_st_resid_restrict(hipStream_t st, const GridLevel& L, double alpha, const double* xu, const double* xp,
                             const double* bu, const double* bp, const GridLevel& C, int remap, double* cbu,
@@ -264,7 +275,7 @@ void pgxk_multiaxpy_scale(hipStream_t st, size_t len, int nv, const double* V, s
                           double scale, double* w);
 // w -= V h and out[0] = |w'|^2 in one pass over the basis (selective CGS2: the lean second pass)
 void pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w,
-                         double* partials, double* out);
+                         double* partials, double* out, int wide = 8);
 // ---- single-precision V-cycle legs (pgx_mg32.hip) ----
 // Dq <- Dh (values above 1e30 are clamped: an overshot Newton iterate must not put infinities into the preconditioner)
 void pgxk_f_pack_d(hipStream_t st, const GridLevel& L);

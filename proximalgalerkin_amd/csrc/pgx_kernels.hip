@@ -1228,24 +1228,29 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_reduce_partials_scaled(int nblock
   if (threadIdx.x == 0) out[v] = r * sc.s[v];
 }
 
-void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
-                   double* out, const PgxDotScale* scale) {
-  const size_t len2 = len / 2, ldv2 = ldv / 2;
-  size_t nb = (len2 + PGX_BLOCK - 1) / PGX_BLOCK;
+int pgxk_multidot_blocks(size_t len) {
+  size_t nb = (len / 2 + PGX_BLOCK - 1) / PGX_BLOCK;
   if (nb > PGX_RED_BLOCKS) nb = PGX_RED_BLOCKS;
-  if (nb == 0) nb = 1;
+  return nb == 0 ? 1 : (int)nb;
+}
+
+void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
+                   double* out, const PgxDotScale* scale, int wide) {
+  const size_t len2 = len / 2, ldv2 = ldv / 2;
+  const size_t nb = (size_t)pgxk_multidot_blocks(len);
   dim3 grid((unsigned)nb), block(PGX_BLOCK);
+  const int cap = wide > 16 ? 16 : wide < 1 ? 1 : wide;
   int done = 0;
   while (done < nv) {
     const int rem = nv - done;
     const double2* Vp = (const double2*)(V + (size_t)done * ldv);
-    // one launch per chunk of at most 8 vectors, the last chunk of EXACTLY the remaining size: w is read once per chunk (the
-    // 8/4/2/1 split of rounds 1-3 read it up to three times); the per-vector partials do not depend on the grouping
+    // one launch per chunk of at most `wide` (8 or 16) vectors, the last chunk of EXACTLY the remaining size: w is read once per
+    // chunk (the 8/4/2/1 split of rounds 1-3 read it up to three times); the per-vector partials do not depend on the grouping
 #define PGX_MD(N)                                                                                                          \
   case N:                                                                                                                  \
     hipLaunchKernelGGL(k_multidot<N>, grid, block, 0, st, len2, Vp, ldv2, (const double2*)w, partials, nv, done);          \
     break
-    const int take = rem >= 8 ? 8 : rem;
+    const int take = rem >= cap ? cap : rem;
     switch (take) {
       PGX_MD(1);
       PGX_MD(2);
@@ -1255,14 +1260,80 @@ void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t l
       PGX_MD(6);
       PGX_MD(7);
       PGX_MD(8);
+      PGX_MD(9);
+      PGX_MD(10);
+      PGX_MD(11);
+      PGX_MD(12);
+      PGX_MD(13);
+      PGX_MD(14);
+      PGX_MD(15);
+      PGX_MD(16);
     }
 #undef PGX_MD
     done += take;
   }
+  if (!out) return;  // the caller runs the second stage itself (pgxk_reduce_publish)
   if (scale)
     hipLaunchKernelGGL(k_reduce_partials_scaled, dim3(nv), block, 0, st, (int)nb, nv, partials, *scale, out);
   else
     hipLaunchKernelGGL(k_reduce_partials, dim3(nv), block, 0, st, (int)nb, nv, partials, out);
+}
+
+// The second stage of a two-stage reduction and the read-back of its result in ONE one-block launch: rows of nb partials are
+// summed in the fixed shape of k_reduce_rows / k_reduce_partials (nv = 1) - thread t adds p[t], p[t + 256], ..., then block_sum -
+// so out[r] is bitwise what those kernels leave; then wave 0 does what k_publish (pgx_api.hip) does: the sums and up to n1 more
+// device doubles go to mapped host memory with system-scope stores, a fence, and the sequence word the host polls.  Ordered
+// behind its producers by the stream; nothing waits on the device.
+__global__ void __launch_bounds__(PGX_BLOCK) k_reduce_publish(int nb, const double* __restrict__ p, int nrows, double* out, double* hout,
+                                                              int n1, const double* src1, double* dst1, unsigned long long seq,
+                                                              unsigned long long* seqp) {
+  __shared__ double sm[PGX_BLOCK / WAVE];
+  for (int r = 0; r < nrows; ++r) {
+    const double* row = p + (size_t)r * nb;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) s += row[b];
+    const double t = block_sum(s, sm);
+    if (threadIdx.x == 0) {
+      out[r] = t;
+      __hip_atomic_store(hout + r, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+  if (threadIdx.x >= WAVE) return;
+  for (int i = threadIdx.x; i < n1; i += WAVE) __hip_atomic_store(dst1 + i, src1[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __threadfence_system();  // one wave: every lane's stores are ordered before lane 0's flag store below
+  if (threadIdx.x == 0) __hip_atomic_store(seqp, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+void pgxk_reduce_publish(hipStream_t st, int nb, const double* partials, int nrows, double* out, double* hout, int n1, const double* src1,
+                         double* dst1, unsigned long long seq, unsigned long long* seqp) {
+  hipLaunchKernelGGL(k_reduce_publish, dim3(1), dim3(PGX_BLOCK), 0, st, nb, partials, nrows, out, hout, n1, src1, dst1, seq, seqp);
+}
+
+// y += x and the block's shares of |x|^2 and |y'|^2 in one pass (the Newton update and the two norms of its step test).  Grid,
+// per-thread order and block_sum are those of k_multidot<1>, the element update is k_axpy's with a = 1: both sums and y are
+// bitwise what k_axpy followed by two k_multidot<1> give.  partials: [2][gridDim.x], rows for pgxk_reduce_publish.
+__global__ void __launch_bounds__(PGX_BLOCK) k_axpy_norms(size_t len2, double a, const double2* __restrict__ x, double2* __restrict__ y,
+                                                          double* __restrict__ partials) {
+  __shared__ double sm[PGX_BLOCK / WAVE];
+  double accx = 0.0, accy = 0.0;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < len2; i += (size_t)gridDim.x * blockDim.x) {
+    double2 xv = x[i], yv = y[i];
+    yv.x += a * xv.x;
+    yv.y += a * xv.y;
+    y[i] = yv;
+    accx += xv.x * xv.x + xv.y * xv.y;
+    accy += yv.x * yv.x + yv.y * yv.y;
+  }
+  const double rx = block_sum(accx, sm);
+  const double ry = block_sum(accy, sm);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = rx;
+    partials[gridDim.x + blockIdx.x] = ry;
+  }
+}
+int pgxk_axpy_norms(hipStream_t st, size_t len, const double* x, double* y, double* partials) {
+  const int nb = pgxk_multidot_blocks(len);
+  hipLaunchKernelGGL(k_axpy_norms, dim3(nb), dim3(PGX_BLOCK), 0, st, len / 2, 1.0, (const double2*)x, (double2*)y, partials);
+  return nb;
 }
 
 template <int NV>
@@ -1408,7 +1479,7 @@ void pgxk_multiaxpy_scale(hipStream_t st, size_t len, int nv, const double* V, s
   }
 }
 
-// w -= sum_v h[v] V_v in chunks of <= 8 vectors; the LAST chunk also leaves the block's share of |w'|^2 in partials[block]
+// w -= sum_v h[v] V_v in chunks of <= 8 (16: `wide`) vectors; the LAST chunk also leaves the block's share of |w'|^2 in partials[block]
 // (fixed-shape two-stage reduction: reproducible).  The lean second pass of selective CGS2: one read of the basis, one
 // read-modify-write of w, no LDS parking of basis slices (k_axpy_dot does that to get V^T w' in the same pass, which is only
 // needed when the second projection is - 11 of 266 iterations at 2048^2).
@@ -1445,29 +1516,45 @@ static void launch_multiaxpy_norm(hipStream_t st, dim3 grid, size_t len2, const 
   else
     hipLaunchKernelGGL((k_multiaxpy_norm<NV, false>), grid, dim3(PGX_BLOCK), 0, st, len2, Vp, ldv2, h, w, partials);
 }
-// out[0] = |w - V h|^2, w updated in place.  partials: >= PGX_RED_BLOCKS doubles.
+int pgxk_stream_blocks(size_t len) { return (int)stream_grid(len / 2).x; }
+// out[0] = |w - V h|^2, w updated in place.  partials: >= pgxk_stream_blocks(len) doubles.  out == nullptr: the block partials
+// stay in partials[0 .. pgxk_stream_blocks(len)) for the caller's own second stage (pgxk_reduce_publish)
 void pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w,
-                         double* partials, double* out) {
+                         double* partials, double* out, int wide) {
   const size_t len2 = len / 2, ldv2 = ldv / 2;
   dim3 grid = stream_grid(len2);
+  const int cap = wide > 16 ? 16 : wide < 1 ? 1 : wide;
   int done = 0;
   while (done < nv) {
-    const int step = std::min(8, nv - done);
+    const int step = std::min(cap, nv - done);
     const bool last = done + step == nv;
     const double2* Vp = (const double2*)(V + (size_t)done * ldv);
+#define PGX_MAN(N)                                                                                         \
+  case N:                                                                                                  \
+    launch_multiaxpy_norm<N>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials);            \
+    break
     switch (step) {
-      case 8: launch_multiaxpy_norm<8>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials); break;
-      case 7: launch_multiaxpy_norm<7>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials); break;
-      case 6: launch_multiaxpy_norm<6>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials); break;
-      case 5: launch_multiaxpy_norm<5>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials); break;
-      case 4: launch_multiaxpy_norm<4>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials); break;
-      case 3: launch_multiaxpy_norm<3>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials); break;
-      case 2: launch_multiaxpy_norm<2>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials); break;
+      PGX_MAN(16);
+      PGX_MAN(15);
+      PGX_MAN(14);
+      PGX_MAN(13);
+      PGX_MAN(12);
+      PGX_MAN(11);
+      PGX_MAN(10);
+      PGX_MAN(9);
+      PGX_MAN(8);
+      PGX_MAN(7);
+      PGX_MAN(6);
+      PGX_MAN(5);
+      PGX_MAN(4);
+      PGX_MAN(3);
+      PGX_MAN(2);
       default: launch_multiaxpy_norm<1>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials); break;
     }
+#undef PGX_MAN
     done += step;
   }
-  hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(PGX_BLOCK), 0, st, (int)grid.x, partials, out);
+  if (out) hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(PGX_BLOCK), 0, st, (int)grid.x, partials, out);
 }
 
 void pgxk_multiaxpy(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w) {
@@ -1508,11 +1595,12 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_lincomb(size_t len2, int nv, cons
     x[i] = s;
   }
 }
-// (xu, xp)[v] += sum_i y[i] Zf_i[v] for float2-interleaved Z_i (see st_load_x): the solution update of a cycle whose Z_j are float
+// (xu, xp)[v] (+)= sum_i y[i] Zf_i[v] for float2-interleaved Z_i (see st_load_x): the solution update of a cycle whose Z_j are float
 __global__ void __launch_bounds__(PGX_BLOCK) k_lincomb_f2(size_t n, int nv, const float2* __restrict__ Zf, size_t ldz,
-                                                          const double* __restrict__ y, double* __restrict__ xu, double* __restrict__ xp) {
+                                                          const double* __restrict__ y, double* __restrict__ xu, double* __restrict__ xp,
+                                                          int accumulate) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    double su = xu[i], sp = xp[i];
+    double su = accumulate ? xu[i] : 0.0, sp = accumulate ? xp[i] : 0.0;
     for (int v = 0; v < nv; ++v) {
       const float2 a = Zf[v * ldz + i];
       const double yv = y[v];
@@ -1523,9 +1611,10 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_lincomb_f2(size_t n, int nv, cons
     xp[i] = sp;
   }
 }
-void pgxk_lincomb_f2(hipStream_t st, size_t n, int nv, const float2* Zf, size_t ldz, const double* y, double* xu, double* xp) {
+void pgxk_lincomb_f2(hipStream_t st, size_t n, int nv, const float2* Zf, size_t ldz, const double* y, double* xu, double* xp,
+                     int accumulate) {
   const unsigned grid = (unsigned)std::min<size_t>((n + PGX_BLOCK - 1) / PGX_BLOCK, 256 * 32);
-  hipLaunchKernelGGL(k_lincomb_f2, dim3(grid), dim3(PGX_BLOCK), 0, st, n, nv, Zf, ldz, y, xu, xp);
+  hipLaunchKernelGGL(k_lincomb_f2, dim3(grid), dim3(PGX_BLOCK), 0, st, n, nv, Zf, ldz, y, xu, xp, accumulate);
 }
 
 void pgxk_lincomb(hipStream_t st, size_t len, int nv, const double* Z, size_t ldz, const double* y, double* x,
@@ -2718,12 +2807,21 @@ __device__ __forceinline__ double2 st_load_x(const double* __restrict__ xu, cons
   }
   return make_double2(xu[v], xp[v]);
 }
-template <bool FAST, bool XF = false>
+// s b - jx with jx taken as the ROUNDED double the plain mode stores: the empty asm keeps the compiler from contracting the last
+// multiply-add of jx into this subtraction (one rounding less than the stored-and-reloaded sequence it replaces)
+__device__ __forceinline__ double st_resid(double s, double b, double jx) {
+  asm volatile("" : "+v"(jx));
+  return s * b - jx;
+}
+// RES (residual mode): the tile stores s b - J x instead of J x, b = (bu, bp) read at the vertex being stored, s = +-1 - element
+// for element what k_scale_copy(-1) and k_axpy(+ s b) make of the stored J x (s b is exact, the one rounding is that of the sum)
+template <bool FAST, bool XF = false, bool RES = false>
 __device__ __forceinline__ void st_spmv_tile(int tx, int ty, int nx, int ny, int n, const double* __restrict__ K,
                                              const double* __restrict__ M, const dsten_t* __restrict__ Dh, const StConst& sc,
                                              const uint8_t* __restrict__ mask, double alpha, const double* __restrict__ xu,
                                              const double* __restrict__ xp, double* __restrict__ yu, double* __restrict__ yp,
-                                             double2* ximg) {
+                                             double2* ximg, const double* __restrict__ bu = nullptr,
+                                             const double* __restrict__ bp = nullptr, double s = 1.0) {
   constexpr int W = 64, CXS = 62, RY = PGX_SPMV_RY, HX = RY + 2, NW = PGX_ROWMAP_BLOCK / 64;
   const int sx = nx + 1;
   const int i0 = tx * CXS - 1, j0 = ty * RY - 1;  // image origin: one halo column / row before the tile
@@ -2770,8 +2868,8 @@ __device__ __forceinline__ void st_spmv_tile(int tx, int ty, int nx, int ny, int
       const double ap = m0 * x0.x + m1 * u12 + m3 * u34 + m5 * u56 -
                         (d0 * x0.y + d1 * x1.y + d2 * x2.y + d3 * x3.y + d4 * x4.y + d5 * x5.y + d6 * x6.y);
       if (act) {
-        __builtin_nontemporal_store(au, yu + v);
-        __builtin_nontemporal_store(ap, yp + v);
+        __builtin_nontemporal_store(RES ? st_resid(s, bu[v], au) : au, yu + v);
+        __builtin_nontemporal_store(RES ? st_resid(s, bp[v], ap) : ap, yp + v);
       }
     }
   } else {
@@ -2790,8 +2888,9 @@ __device__ __forceinline__ void st_spmv_tile(int tx, int ty, int nx, int ny, int
           au += alpha * c.kv[t] * xn.x + c.mv[t] * xn.y;
           ap += c.mv[t] * xn.x - c.dv[t] * xn.y;
         }
-        yu[v] = c.rowbc ? st_load_x<XF>(xu, xp, (unsigned)v).x : au;
-        yp[v] = ap;
+        const double ju = c.rowbc ? st_load_x<XF>(xu, xp, (unsigned)v).x : au;  // Dirichlet rows: identity
+        yu[v] = RES ? st_resid(s, bu[v], ju) : ju;
+        yp[v] = RES ? st_resid(s, bp[v], ap) : ap;
       }
     }
   }
@@ -2801,11 +2900,12 @@ __device__ __forceinline__ void st_spmv_tile(int tx, int ty, int nx, int ny, int
 // same rows, all in flight before the first LDS store - instead of the iterate first and, behind the barrier, seven D loads per
 // vertex (three of them re-reads of the neighbours' links).  The mirrored links come from the neighbours as in the smoother: the
 // left lane's register (DPP) and the (D2, D3) pair every row hands to the row above it through LDS.
-template <bool D4, bool XF = false>
+template <bool D4, bool XF = false, bool RES = false>
 __device__ __forceinline__ void st_spmv_fast(int tx, int ty, int nx, int n, const dsten_t* __restrict__ Dh, const double4* __restrict__ Dd4,
                                              const StConst& sc, double alpha, const double* __restrict__ xu,
                                              const double* __restrict__ xp, double* __restrict__ yu, double* __restrict__ yp,
-                                             double2* ximg, double2* exch) {
+                                             double2* ximg, double2* exch, const double* __restrict__ bu = nullptr,
+                                             const double* __restrict__ bp = nullptr, double s = 1.0) {
   constexpr int W = 64, CXS = 62, RY = PGX_SPMV_RY, HX = RY + 2, NW = PGX_ROWMAP_BLOCK / 64, R = (HX + NW - 1) / NW;
   const int sx = nx + 1;
   const int i0 = tx * CXS - 1, j0 = ty * RY - 1;
@@ -2867,19 +2967,21 @@ __device__ __forceinline__ void st_spmv_fast(int tx, int ty, int nx, int n, cons
                       (d0[k] * x0.y + d1[k] * x1.y + d2 * x2.y + d3[k] * x3.y + d4 * x4.y + d5[k] * x5.y + d6 * x6.y);
     if (act) {
       const unsigned v = (unsigned)((j0 + lj) * sx + gi);
-      __builtin_nontemporal_store(au, yu + v);
-      __builtin_nontemporal_store(ap, yp + v);
+      __builtin_nontemporal_store(RES ? st_resid(s, bu[v], au) : au, yu + v);
+      __builtin_nontemporal_store(RES ? st_resid(s, bp[v], ap) : ap, yp + v);
     }
   }
 }
 
-template <bool XF>
+template <bool XF, bool RES = false>
 __global__ void __launch_bounds__(PGX_ROWMAP_BLOCK) k_st_spmv_r(int nx, int ny, int n, RrGrid g, int nbnd,
                                                                 const double* __restrict__ K, const double* __restrict__ M,
                                                                 const dsten_t* __restrict__ Dh, const double4* __restrict__ Dd4,
                                                                 StConst sc, const uint8_t* __restrict__ mask, double alpha,
                                                                 const double* __restrict__ xu, const double* __restrict__ xp,
-                                                                int remap, double* __restrict__ yu, double* __restrict__ yp) {
+                                                                int remap, double* __restrict__ yu, double* __restrict__ yp,
+                                                                const double* __restrict__ bu = nullptr,
+                                                                const double* __restrict__ bp = nullptr, double s = 1.0) {
   constexpr int W = 64, HX = PGX_SPMV_RY + 2, PAD = W + 1;
   __shared__ double2 ximg_[HX * W + 2 * PAD], exch_[HX * W + 2 * PAD];
   int b = blockIdx.x;
@@ -2898,19 +3000,20 @@ __global__ void __launch_bounds__(PGX_ROWMAP_BLOCK) k_st_spmv_r(int nx, int ny, 
       ty = g.nfy + 1 + b / g.ntx;
       tx = b % g.ntx;
     }
-    st_spmv_tile<false, XF>(tx, ty, nx, ny, n, K, M, Dh, sc, mask, alpha, xu, xp, yu, yp, ximg_ + PAD);
+    st_spmv_tile<false, XF, RES>(tx, ty, nx, ny, n, K, M, Dh, sc, mask, alpha, xu, xp, yu, yp, ximg_ + PAD, bu, bp, s);
   } else {
     b = xcd_block(b - nbnd, gridDim.x - nbnd, remap);
     if (Dd4)
-      st_spmv_fast<true, XF>(1 + b % g.nfx, 1 + b / g.nfx, nx, n, Dh, Dd4, sc, alpha, xu, xp, yu, yp, ximg_ + PAD, exch_ + PAD);
+      st_spmv_fast<true, XF, RES>(1 + b % g.nfx, 1 + b / g.nfx, nx, n, Dh, Dd4, sc, alpha, xu, xp, yu, yp, ximg_ + PAD, exch_ + PAD, bu, bp, s);
     else
-      st_spmv_fast<false, XF>(1 + b % g.nfx, 1 + b / g.nfx, nx, n, Dh, Dd4, sc, alpha, xu, xp, yu, yp, ximg_ + PAD, exch_ + PAD);
+      st_spmv_fast<false, XF, RES>(1 + b % g.nfx, 1 + b / g.nfx, nx, n, Dh, Dd4, sc, alpha, xu, xp, yu, yp, ximg_ + PAD, exch_ + PAD, bu, bp, s);
   }
 }
 
-// y = J x on a structured level, matrix-free (see above); levels without uniform interior stencils take k_st_apply<0>
+// y = J x on a structured level, matrix-free (see above); levels without uniform interior stencils take k_st_apply<0>.
+// bu != nullptr (uniform levels, fp64 iterate only): y = s (bu, bp) - J x, the residual mode of the tiles
 void pgxk_st_spmv(hipStream_t st, const GridLevel& L, double alpha, const double* xu, const double* xp, int remap, double* yu,
-                  double* yp, const float2* xf) {
+                  double* yp, const float2* xf, const double* bu, const double* bp, double s) {
   if (!L.uniform) {
     pgxk_st_apply(st, 0, L, alpha, xu, xp, nullptr, nullptr, 0.0, remap ? 2 : 0, yu, yp);
     return;
@@ -2927,12 +3030,15 @@ void pgxk_st_spmv(hipStream_t st, const GridLevel& L, double alpha, const double
   g.nfy = std::min(g.nfy, g.nty - 1);
   if (!L.interior_free || g.nfx <= 0 || g.nfy <= 0) g.nfx = g.nfy = 0;
   const int nfast = g.nfx * g.nfy, nbnd = g.ntx * g.nty - nfast;
-  if (xf)  // the iterate as one float2 field (pgxk_st_spmv_f2_ok levels only)
-    hipLaunchKernelGGL(k_st_spmv_r<true>, dim3(nbnd + nfast), dim3(PGX_ROWMAP_BLOCK), 0, st, L.nx, L.ny, L.n, g, nbnd, L.K, L.M, L.Dh, L.Dd4,
-                       make_stconst(L), L.mask, alpha, reinterpret_cast<const double*>(xf), nullptr, remap, yu, yp);
+  if (bu)
+    hipLaunchKernelGGL((k_st_spmv_r<false, true>), dim3(nbnd + nfast), dim3(PGX_ROWMAP_BLOCK), 0, st, L.nx, L.ny, L.n, g, nbnd, L.K, L.M, L.Dh,
+                       L.Dd4, make_stconst(L), L.mask, alpha, xu, xp, remap, yu, yp, bu, bp, s);
+  else if (xf)  // the iterate as one float2 field (pgxk_st_spmv_f2_ok levels only)
+    hipLaunchKernelGGL((k_st_spmv_r<true, false>), dim3(nbnd + nfast), dim3(PGX_ROWMAP_BLOCK), 0, st, L.nx, L.ny, L.n, g, nbnd, L.K, L.M, L.Dh, L.Dd4,
+                       make_stconst(L), L.mask, alpha, reinterpret_cast<const double*>(xf), nullptr, remap, yu, yp, nullptr, nullptr, 1.0);
   else
-    hipLaunchKernelGGL(k_st_spmv_r<false>, dim3(nbnd + nfast), dim3(PGX_ROWMAP_BLOCK), 0, st, L.nx, L.ny, L.n, g, nbnd, L.K, L.M, L.Dh, L.Dd4,
-                       make_stconst(L), L.mask, alpha, xu, xp, remap, yu, yp);
+    hipLaunchKernelGGL((k_st_spmv_r<false, false>), dim3(nbnd + nfast), dim3(PGX_ROWMAP_BLOCK), 0, st, L.nx, L.ny, L.n, g, nbnd, L.K, L.M, L.Dh, L.Dd4,
+                       make_stconst(L), L.mask, alpha, xu, xp, remap, yu, yp, nullptr, nullptr, 1.0);
 }
 
 __global__ void __launch_bounds__(256) k_pack_d4(int n, const dsten_t* __restrict__ Dh, double4* __restrict__ Dd4) {

@@ -1,0 +1,100 @@
+"""The lean passes of the Krylov / Newton driver (csrc/pgx_api.hip: fgmres, pgx_newton_solve): Gram-Schmidt launches of up to 16 basis
+vectors (PGX_GS_WIDE), the second reduction stage and the read-back in one launch (PGX_FUSED_PUBLISH), the true residual of a restart
+cycle out of the operator kernel (PGX_FUSED_RESID), the signed right-hand side without a -F copy or a zero fill (PGX_LEAN_RHS), the
+Newton update with its two norms (PGX_FUSED_STEP).  Every one of them is an exact transformation: with a key off and on the Newton
+counts per proximal step, the linear iterations and the final iterate (BITWISE) must agree."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+DOMAIN = ((-1.0, -1.0), (1.0, 1.0))
+BASE = {"snes_linesearch_type": "none", "snes_rtol": 1e-6, "snes_max_it": 100, "snes_error_if_not_converged": True}
+OFF = {"PGX_GS_WIDE": 8, "PGX_FUSED_PUBLISH": 0, "PGX_FUSED_RESID": 0, "PGX_LEAN_RHS": 0, "PGX_FUSED_STEP": 0}
+_RUNS = {}
+
+
+def _solve(cells, tuning, opts):
+    """One settings-B LVPP run (as tests/test_gpu_mg32.py: _solve_rect) -> final iterate, Newton counts and linear iterations per
+    proximal step.  Runs are kept: a configuration that several tests compare against is solved once and never modified."""
+    key = (tuple(cells), tuple(sorted(tuning.items())), tuple(sorted(opts.items())))
+    if key in _RUNS:
+        return _RUNS[key]
+    from proximalgalerkin_amd import _lib, fem
+    from proximalgalerkin_amd.obstacle import run_outer_loop, setup_problem
+
+    for k, v in tuning.items():
+        _lib.tuning_set(k, v)
+    try:
+        msh = fem.create_rectangle(DOMAIN, cells)
+        problem, sol, sol_k, alpha = setup_problem(msh, 1, petsc_options=dict(BASE, **opts))
+        lin, inner = [], problem.solve
+
+        def solve():
+            inner()
+            lin.append(int(problem.solver.getLinearSolveIterations()))
+
+        problem.solve = solve
+        hist = run_outer_loop(problem, sol, sol_k, alpha, 100, "double_exponential", 1e2, 1e-4, verbose=False)
+        x = sol.x.array.copy()
+        x.setflags(write=False)
+        problem.close()
+    finally:
+        for k in tuning:
+            _lib.tuning_set(k, None)
+    _RUNS[key] = (x, [int(n) for n in hist["Newton steps"]], lin)
+    return _RUNS[key]
+
+
+def _assert_same(a, b, what):
+    (xa, na, la), (xb, nb, lb) = a, b
+    print(f"{what}: Newton {na} / {nb}, linear iterations {sum(la)} / {sum(lb)}, "
+          f"max |difference| of the iterates {np.max(np.abs(xa - xb)):.3e}")
+    assert na == nb, what
+    assert sum(la) == sum(lb), (what, la, lb)
+    assert np.array_equal(xa, xb), what
+
+
+@pytest.mark.parametrize("key", list(OFF) + ["all"])
+def test_each_switch_is_exact(require_gpu, key):
+    off = OFF if key == "all" else {key: OFF[key]}
+    _assert_same(_solve((128, 128), off, {}), _solve((128, 128), {}, {}), f"{key} off / on")
+
+
+def test_wide_chunks_run_with_nine_to_sixteen_vectors_and_with_a_remainder(require_gpu):
+    """mg_nu = 2: the weaker cycle takes the solves past 8 and past 16 basis vectors, so k_multidot / k_multiaxpy_norm run at every
+    NV = 9 ... 16 and the 16 + remainder chunking runs too.  A proximal step with `lin` linear iterations over `n` Newton steps has
+    a solve of at least lin / n iterations, and iteration number i projects against i basis vectors.  (With the default ksp_rtol of
+    1e-10 the proximal steps average 11 ... 15 iterations per solve at 128^2 - none provably beyond 16 - hence the tighter one.)"""
+    opts = {"mg_nu": 2, "ksp_rtol": 1e-13}
+    a = _solve((128, 128), {"PGX_GS_WIDE": 8}, opts)
+    b = _solve((128, 128), {}, opts)
+    longest = max(-(-lin // n) for lin, n in zip(b[2], b[1]) if n)
+    print(f"mg_nu = 2: Newton {b[1]}, linear iterations {b[2]}: some solve took at least {longest} iterations")
+    _assert_same(a, b, "PGX_GS_WIDE 8 / 16, mg_nu = 2")
+    assert longest > 8
+    assert longest > 16
+
+
+@pytest.mark.parametrize("key", ["PGX_FUSED_RESID", "PGX_LEAN_RHS"])
+def test_restarted_solves_are_exact(require_gpu, key):
+    """Restart length 4: every solve restarts from the residual the operator kernel wrote and accumulates into x across cycles."""
+    opts = {"ksp_gmres_restart": 4}
+    b = _solve((128, 128), {}, opts)
+    print(f"restart 4: Newton {b[1]}, linear iterations per proximal step {b[2]}")
+    assert max(-(-lin // n) for lin, n in zip(b[2], b[1]) if n) > 4  # some solve did restart
+    _assert_same(_solve((128, 128), {key: 0}, opts), b, f"{key} off / on, restart 4")
+
+
+@pytest.mark.parametrize("restart", [None, 6])
+@pytest.mark.parametrize("cells", [(32, 32), (200, 72), (128, 128)])
+def test_fused_residual_on_grids_that_cut_the_operator_tiles(require_gpu, cells, restart):
+    """32^2: boundary tiles only (interior tiles need nx >= 125); 200 x 72: interior and boundary tiles, nx + 1 no multiple of 62 and
+    ny + 1 none of 14 or 27; 128^2.  With the default restart length the kernel's residual decides when each solve ends; with
+    restart length 6 it is also the first basis vector of every further cycle (FGMRES(4) does not converge on the 200 x 72 grid, with
+    or without the fused residual: 212 iterations into the second Newton step of proximal step 4)."""
+    opts = {"ksp_gmres_restart": restart} if restart else {}
+    _assert_same(_solve(cells, {"PGX_FUSED_RESID": 0}, opts), _solve(cells, {}, opts), f"PGX_FUSED_RESID off / on, {cells}")
+
+
+def test_stream_synchronising_read_backs_take_the_unfused_launches(require_gpu):
+    _assert_same(_solve((128, 128), {"PGX_HOST_POLL": 0}, {}), _solve((128, 128), {}, {}), "PGX_HOST_POLL 0 / default")
