@@ -130,6 +130,14 @@ struct pgx_handle {
   int spmv_d4 = 1;          // PGX_SPMV_D4=0: the matrix-free operator apply reads the four D arrays instead of its double4 copy
   int lazy_norm = 1;        // PGX_LAZY_NORM=0: every new Krylov vector is normalised in place (one more pass over it per iteration)
   double rhs_scale = 1.0;   // factor the next level-0 V-cycle applies to its fp64 right-hand side as it reads it (lazy normalisation)
+  const float* rhs_f32 = nullptr;  // != nullptr: the next level-0 single-precision cycle reads its right-hand side HERE, as the float pair
+                                   // (rhs_f32, rhs_f32 + n) - a vector of FGMRES's float basis - instead of the fp64 pair it is called with
+  int v_f32 = 1;            // PGX_V_F32=0: the Krylov basis of the lean P1 path in fp64 (see fgmres)
+  double v_f32_gain = 1e-4; // PGX_V_F32_GAIN: a cycle on the float basis ends once its estimate is below this factor times its starting residual
+  double v_f32_max = 1e30;  // PGX_V_F32_MAX: a new basis vector with a norm above this (or not finite) does not fit a float: guard in fgmres
+  int v_f32_min = 1000000;  // PGX_V_F32_MIN: the float basis from this many vertices up, where the Gram-Schmidt passes are bound by HBM
+                            // bandwidth; below, its few extra iterations and cycles are not paid back by the halved streams
+  bool v_f32_off = false;   // the guard fired: fp64 basis for the rest of this Newton solve (reset by pgx_newton_solve, like omega_now)
   int host_poll = 1;  // PGX_HOST_POLL=0: hipMemcpyAsync + hipStreamSynchronize for every small read-back (round 3)
   // Krylov / Newton driver passes (single handles with host_poll; the last three only with the matrix-free P1 operator: krylov_lean())
   int gs_wide = 16;       // PGX_GS_WIDE=8: Gram-Schmidt launches of at most 8 basis vectors (k_multidot / k_multiaxpy_norm; 16: one pass over w up to 16)
@@ -1247,6 +1255,10 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_LEAN_RHS")) h->lean_rhs = atoi(e);
   if (const char* e = pgx_tune("PGX_FUSED_STEP")) h->fused_step = atoi(e);
   if (const char* e = pgx_tune("PGX_LAZY_NORM")) h->lazy_norm = atoi(e);
+  if (const char* e = pgx_tune("PGX_V_F32")) h->v_f32 = atoi(e);
+  if (const char* e = pgx_tune("PGX_V_F32_GAIN")) h->v_f32_gain = atof(e);
+  if (const char* e = pgx_tune("PGX_V_F32_MAX")) h->v_f32_max = atof(e);
+  if (const char* e = pgx_tune("PGX_V_F32_MIN")) h->v_f32_min = atoi(e);
   if (const char* e = pgx_tune("PGX_Z_F32")) h->z_f32 = atoi(e);
   if (const char* e = pgx_tune("PGX_F32_DBF16")) h->f32_dbf16 = atoi(e);
   if (const char* e = pgx_tune("PGX_SPMV_D4")) h->spmv_d4 = atoi(e);
@@ -2006,8 +2018,9 @@ static const float2* vcycle_f(pgx_handle* h, int l, const double* bu, const doub
   {
     const bool rr = fuse && nl == 1;
     const double bscale = (l == 0 && bu) ? h->rhs_scale : 1.0;
+    const float* const b32 = (l == 0 && bu) ? h->rhs_f32 : nullptr;  // the Krylov vector as two float fields (fgmres: float basis)
     pgxk_f_smooth(h->st, K, 1, L, h->alpha, nullptr, bu, bp, rr ? &C : nullptr, nullptr, nullptr, nullptr, omega, remap, cu, nullptr,
-                  nullptr, rr ? cbf : nullptr, rr ? cb64u : nullptr, rr ? cb64p : nullptr, bscale);
+                  nullptr, rr ? cbf : nullptr, rr ? cb64u : nullptr, rr ? cb64p : nullptr, bscale, b32, b32 ? b32 + L.n : nullptr);
   }
   for (int s = 1; s < nl; ++s) {
     const bool rr = fuse && s + 1 == nl;
@@ -2684,6 +2697,7 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
   double res = bnorm;
   double prev_cycle_res = bnorm;
   bool first_cycle = true;
+  bool redo = false;  // the cycle about to start repeats one that the float-basis guard abandoned (below)
   // Smoother damping.  The default 0.8 is the fast choice while psi is smooth on the mesh scale (lambda_max of the
   // Jacobi-scaled element matrices is 2); an overshot Newton iterate makes exp(psi) jump by orders of magnitude
   // inside single elements, lambda_max approaches its bound 3 (dofs per triangle) and only omega < 2/3 is a
@@ -2691,12 +2705,36 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
   // < 10x) the rest of this Newton solve runs at the unconditionally stable value.
   const double omega_safe = 0.6;
   double omega = (h->omega_now > 0.0) ? std::min(h->omega_now, o->mg_omega) : o->mg_omega;
+  // Lazy normalisation (round 4): a new basis vector stays as the Gram-Schmidt pass left it, W_{j+1} = w', and only its scale
+  // s_{j+1} = 1 / |w'| is kept (v_i = s_i W_i): the V-cycle multiplies its right-hand side by s_j as its first launch reads it, the
+  // batched dot products come back as s_i^2 (W_i . w) - the coefficients the projection w' = w - sum_i (v_i . w) v_i applies to the
+  // stored W_i - and the pass over w that only divided it by its norm (67 MB read + written per iteration) is gone.  Only where
+  // the preconditioner is the single-precision cycle entered on level 0 (it is the one that takes the factor).
+  const bool lazy = h->lazy_norm && h->cgs_selective && !h->lu_active && h->degree == 1 && m + 2 <= PGX_DOT_SCALE_MAX && !h->lev.empty() &&
+                    f32_cycle_ok(h, 0, o->mg_nu);  // (the non-selective CGS2 kernels carry no scale factors: that mode runs un-lazy)
+  // Z_j in single precision (round 5): on this path z_j leaves a float cycle, so storing it as one float2 field loses nothing - the
+  // cycle's last launch writes it in place, the operator apply reads it (k_st_spmv_r<true>), the solution update sums it
+  // (k_lincomb_f2): 100 MB less per Krylov iteration at 2048^2 than the fp64 pair.  w = J z_j and H stay fp64.
+  const bool zf32 = z_f32_active(h, o->mg_nu);
+  // The basis V in single precision (PGX_V_F32, the lean P1 path only, from PGX_V_F32_MIN vertices up): the vectors are stored as float in the same [u | psi] layout, at
+  // a stride padded to 16 bytes, inside the storage of the fp64 basis; w = J z_j is fp64 in h->w, dot products and projections are
+  // fp64 on the widened basis, and the last chunk of the second pass stores (float) w' as V_{j+1} and returns the norm of the ROUNDED
+  // vector.  The Gram-Schmidt passes move j + 3.5 instead of 2 j + 5 fp64 vectors.  The Arnoldi estimate of such a cycle stalls near
+  // 1e-7 of the residual the cycle started from (the basis spans r / beta to float accuracy only), so a cycle ends once the estimate has
+  // gained v_f32_gain; the loop head then takes the TRUE residual in fp64 and the next cycle starts from it.
+  const bool vf32_ok = h->v_f32 && lean && lazy && zf32 && h->nd >= h->v_f32_min;
+  float* const Vf = reinterpret_cast<float*>(h->V);
+  const size_t ldvf = (nk + 3) & ~(size_t)3;  // (m + 1) ldvf floats fit in the (restart + 1) nk doubles of h->V
   while (true) {
     double beta;
+    const bool vf32 = vf32_ok && !h->v_f32_off;
     if (first_cycle && its >= o->ksp_max_it) break;
     if (first_cycle) {
       beta = bnorm;
-      pgxk_scale_copy(h->st, nk, bsign * (1.0 / beta), b, h->V);  // (bsign = -1: bitwise (-b) / beta)
+      if (vf32)
+        pgxk_scale_copy_f32(h->st, nk, bsign * (1.0 / beta), b, Vf);
+      else
+        pgxk_scale_copy(h->st, nk, bsign * (1.0 / beta), b, h->V);  // (bsign = -1: bitwise (-b) / beta)
     } else {
       // r = bsign b - J x
       PhaseTimer t(h, 3);
@@ -2712,27 +2750,26 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
       if (rc) return rc;
       res = beta;
       if (o->monitor > 1) printf("      ksp true residual after cycle: %.6e (rel %.3e)\n", beta, beta / bnorm);
-      if (beta <= target) break;
+      // (redo: the same residual as at the head of the abandoned cycle - x was not touched - which passed both tests then)
+      if (!redo && beta <= target) break;
       // attainable-accuracy exit: a full restart cycle that gains < 10x once we are at LU-level residuals
-      if (beta > 0.1 * prev_cycle_res && beta <= 1e-7 * bnorm) break;
+      if (!redo && beta > 0.1 * prev_cycle_res && beta <= 1e-7 * bnorm) break;
       if (its >= o->ksp_max_it) break;
       prev_cycle_res = beta;
-      pgxk_scale_copy(h->st, nk, 1.0 / beta, wk, h->V);
+      if (vf32)
+        pgxk_scale_copy_f32(h->st, nk, 1.0 / beta, wk, Vf);
+      else
+        pgxk_scale_copy(h->st, nk, 1.0 / beta, wk, h->V);
     }
+    const bool was_first = first_cycle;
     first_cycle = false;
+    redo = false;
+    bool abandoned = false;
+    double hn_bad = 0.0;
+    // float basis: the estimate is only trusted down to v_f32_gain times the residual this cycle started from
+    const double cycle_target = vf32 ? std::max(target, h->v_f32_gain * beta) : target;
     std::fill(g.begin(), g.end(), 0.0);
     g[0] = beta;
-    // Lazy normalisation (round 4): a new basis vector stays as the Gram-Schmidt pass left it, W_{j+1} = w', and only its scale
-    // s_{j+1} = 1 / |w'| is kept (v_i = s_i W_i): the V-cycle multiplies its right-hand side by s_j as its first launch reads it, the
-    // batched dot products come back as s_i^2 (W_i . w) - the coefficients the projection w' = w - sum_i (v_i . w) v_i applies to the
-    // stored W_i - and the pass over w that only divided it by its norm (67 MB read + written per iteration) is gone.  Only where
-    // the preconditioner is the single-precision cycle entered on level 0 (it is the one that takes the factor).
-    const bool lazy = h->lazy_norm && h->cgs_selective && !h->lu_active && h->degree == 1 && m + 2 <= PGX_DOT_SCALE_MAX && !h->lev.empty() &&
-                      f32_cycle_ok(h, 0, o->mg_nu);  // (the non-selective CGS2 kernels carry no scale factors: that mode runs un-lazy)
-    // Z_j in single precision (round 5): on this path z_j leaves a float cycle, so storing it as one float2 field loses nothing - the
-    // cycle's last launch writes it in place, the operator apply reads it (k_st_spmv_r<true>), the solution update sums it
-    // (k_lincomb_f2): 100 MB less per Krylov iteration at 2048^2 than the fp64 pair.  w = J z_j, the basis V and H stay fp64.
-    const bool zf32 = z_f32_active(h, o->mg_nu);
     float2* const Zf = reinterpret_cast<float2*>(h->Z);
     PgxDotScale sc2;  // s_i^2
     std::vector<double> sv((size_t)m + 2, 1.0);  // s_i
@@ -2745,7 +2782,9 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
         PhaseTimer t(h, 4);
         h->rhs_scale = lazy ? sv[j] : 1.0;
         h->zf_out = zf32 ? Zf + (size_t)j * h->nd : nullptr;
+        h->rhs_f32 = vf32 ? Vf + (size_t)j * ldvf : nullptr;  // (vj is then not read: the cycle's first launch takes the float pair)
         rc = precond(h, vj, zj, o->mg_nu, omega);
+        h->rhs_f32 = nullptr;
         h->zf_out = nullptr;
         h->rhs_scale = 1.0;
         if (rc) return rc;
@@ -2756,18 +2795,19 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
           spmv_dev(h, zj, h->w);
           gather_owned(h, h->w, h->V + (size_t)(j + 1) * nk);
         } else if (zf32) {
-          double* const wn = h->V + (size_t)(j + 1) * n2;
+          double* const wn = vf32 ? h->w : h->V + (size_t)(j + 1) * n2;  // float basis: w stays fp64, in the scratch
           pgxk_st_spmv(h->st, h->lev[0], h->alpha, nullptr, nullptr, h->xcd_remap ? 1 : 0, wn, wn + h->nd, Zf + (size_t)j * h->nd);
         } else {
           spmv_dev(h, zj, h->V + (size_t)(j + 1) * n2);
         }
       }
-      // w = J z_j was written straight into the V_{j+1} slot.  CGS2 (classical Gram-Schmidt, always two
+      // w = J z_j was written straight into the V_{j+1} slot (float basis: into h->w).  CGS2 (classical Gram-Schmidt, always two
       // passes: one pass loses orthogonality on these ill-conditioned systems and the true residual stalls).
       // Each pass is ONE batched dot kernel [h; ww] = [V_0..V_j, w]^T w plus one batched axpy; the norm of the
       // result comes from Pythagoras on the second pass (|w''|^2 = ww' - |h2|^2, cancellation-free because
       // the second pass removes almost nothing), so no separate norm kernel.
       double* wj = h->V + (size_t)(j + 1) * nk;
+      float* const vnext = Vf + (size_t)(j + 1) * ldvf;  // float basis: where (float) w' goes
       double hn = 0.0;
       {
         PhaseTimer t(h, 5);
@@ -2776,18 +2816,27 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
         const PgxDotScale* const dsc = lazy ? &sc2 : nullptr;
         // pass 1: h1 = V^T w.  passes 2+3 fused: w' = w - V h1 and [h2; |w'|^2] in one sweep over the basis.
         // Sharded: each batch of partial dot products is completed by ONE packed all-reduce, enqueued on the stream.
-        pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h1, dsc, h->gs_wide);
+        if (vf32)
+          pgxk_multidot_f32(h->st, nk, j + 1, Vf, ldvf, h->w, nullptr, h->partials, d_h1, dsc, h->gs_wide);
+        else
+          pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h1, dsc, h->gs_wide);
         if (dist && (rc = allreduce_dev(h, d_h1, j + 1))) return rc;
         double wp2, h1h1 = 0.0, hh = 0.0;
         bool second;
         if (h->cgs_selective) {
           // lean second pass: w' = w - V h1 and |w'|^2; V^T w' (for the second projection) only if the test below asks for it
           if (fused_readback(h)) {  // the norm's second stage and the read-back of [h1; |w'|^2] in one launch
-            pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, nullptr, h->gs_wide);
+            if (vf32)
+              pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h1, 0, h->w, vnext, h->partials, nullptr, h->gs_wide);
+            else
+              pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, nullptr, h->gs_wide);
             if ((rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_h2 + j + 1, (size_t)(m + 2) + j + 1, d_h1, (size_t)(j + 1), 0)))
               return rc;
           } else {
-            pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, d_h2 + j + 1, h->gs_wide);
+            if (vf32)
+              pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h1, 0, h->w, vnext, h->partials, d_h2 + j + 1, h->gs_wide);
+            else
+              pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, d_h2 + j + 1, h->gs_wide);
             if (dist && (rc = allreduce_dev(h, d_h2 + j + 1, 1))) return rc;
             if ((rc = replica_agree(h, h->d_small, 2 * (size_t)(m + 2)))) return rc;
             if ((rc = fetch_small(h, d_h1, (size_t)(j + 1), 0, d_h2 + j + 1, 1, (size_t)(m + 2) + j + 1))) return rc;
@@ -2801,7 +2850,10 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
           // first one cancelled most of w, |w'| < eta |w| with |w|^2 = |w'|^2 + |h1|^2
           second = wp2 < h->cgs_eta2 * (wp2 + h1h1);
           if (second) {
-            pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h2, dsc, h->gs_wide);
+            if (vf32)  // against the vector as stored: (float) w', widened
+              pgxk_multidot_f32(h->st, nk, j + 1, Vf, ldvf, nullptr, vnext, h->partials, d_h2, dsc, h->gs_wide);
+            else
+              pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h2, dsc, h->gs_wide);
             if (dist && (rc = allreduce_dev(h, d_h2, j + 1))) return rc;
             if ((rc = replica_agree(h, d_h2, (size_t)(j + 1)))) return rc;
             if ((rc = fetch_small(h, d_h2, (size_t)(j + 1), (size_t)(m + 2)))) return rc;
@@ -2825,7 +2877,20 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
           H[(size_t)i * m + j] = h->h_small[i] + h2;
           hh += h2 * h2;
         }
-        if (second) {
+        if (second && vf32) {
+          // float basis: the stored vector, widened, is projected again and re-rounded in the same launch, which also sums the squares of
+          // what it stores: hn is the norm of the vector kept (Pythagoras would describe the unrounded one).  One more small read-back,
+          // on the rare path only.
+          double* const d_n2 = d_h2 + j + 1;
+          if (fused_readback(h)) {
+            pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h2, 1, h->w, vnext, h->partials, nullptr, h->gs_wide);
+            if ((rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_n2, (size_t)(m + 2) + j + 1))) return rc;
+          } else {
+            pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h2, 1, h->w, vnext, h->partials, d_n2, h->gs_wide);
+            if ((rc = fetch_small(h, d_n2, 1, (size_t)(m + 2) + j + 1))) return rc;
+          }
+          hn = std::sqrt(std::max(h->h_small[(m + 2) + j + 1], 0.0));
+        } else if (second) {
           hn = std::sqrt(std::max(wp2 - hh, 0.0));
           // last pass fused with the normalisation: v_{j+1} = (w' - V h2) / hn   (|w''|^2 = |w'|^2 - |h2|^2, Pythagoras)
           if (hn > 0.0) {
@@ -2838,6 +2903,16 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
           hn = std::sqrt(std::max(wp2, 0.0));
           if (hn > 0.0 && !lazy) pgxk_scale_copy(h->st, nk, 1.0 / hn, wj, wj);
           ++h->cgs_skipped;
+        }
+        // Guard of the float basis: an overshot Newton iterate puts 1e300 into D(psi), and w = J z_j can then leave the float range.  A
+        // new vector whose norm is not finite (or above v_f32_max) ends the float basis for the rest of this Newton solve: this cycle is
+        // abandoned - its columns are dropped, x is not updated, its iterations stay counted - and redone in fp64 from the same residual.
+        if (vf32 && (!std::isfinite(hn) || hn > h->v_f32_max)) {
+          ++its;
+          ++h->cgs_total;
+          hn_bad = hn;
+          abandoned = true;
+          break;
         }
         if (lazy && hn > 0.0) {
           sv[j + 1] = 1.0 / hn;
@@ -2869,7 +2944,7 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
         *relres = res / bnorm;
         return PGX_OK;
       }
-      if (res <= target || hn == 0.0) {
+      if (res <= cycle_target || hn == 0.0) {
         ++j;
         break;
       }
@@ -2881,6 +2956,14 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
         h->omega_now = omega = omega_safe;  // sticky until pgx_newton_solve returns: later iterates are rough too
         if (o->monitor > 1) printf("      ksp stagnates: smoother damping -> %.2f for the rest of this Newton solve\n", omega);
       }
+    }
+    if (abandoned) {
+      h->v_f32_off = true;
+      if (o->monitor > 1) printf("      ksp: basis vector outside the float range (norm %.3e): this cycle again, with the fp64 basis\n", hn_bad);
+      res = beta;
+      first_cycle = was_first;  // the first cycle starts again from b (x is still unset with PGX_LEAN_RHS), a later one from b - J x
+      redo = !was_first;
+      continue;
     }
     // y = H^-1 g (upper triangular), x += Z y
     for (int i = j - 1; i >= 0; --i) {
@@ -3319,6 +3402,7 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
   int its = 0, lin = 0, rsn = 0;
   double fnorm = 0, fnorm0 = 0, ttol = 0;
   h->omega_now = 0.0;
+  h->v_f32_off = false;
   int rc = PGX_OK;
   // Sharded: x, xw, dx, F are local vectors (owned + ghost rows); norms run on owned-compact copies (rhs doubles as the
   // compact copy of F), and the ghost rows of the iterate are refreshed after every update, before the next assembly.

@@ -125,6 +125,7 @@ int pgxk_observables_blocks(int nc);
 // vectors (length len)
 void pgxk_axpy(hipStream_t st, size_t len, double a, const double* x, double* y);          // y += a x
 void pgxk_scale_copy(hipStream_t st, size_t len, double a, const double* x, double* y);    // y = a x
+void pgxk_scale_copy_f32(hipStream_t st, size_t len, double a, const double* x, float* y);  // y = (float)(a x)
 void pgxk_set(hipStream_t st, size_t len, double a, double* y);
 void pgxk_to_float(hipStream_t st, size_t len, const double* x, float* y);
 // out[i] = V_i . w, i<nv (V_i = V + i*ldv).  partials: [PGX_RED_BLOCKS * nv] scratch
@@ -137,6 +138,10 @@ struct PgxDotScale {
 // wide: vectors per launch (8 or 16); out == nullptr: no second stage, partials[0 .. pgxk_multidot_blocks(len) * nv) stay for the caller
 void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
                    double* out, const PgxDotScale* scale = nullptr, int wide = 8);
+// the same against a FLOAT basis (fgmres: the lean P1 path), widened to fp64 as it is read; ldv in floats, a multiple of 4.  The vector is
+// fp64 (w) or, w == nullptr, a float one (wf: the stored next basis vector, second projection).  Same grid, partials and second stage.
+void pgxk_multidot_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* w, const float* wf, double* partials,
+                       double* out, const PgxDotScale* scale = nullptr, int wide = 8);
 int pgxk_multidot_blocks(size_t len);
 int pgxk_stream_blocks(size_t len);  // grid of the streaming vector kernels (pgxk_multiaxpy_norm's partials)
 // out[r] = sum of row r of partials ([nrows][nb]) in the shape of k_reduce_rows, then out[0 .. nrows) -> hout and src1[0 .. n1) -> dst1
@@ -276,6 +281,11 @@ void pgxk_multiaxpy_scale(hipStream_t st, size_t len, int nv, const double* V, s
 // w -= V h and out[0] = |w'|^2 in one pass over the basis (selective CGS2: the lean second pass)
 void pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w,
                          double* partials, double* out, int wide = 8);
+// float basis: w' = w - V h leaves as vnext = (float) w' and out[0] = |vnext|^2, the norm of the ROUNDED vector.  More than `wide`
+// vectors: the chunks before the last keep w' in the fp64 scratch w.  from_vnext != 0: the vector projected is vnext itself
+// (second projection), w is scratch only
+void pgxk_multiaxpy_norm_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* h, int from_vnext, double* w,
+                             float* vnext, double* partials, double* out, int wide = 8);
 // ---- single-precision V-cycle legs (pgx_mg32.hip) ----
 // Dq <- Dh (values above 1e30 are clamped: an overshot Newton iterate must not put infinities into the preconditioner)
 void pgxk_f_pack_d(hipStream_t st, const GridLevel& L);
@@ -283,14 +293,16 @@ void pgxk_f_pack_d(hipStream_t st, const GridLevel& L);
 //   first != 0: S^K(0), xf unused; else S^K(xf + P x_c) with the coarse correction x_c = cf (float2: the next level is single
 //   precision) or (cdu, cdp) (fp64 arrays), all three nullptr: none.  C = the coarse level (its nx), nullptr without correction.
 //   b64u / b64p != nullptr: the right-hand side is read from these fp64 arrays and its float2 copy written to L.bf for the
-//   launches that follow (finest level, first launch); else L.bf is read.
+//   launches that follow (finest level, first launch); else L.bf is read.  b32u / b32p != nullptr: the same from two float arrays
+//   (a vector of FGMRES's float basis); they take precedence over the fp64 pair.
 //   y64u / y64p != nullptr: the result is written as fp64 arrays (finest level, last launch); else to yf.
 //   cbf or (cb64u, cb64p) != nullptr: the launch also restricts the residual of its result to the coarse level C, like
 //   pgxk_f_resid_restrict (no coarse correction and a float2 result in that case).
 void pgxk_f_smooth(hipStream_t st, int K, int first, const GridLevel& L, double alpha, const float2* xf, const double* b64u,
                    const double* b64p, const GridLevel* C, const float2* cf, const double* cdu, const double* cdp, double omega,
                    int remap, float2* yf, double* y64u, double* y64p, float2* cbf = nullptr, double* cb64u = nullptr,
-                   double* cb64p = nullptr, double bscale = 1.0);  // bscale: factor applied to the fp64 right-hand side as it is read
+                   double* cb64p = nullptr, double bscale = 1.0,  // bscale: factor applied to the fp64 / float right-hand side as it is read
+                   const float* b32u = nullptr, const float* b32p = nullptr);
 // b_c = P^T (L.bf - J xf): to cbf (float2) or, when cb64u != nullptr, to the fp64 arrays (cb64u, cb64p) of an fp64 coarse level
 void pgxk_f_resid_restrict(hipStream_t st, const GridLevel& L, double alpha, const float2* xf, const GridLevel& C, int remap,
                            float2* cbf, double* cb64u, double* cb64p);

@@ -15,6 +15,7 @@
 #include "pgx_internal.h"
 #include "pgx_stencil.h"
 #include <algorithm>
+#include <type_traits>
 
 #define WAVE 64
 
@@ -1167,6 +1168,24 @@ void pgxk_scale_copy(hipStream_t st, size_t len, double a, const double* x, doub
                      (double2*)y);
 }
 
+// y = (float)(a x): the first vector of a Krylov cycle with a float basis.  Four elements per lane (two 16-byte loads, one 16-byte
+// store); len mod 4 = 2 (see GsLane): the last two elements go to the lane whose walk ends on them
+__global__ void __launch_bounds__(PGX_BLOCK) k_scale_copy_f32(size_t ng, int tail, double a, const double2* __restrict__ x, float* __restrict__ y) {
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  for (; i < ng; i += (size_t)gridDim.x * blockDim.x) {
+    const double2 x0 = x[2 * i], x1 = x[2 * i + 1];
+    *(float4*)(y + 4 * i) = make_float4((float)(x0.x * a), (float)(x0.y * a), (float)(x1.x * a), (float)(x1.y * a));
+  }
+  if (tail && i == ng) {
+    const double2 x0 = x[2 * i];
+    *(float2*)(y + 4 * i) = make_float2((float)(x0.x * a), (float)(x0.y * a));
+  }
+}
+void pgxk_scale_copy_f32(hipStream_t st, size_t len, double a, const double* x, float* y) {
+  const size_t ng = len / 4;
+  hipLaunchKernelGGL(k_scale_copy_f32, stream_grid(ng + 1), dim3(PGX_BLOCK), 0, st, ng, (int)(len - 4 * ng), a, (const double2*)x, y);
+}
+
 __global__ void __launch_bounds__(PGX_BLOCK) k_set(size_t len, double a, double* __restrict__ y) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < len; i += (size_t)gridDim.x * blockDim.x)
     y[i] = a;
@@ -1182,23 +1201,104 @@ void pgxk_to_float(hipStream_t st, size_t len, const double* x, float* y) {
   hipLaunchKernelGGL(k_to_float, stream_grid(len), dim3(PGX_BLOCK), 0, st, len, x, y);
 }
 
+// What a lane moves per step of the Gram-Schmidt kernels: 16 bytes of every basis vector, G = 2 doubles or 4 floats, widened to
+// double, against the same G elements of w (fp64: G / 2 loads of 16 bytes; float: one).  A float vector of the Krylov method has
+// len = 2 nd elements with nd odd on every multigrid grid, so len mod 4 = 2: its last two elements are the `tail` (8-byte loads of
+// the floats), taken by the lane whose grid-stride walk ends exactly on them - a fixed lane, so the sums stay reproducible.
+template <class T>
+struct GsLane;
+template <>
+struct GsLane<double> {
+  static constexpr int G = 2;
+};
+template <>
+struct GsLane<float> {
+  static constexpr int G = 4;
+};
+template <int G>
+__device__ __forceinline__ void gs_ld_basis(const double* p, double* a) {  // streamed once: non-temporal
+  static_assert(G == 2, "fp64 basis: two elements per lane");
+  const double2 v = ldnt2((const double2*)p);
+  a[0] = v.x, a[1] = v.y;
+}
+template <int G>
+__device__ __forceinline__ void gs_ld_basis(const float* p, double* a) {
+  typedef float vf __attribute__((ext_vector_type(G)));
+  const vf v = __builtin_nontemporal_load((const vf*)p);
+#pragma unroll
+  for (int k = 0; k < G; ++k) a[k] = (double)v[k];
+}
+template <int G>
+__device__ __forceinline__ void gs_ld(const double* p, double* a) {
+#pragma unroll
+  for (int k = 0; k < G; k += 2) {
+    const double2 v = *(const double2*)(p + k);
+    a[k] = v.x, a[k + 1] = v.y;
+  }
+}
+template <int G>
+__device__ __forceinline__ void gs_ld(const float* p, double* a) {
+  typedef float vf __attribute__((ext_vector_type(G)));
+  const vf v = *(const vf*)p;
+#pragma unroll
+  for (int k = 0; k < G; ++k) a[k] = (double)v[k];
+}
+// store G elements; s <- the values as stored (rounded where the destination is float), widened
+template <int G>
+__device__ __forceinline__ void gs_st(double* p, const double* a, double* s) {
+#pragma unroll
+  for (int k = 0; k < G; k += 2) {
+    *(double2*)(p + k) = make_double2(a[k], a[k + 1]);
+    s[k] = a[k], s[k + 1] = a[k + 1];
+  }
+}
+template <int G>
+__device__ __forceinline__ void gs_st(float* p, const double* a, double* s) {
+  typedef float vf __attribute__((ext_vector_type(G)));
+  vf v;
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    v[k] = (float)a[k];
+    s[k] = (double)v[k];
+  }
+  *(vf*)p = v;
+}
+
 // out[i] = V_i . w : each block streams a slice of w ONCE for NV vectors (Gram-Schmidt is the
 // second-largest HBM consumer of the Newton solve; batching cuts its traffic from 2 to 1+1/NV
 // vector reads per dot product).  Two-stage, fixed grid -> bitwise reproducible.
-template <int NV>
-__global__ void __launch_bounds__(PGX_BLOCK) k_multidot(size_t len2, const double2* __restrict__ V, size_t ldv2,
-                                                        const double2* __restrict__ w,
+// VT: element type of the basis (fp64, or the float basis of the lean P1 path); WT: that of w.  Products and sums are fp64.
+// ng = len / G groups, tail = len - G ng (0 or 2; always 0 for an fp64 basis), ldv in elements.
+template <int NV, class VT, class WT>
+__global__ void __launch_bounds__(PGX_BLOCK) k_multidot(size_t ng, int tail, const VT* __restrict__ V, size_t ldv,
+                                                        const WT* __restrict__ w,
                                                         double* __restrict__ partials, int pstride, int poff) {
+  constexpr int G = GsLane<VT>::G;
   __shared__ double sm[PGX_BLOCK / WAVE];
   double acc[NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < len2; i += (size_t)gridDim.x * blockDim.x) {
-    const double2 wv = w[i];
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  for (; i < ng; i += (size_t)gridDim.x * blockDim.x) {
+    double wv[G];
+    gs_ld<G>(w + G * i, wv);
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      const double2 a = ldnt2(V + v * ldv2 + i);
-      acc[v] += a.x * wv.x + a.y * wv.y;
+      double a[G];
+      gs_ld_basis<G>(V + v * ldv + G * i, a);
+#pragma unroll
+      for (int k = 0; k < G; k += 2) acc[v] += fma(a[k], wv[k], a[k + 1] * wv[k + 1]);  // the contraction spelled out: every
+                                                                                      // instantiation rounds alike, whatever the compiler would pick
+    }
+  }
+  if (G == 4 && tail && i == ng) {
+    double wv[2];
+    gs_ld<2>(w + G * i, wv);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      double a[2];
+      gs_ld<2>(V + v * ldv + G * i, a);
+      acc[v] += fma(a[0], wv[0], a[1] * wv[1]);
     }
   }
 #pragma unroll
@@ -1234,21 +1334,24 @@ int pgxk_multidot_blocks(size_t len) {
   return nb == 0 ? 1 : (int)nb;
 }
 
-void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
-                   double* out, const PgxDotScale* scale, int wide) {
-  const size_t len2 = len / 2, ldv2 = ldv / 2;
+template <class VT, class WT>
+static void multidot_t(hipStream_t st, size_t len, int nv, const VT* V, size_t ldv, const WT* w, double* partials, double* out,
+                       const PgxDotScale* scale, int wide) {
+  constexpr int G = GsLane<VT>::G;
+  const size_t ng = len / G;
+  const int tail = (int)(len - G * ng);
   const size_t nb = (size_t)pgxk_multidot_blocks(len);
   dim3 grid((unsigned)nb), block(PGX_BLOCK);
   const int cap = wide > 16 ? 16 : wide < 1 ? 1 : wide;
   int done = 0;
   while (done < nv) {
     const int rem = nv - done;
-    const double2* Vp = (const double2*)(V + (size_t)done * ldv);
+    const VT* Vp = V + (size_t)done * ldv;
     // one launch per chunk of at most `wide` (8 or 16) vectors, the last chunk of EXACTLY the remaining size: w is read once per
     // chunk (the 8/4/2/1 split of rounds 1-3 read it up to three times); the per-vector partials do not depend on the grouping
 #define PGX_MD(N)                                                                                                          \
   case N:                                                                                                                  \
-    hipLaunchKernelGGL(k_multidot<N>, grid, block, 0, st, len2, Vp, ldv2, (const double2*)w, partials, nv, done);          \
+    hipLaunchKernelGGL((k_multidot<N, VT, WT>), grid, block, 0, st, ng, tail, Vp, ldv, w, partials, nv, done);             \
     break
     const int take = rem >= cap ? cap : rem;
     switch (take) {
@@ -1277,6 +1380,17 @@ void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t l
     hipLaunchKernelGGL(k_reduce_partials_scaled, dim3(nv), block, 0, st, (int)nb, nv, partials, *scale, out);
   else
     hipLaunchKernelGGL(k_reduce_partials, dim3(nv), block, 0, st, (int)nb, nv, partials, out);
+}
+void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
+                   double* out, const PgxDotScale* scale, int wide) {
+  multidot_t(st, len, nv, V, ldv, w, partials, out, scale, wide);
+}
+void pgxk_multidot_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* w, const float* wf,
+                       double* partials, double* out, const PgxDotScale* scale, int wide) {
+  if (w)
+    multidot_t(st, len, nv, V, ldv, w, partials, out, scale, wide);
+  else
+    multidot_t(st, len, nv, V, ldv, wf, partials, out, scale, wide);
 }
 
 // The second stage of a two-stage reduction and the read-back of its result in ONE one-block launch: rows of nb partials are
@@ -1483,55 +1597,96 @@ void pgxk_multiaxpy_scale(hipStream_t st, size_t len, int nv, const double* V, s
 // (fixed-shape two-stage reduction: reproducible).  The lean second pass of selective CGS2: one read of the basis, one
 // read-modify-write of w, no LDS parking of basis slices (k_axpy_dot does that to get V^T w' in the same pass, which is only
 // needed when the second projection is - 11 of 266 iterations at 2048^2).
-template <int NV, bool NORM>
-__global__ void __launch_bounds__(PGX_BLOCK) k_multiaxpy_norm(size_t len2, const double2* __restrict__ V, size_t ldv2,
-                                                              const double* __restrict__ h, double2* __restrict__ w,
+// VT: element type of the basis, WT: that of the vector read (see k_multidot); the projection is fp64.  With an fp64 basis w is
+// updated in place.  With a float basis the vector is read as WT from win and leaves as OT: the LAST chunk (NORM) stores (float) w' -
+// the next basis vector - and sums the squares of the ROUNDED values, so the norm is that of the vector stored; a chunk before it
+// leaves w' in fp64 (the scratch w), whatever it read: the result does not depend on the chunking.  WT == OT: in place, win unused.
+template <int NV, bool NORM, class VT, class WT>
+__global__ void __launch_bounds__(PGX_BLOCK) k_multiaxpy_norm(size_t ng, int tail, const VT* __restrict__ V, size_t ldv,
+                                                              const double* __restrict__ h, const WT* __restrict__ win,
+                                                              typename std::conditional<NORM && std::is_same<VT, float>::value, float, double>::type* __restrict__ wout,
                                                               double* __restrict__ partials) {
+  typedef typename std::conditional<NORM && std::is_same<VT, float>::value, float, double>::type OT;
+  constexpr int G = GsLane<VT>::G;
+  const WT* const wi = std::is_same<WT, OT>::value ? (const WT*)wout : win;
   __shared__ double sm[PGX_BLOCK / WAVE];
   double hv[NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) hv[v] = h[v];
   double acc = 0.0;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < len2; i += (size_t)gridDim.x * blockDim.x) {
-    double2 wv = w[i];
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  for (; i < ng; i += (size_t)gridDim.x * blockDim.x) {
+    double wv[G], s[G];
+    gs_ld<G>(wi + G * i, wv);
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      const double2 a = ldnt2(V + v * ldv2 + i);
-      wv.x -= hv[v] * a.x;
-      wv.y -= hv[v] * a.y;
+      double a[G];
+      gs_ld_basis<G>(V + v * ldv + G * i, a);
+#pragma unroll
+      for (int k = 0; k < G; ++k) wv[k] -= hv[v] * a[k];
     }
-    w[i] = wv;
-    if (NORM) acc += wv.x * wv.x + wv.y * wv.y;
+    gs_st<G>(wout + G * i, wv, s);
+    if (NORM) {
+#pragma unroll
+      for (int k = 0; k < G; k += 2) acc += fma(s[k + 1], s[k + 1], s[k] * s[k]);
+    }
+  }
+  if (G == 4 && tail && i == ng) {
+    double wv[2], s[2];
+    gs_ld<2>(wi + G * i, wv);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      double a[2];
+      gs_ld<2>(V + v * ldv + G * i, a);
+      wv[0] -= hv[v] * a[0];
+      wv[1] -= hv[v] * a[1];
+    }
+    gs_st<2>(wout + G * i, wv, s);
+    if (NORM) acc += fma(s[1], s[1], s[0] * s[0]);
   }
   if (NORM) {
     const double r = block_sum(acc, sm);
     if (threadIdx.x == 0) partials[blockIdx.x] = r;
   }
 }
-template <int NV>
-static void launch_multiaxpy_norm(hipStream_t st, dim3 grid, size_t len2, const double2* Vp, size_t ldv2, const double* h, bool norm,
-                                  double2* w, double* partials) {
-  if (norm)
-    hipLaunchKernelGGL((k_multiaxpy_norm<NV, true>), grid, dim3(PGX_BLOCK), 0, st, len2, Vp, ldv2, h, w, partials);
-  else
-    hipLaunchKernelGGL((k_multiaxpy_norm<NV, false>), grid, dim3(PGX_BLOCK), 0, st, len2, Vp, ldv2, h, w, partials);
-}
 int pgxk_stream_blocks(size_t len) { return (int)stream_grid(len / 2).x; }
-// out[0] = |w - V h|^2, w updated in place.  partials: >= pgxk_stream_blocks(len) doubles.  out == nullptr: the block partials
-// stay in partials[0 .. pgxk_stream_blocks(len)) for the caller's own second stage (pgxk_reduce_publish)
-void pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w,
-                         double* partials, double* out, int wide) {
-  const size_t len2 = len / 2, ldv2 = ldv / 2;
-  dim3 grid = stream_grid(len2);
+// one chunk of N vectors; inf: the vector is read as float from wf (the stored next basis vector: second projection), else as fp64 from w
+template <int N, class VT>
+static void launch_multiaxpy_norm(hipStream_t st, dim3 grid, size_t ng, int tail, const VT* Vp, size_t ldv, const double* h, bool last,
+                                  bool inf, double* w, float* wf, double* partials) {
+  const dim3 block(PGX_BLOCK);
+  if constexpr (std::is_same<VT, double>::value) {
+    if (last)
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, double, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials);
+    else
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, false, double, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials);
+  } else {
+    if (last && inf)
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, float, float>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const float*)nullptr, wf, partials);
+    else if (last)
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, float, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)w, wf, partials);
+    else if (inf)
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, false, float, float>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const float*)wf, w, partials);
+    else
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, false, float, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials);
+  }
+}
+template <class VT>
+static void multiaxpy_norm_t(hipStream_t st, size_t len, int nv, const VT* V, size_t ldv, const double* h, bool inf, double* w, float* wf,
+                             double* partials, double* out, int wide) {
+  constexpr int G = GsLane<VT>::G;
+  const size_t ng = len / G;
+  const int tail = (int)(len - G * ng);
+  dim3 grid = stream_grid(len / 2);
   const int cap = wide > 16 ? 16 : wide < 1 ? 1 : wide;
   int done = 0;
   while (done < nv) {
     const int step = std::min(cap, nv - done);
     const bool last = done + step == nv;
-    const double2* Vp = (const double2*)(V + (size_t)done * ldv);
-#define PGX_MAN(N)                                                                                         \
-  case N:                                                                                                  \
-    launch_multiaxpy_norm<N>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials);            \
+    const VT* Vp = V + (size_t)done * ldv;
+#define PGX_MAN(N)                                                                                                     \
+  case N:                                                                                                              \
+    launch_multiaxpy_norm<N>(st, grid, ng, tail, Vp, ldv, h + done, last, inf && done == 0, w, wf, partials);          \
     break
     switch (step) {
       PGX_MAN(16);
@@ -1549,12 +1704,22 @@ void pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, si
       PGX_MAN(4);
       PGX_MAN(3);
       PGX_MAN(2);
-      default: launch_multiaxpy_norm<1>(st, grid, len2, Vp, ldv2, h + done, last, (double2*)w, partials); break;
+      default: launch_multiaxpy_norm<1>(st, grid, ng, tail, Vp, ldv, h + done, last, inf && done == 0, w, wf, partials); break;
     }
 #undef PGX_MAN
     done += step;
   }
   if (out) hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(PGX_BLOCK), 0, st, (int)grid.x, partials, out);
+}
+// out[0] = |w - V h|^2, w updated in place.  partials: >= pgxk_stream_blocks(len) doubles.  out == nullptr: the block partials
+// stay in partials[0 .. pgxk_stream_blocks(len)) for the caller's own second stage (pgxk_reduce_publish)
+void pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w,
+                         double* partials, double* out, int wide) {
+  multiaxpy_norm_t(st, len, nv, V, ldv, h, false, w, nullptr, partials, out, wide);
+}
+void pgxk_multiaxpy_norm_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* h, int from_vnext, double* w,
+                             float* vnext, double* partials, double* out, int wide) {
+  multiaxpy_norm_t(st, len, nv, V, ldv, h, from_vnext != 0, w, vnext, partials, out, wide);
 }
 
 void pgxk_multiaxpy(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w) {

@@ -181,6 +181,7 @@ __device__ __forceinline__ float2 f_add_coarse(float2 x, int gi, int gj, int nxc
 
 // ------------------------------------------------------------------------------------------------
 // K sweeps per launch.  IO: 0 = float2 in and out; 1 = right-hand side from fp64 arrays, copied to bfo (FIRST launches only);
+// 3 = the same from two float arrays (a vector of FGMRES's float basis: 8 instead of 16 bytes per vertex);
 // 2 = result to fp64 arrays (launches with an iterate only).  CADD: the coarse correction added to the iterate (f_add_coarse).
 // RR != 0: the launch ALSO restricts the residual of its result, b_c = P^T (b - J S^K(x)), to the coarse level (1: float2 cbf,
 // 2: fp64 arrays) - the last pre-smoothing launch and the residual + restriction launch of a level in one: the image carries
@@ -202,7 +203,16 @@ struct FSmoothArgs {
   float alpha, omega;
   double bscale;  // IO == 1: the fp64 right-hand side is multiplied by this as it is read (lazily normalised Krylov vectors)
   FConst sc;
+  const float *b32u, *b32p;  // IO == 3 (behind sc: the offsets the other instantiations read their arguments at stay put)
 };
+
+// the right-hand side at vertex v as the launch's IO reads it
+template <int IO>
+__device__ __forceinline__ float2 f_load_rhs(const FSmoothArgs& A, unsigned v) {
+  if (IO == 1) return make_float2((float)(A.b64u[v] * A.bscale), (float)(A.b64p[v] * A.bscale));
+  if (IO == 3) return make_float2((float)((double)A.b32u[v] * A.bscale), (float)((double)A.b32p[v] * A.bscale));
+  return A.bf[v];
+}
 
 template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR>
 __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float2* img0, float2* img1, float2* exch) {
@@ -227,7 +237,7 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
     if (lj < H0 - 1) {  // rows 1 .. H0-2 are updated; row 0 only hands its upward links to row 1
       const unsigned v = (unsigned)((j0 + lj) * sx + gi);
       dw[k] = Dq[v];
-      if (lj >= 1) rb[k] = (IO == 1) ? make_float2((float)(A.b64u[v] * A.bscale), (float)(A.b64p[v] * A.bscale)) : A.bf[v];
+      if (lj >= 1) rb[k] = f_load_rhs<IO>(A, v);
     }
   }
   if (!FIRST) {
@@ -274,7 +284,7 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
         g1[k] = mo * rc;
         g3[k] = ko * rc;
       }
-      if (IO == 1 && lj >= HALO && lj < H0 - HALO && own_lane) A.bfo[(unsigned)((j0 + lj) * sx + gi)] = rb[k];
+      if ((IO == 1 || IO == 3) && lj >= HALO && lj < H0 - HALO && own_lane) A.bfo[(unsigned)((j0 + lj) * sx + gi)] = rb[k];
     }
   }
   // (au, ap) = the two rows of J at image vertex q of row slot k
@@ -418,7 +428,7 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
       const int v = gj * sx + gi;
       dw[k] = Dq[v];
       bc[k] = A.mask[v] != 0;
-      if (lj >= 1 && lj < H0 - 1) rb[k] = (IO == 1) ? make_float2((float)(A.b64u[v] * A.bscale), (float)(A.b64p[v] * A.bscale)) : A.bf[v];
+      if (lj >= 1 && lj < H0 - 1) rb[k] = f_load_rhs<IO>(A, (unsigned)v);
       if (!FIRST) xa[k] = f_add_coarse<CADD>(A.xf[v], gi, gj, A.nxc, A.cf, A.cdu, A.cdp);
       if (!(A.sc.uniform && gi > 0 && gi < nx && gj > 0 && gj < ny)) {  // the grid's frame (or a level without uniform stencils)
 #pragma unroll
@@ -500,7 +510,7 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
       if (act) {
         if (s == K && in[k] && lj >= HALO && lj < H0 - HALO && own_lane) {
           const int v = (j0 + lj) * sx + gi;
-          if (IO == 1) A.bfo[v] = rb[k];
+          if (IO == 1 || IO == 3) A.bfo[v] = rb[k];
           if (IO == 2) {
             A.y64u[v] = (double)ou;
             A.y64p[v] = (double)op;
@@ -572,7 +582,12 @@ static void launch_f_smooth_rr_t(hipStream_t st, int first, FSmoothArgs& A, int 
   A.nbnd = (A.g.ntx * A.g.nty - nfast) * (TY / F32_TB);
   const dim3 grid(A.nbnd + nfast), block(F32_BLOCK);
   if (first) {
-    if (A.b64u) {
+    if (A.b32u) {
+      if (rr == 1)
+        hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 3, 0, 1>), grid, block, 0, st, A);
+      else
+        hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 3, 0, 2>), grid, block, 0, st, A);
+    } else if (A.b64u) {
       if (rr == 1)
         hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 1, 0, 1>), grid, block, 0, st, A);
       else
@@ -606,7 +621,9 @@ static void launch_f_smooth_t(hipStream_t st, int first, FSmoothArgs& A, int fas
   A.nbnd = (A.g.ntx * A.g.nty - nfast) * (TY / F32_TB);  // boundary tiles: sub-tiles of F32_TB rows
   const dim3 grid(A.nbnd + nfast), block(F32_BLOCK);
   if (first) {
-    if (A.b64u)
+    if (A.b32u)
+      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 3, 0, 0>), grid, block, 0, st, A);
+    else if (A.b64u)
       hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 1, 0, 0>), grid, block, 0, st, A);
     else
       hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 0, 0, 0>), grid, block, 0, st, A);
@@ -647,9 +664,12 @@ static int f32_tile_rows(const GridLevel& L) {
 
 void pgxk_f_smooth(hipStream_t st, int K, int first, const GridLevel& L, double alpha, const float2* xf, const double* b64u,
                    const double* b64p, const GridLevel* C, const float2* cf, const double* cdu, const double* cdp, double omega,
-                   int remap, float2* yf, double* y64u, double* y64p, float2* cbf, double* cb64u, double* cb64p, double bscale) {
+                   int remap, float2* yf, double* y64u, double* y64p, float2* cbf, double* cb64u, double* cb64p, double bscale,
+                   const float* b32u, const float* b32p) {
   FSmoothArgs A;
   A.bscale = bscale;
+  A.b32u = first ? b32u : nullptr;
+  A.b32p = first ? b32p : nullptr;
   A.nyc = C ? C->ny : 0;
   A.mask_c = C ? C->mask : nullptr;
   A.cbf = cbf;
@@ -669,10 +689,10 @@ void pgxk_f_smooth(hipStream_t st, int K, int first, const GridLevel& L, double 
   A.cf = first ? nullptr : cf;
   A.cdu = first ? nullptr : cdu;
   A.cdp = first ? nullptr : cdp;
-  A.b64u = first ? b64u : nullptr;
-  A.b64p = first ? b64p : nullptr;
-  A.bf = A.b64u ? nullptr : L.bf;
-  A.bfo = A.b64u ? L.bf : nullptr;
+  A.b64u = first && !A.b32u ? b64u : nullptr;
+  A.b64p = first && !A.b32u ? b64p : nullptr;
+  A.bf = (A.b64u || A.b32u) ? nullptr : L.bf;
+  A.bfo = (A.b64u || A.b32u) ? L.bf : nullptr;
   A.yf = yf;
   A.y64u = first ? nullptr : y64u;
   A.y64p = first ? nullptr : y64p;
