@@ -22,7 +22,9 @@
 #define F32_BLOCK 512
 // A/B switches of the interior tiles, both measured slower at 2049^2 and off: F32_WAVES_EU = 8 (a fourth workgroup per CU by a 64-VGPR
 // cap: 12-28 B of scratch per lane, level-0 launches +20 %) and F32_LEAN (the 2x2 block inverse recomputed per sweep: +1 %).
-// 32-row tiles (halo 1.31 instead of 1.52, but 94 VGPRs = two workgroups per CU) were +15 % and are not instantiated.
+// 32-row tiles (halo 1.31 instead of 1.52, but 94 VGPRs = two workgroups per CU) were +15 % and are not instantiated.  The fourth
+// workgroup came without a cap: this file is compiled with -fno-slp-vectorize (csrc/Makefile), which leaves the level-0 interior
+// tiles at 57 instead of 70 VGPRs - eight waves per SIMD - and the level-0 launches 15 % shorter.
 #ifndef F32_LEAN
 #define F32_LEAN 0
 #endif
