@@ -95,6 +95,16 @@ class pgx_nd_stats(C.Structure):
     ]
 
 
+class pgx_dn_stats(C.Structure):  # include/pgx_dn.h
+    _fields_ = [
+        ("n", C.c_int64),
+        ("interchanges", C.c_int64),
+        ("min_pivot", C.c_double),
+        ("max_pivot", C.c_double),
+        ("zero_pivots", C.c_int64),
+    ]
+
+
 class pgx_gc_problem(C.Structure):  # include/pgx_gc.h
     _fields_ = [
         ("nq", C.c_int32),
@@ -252,6 +262,28 @@ class pgx_ev_problem(C.Structure):  # include/pgx_ev.h
     ]
 
 
+class pgx_ma_problem(C.Structure):  # include/pgx_ma.h
+    _fields_ = [
+        ("nv", C.c_int32), ("nc", C.c_int32),
+        ("coords", C.POINTER(C.c_double)),
+        ("cells", C.POINTER(C.c_int32)),
+        ("degree", C.c_int32),
+        ("nu", C.c_int32), ("np", C.c_int32),
+        ("cell_dofs_u", C.POINTER(C.c_int32)),
+        ("cell_dofs_p", C.POINTER(C.c_int32)),
+        ("nq", C.c_int32),
+        ("qwts", C.POINTER(C.c_double)),
+        ("tab_u", C.POINTER(C.c_double)),
+        ("dtab_u", C.POINTER(C.c_double)),
+        ("tab_p", C.POINTER(C.c_double)),
+        ("dtab_p", C.POINTER(C.c_double)),
+        ("ln_rho", C.POINTER(C.c_double)),
+        ("n_bc", C.c_int32),
+        ("bc_dofs", C.POINTER(C.c_int32)),
+        ("g", C.POINTER(C.c_double)),
+    ]
+
+
 class pgx_partition(C.Structure):
     _fields_ = [
         ("rank", C.c_int32),
@@ -336,6 +368,15 @@ SYMBOLS = [
     ("pgx_nd_export_fronts", C.c_int,
      [_H, c_int64_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p, c_int32_p, c_int64_p, c_int32_p]),
     ("pgx_nd_export_dest", C.c_int, [_H, c_int64_p, c_int64_p]),
+    # dense direct solver with partial pivoting (include/pgx_dn.h)
+    ("pgx_dn_create", C.c_int, [C.c_int64, c_int32_p, c_int32_p, C.c_int, C.c_void_p, C.POINTER(_H)]),
+    ("pgx_dn_destroy", None, [_H]),
+    ("pgx_dn_last_error", C.c_char_p, [_H]),
+    ("pgx_dn_get_stats", C.c_int, [_H, C.POINTER(pgx_dn_stats)]),
+    ("pgx_dn_factor", C.c_int, [_H, c_double_p, C.c_int]),
+    ("pgx_dn_solve", C.c_int, [_H, c_double_p, c_double_p, C.c_int]),
+    ("pgx_dn_export_pivots", C.c_int, [_H, c_int32_p]),
+    ("pgx_dn_timing", C.c_int, [_H, C.c_int, c_double_p, c_double_p]),
     # example 06: gradient constraint, vector latent variable (include/pgx_gc.h)
     ("pgx_gc_create", C.c_int, [C.POINTER(pgx_mesh), C.POINTER(pgx_gc_problem), C.c_int, C.POINTER(_H)]),
     ("pgx_gc_create_general", C.c_int, [C.POINTER(pgx_gc_spaces), C.POINTER(pgx_gc_problem), C.c_int, C.POINTER(_H)]),
@@ -400,6 +441,21 @@ SYMBOLS = [
     ("pgx_ev_eval_nodes", C.c_int, [_H, c_double_p]),
     ("pgx_ev_lu_stats", C.c_int, [_H, C.POINTER(pgx_nd_stats)]),
     ("pgx_ev_lu_is_symmetric", C.c_int, [_H]),
+    # example 10: three-field mixed Monge-Ampere on the dense pivoting LU (include/pgx_ma.h)
+    ("pgx_ma_create", C.c_int, [C.POINTER(pgx_ma_problem), C.c_int, C.POINTER(_H)]),
+    ("pgx_ma_destroy", None, [_H]),
+    ("pgx_ma_last_error", C.c_char_p, [_H]),
+    ("pgx_ma_num_dofs", C.c_int, [_H, c_int64_p]),
+    ("pgx_ma_set_state", C.c_int, [_H, c_double_p]),
+    ("pgx_ma_get_state", C.c_int, [_H, c_double_p]),
+    ("pgx_ma_residual", C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
+    ("pgx_ma_jacobian_fill", C.c_int, [_H, c_double_p]),
+    ("pgx_ma_csr_export", C.c_int, [_H, c_int64_p, c_int64_p, c_int32_p, c_int32_p, c_double_p]),
+    ("pgx_ma_spmv", C.c_int, [_H, c_double_p, c_double_p]),
+    ("pgx_ma_newton_solve", C.c_int, [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("pgx_ma_l2_error", C.c_int, [_H, c_double_p, c_double_p]),
+    ("pgx_ma_lu_stats", C.c_int, [_H, C.POINTER(pgx_dn_stats)]),
+    ("pgx_ma_profile", C.c_int, [_H, C.c_int, c_double_p]),
 ]
 # the entry points the seven mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
 _MIXED_COMMON = [

@@ -1,5 +1,5 @@
 """The handle layer the mixed-matrix families share: examples 06 (`pgx_gc_*`), 02 (`pgx_sg_*`), 05 (`pgx_qvi_*`),
-08 (`pgx_ic_*`), 04 (`pgx_mp_*`), 03 (`pgx_fr_*`) and 07 (`pgx_ev_*`).  Each family exports the same entry points under its own prefix, all of them forwards to the shared driver
+08 (`pgx_ic_*`), 04 (`pgx_mp_*`), 03 (`pgx_fr_*`), 07 (`pgx_ev_*`) and 10 (`pgx_ma_*`, which has no previous iterate and no alpha).  Each family exports the same entry points under its own prefix, all of them forwards to the shared driver
 (csrc/pgx_mixed.hip).  A subclass names its prefix in `_prefix`; its constructor creates `self._h` and sets `_lib`, `_opts`,
 `solver` and `ndofs` (and `_flags` where its options take `snes_error_if_not_converged`).
 """

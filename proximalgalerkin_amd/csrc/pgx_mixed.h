@@ -64,6 +64,13 @@ struct MixedBase {
   std::vector<void*> allocs;
   virtual void residual_dev(const double* xin, double* Fout) = 0;  // F(x) incl. the BC rows, asynchronous on st
   virtual void jacobian_dev(const double* xin) = 0;                // fills Jv at x
+  // The linear-solve hook of the Newton drivers: factorise Jv, solve with the factorisation (device pointers, on st), the solver's error
+  // text, and its release before the stream goes.  Default (pgx_mixed.hip): the sparse LU `lu` (pgx_nd) through the row flip
+  // lu_flip_from.  pgx_ma overrides it with the dense LU with partial pivoting (pgx_dn): its Newton matrix is not quasi-definite.
+  virtual int lin_factor();
+  virtual int lin_solve(const double* rhs, double* out);
+  virtual const char* lin_error() const;
+  virtual void lin_release() {}
   virtual ~MixedBase() {}
 };
 

@@ -177,6 +177,7 @@ static void mx_release(MixedBase* h) {
   if (pgx_tune("PGX_LAZY_REPORT"))
     fprintf(stderr, "pgx: lazy refactorisation: %ld Newton systems solved with a stale LU (%ld LU solves), %ld attempts fell back\n",
             h->lazy_hits, h->lazy_its, h->lazy_misses);
+  h->lin_release();
   if (h->lu) pgx_nd_destroy(h->lu);
   for (void* p : h->allocs) hipFree(p);
   if (h->h_out) hipHostFree(h->h_out);
@@ -207,7 +208,8 @@ static __global__ void k_mx_copy_flip(int64_t len, int64_t from, const double* _
   if (i < len) y[i] = i >= from ? -x[i] : x[i];
 }
 // pgx_nd_factor of the current Jacobian / pgx_nd_solve, through the row flip of MixedBase::lu_flip_from
-static int mx_lu_factor(MixedBase* h) {
+int MixedBase::lin_factor() {
+  MixedBase* h = this;
   if (h->lu_flip_from < 0 || h->lu_flip_from >= h->ntot) return pgx_nd_factor(h->lu, h->Jv, 1);
   const int64_t k0 = h->h_rowptr[h->lu_flip_from], len = h->nnz - k0;
   // in place, stream-ordered: negate the tail rows, enqueue the factorisation (every kernel that reads the values is enqueued
@@ -217,7 +219,8 @@ static int mx_lu_factor(MixedBase* h) {
   if (len > 0) hipLaunchKernelGGL(k_mx_negate, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, h->st, len, h->Jv + k0);
   return rc;
 }
-static int mx_lu_solve(MixedBase* h, const double* rhs, double* out) {
+int MixedBase::lin_solve(const double* rhs, double* out) {
+  MixedBase* h = this;
   if (h->lu_flip_from < 0 || h->lu_flip_from >= h->ntot) return pgx_nd_solve(h->lu, rhs, out, 1);
   if (!h->lu_flip_buf) {
     void* q = nullptr;
@@ -229,6 +232,9 @@ static int mx_lu_solve(MixedBase* h, const double* rhs, double* out) {
                      h->lu_flip_buf);
   return pgx_nd_solve(h->lu, h->lu_flip_buf, out, 1);
 }
+const char* MixedBase::lin_error() const { return pgx_nd_last_error(lu); }
+static int mx_lu_factor(MixedBase* h) { return h->lin_factor(); }
+static int mx_lu_solve(MixedBase* h, const double* rhs, double* out) { return h->lin_solve(rhs, out); }
 
 // dx = J^{-1} b by LU + iterative refinement on the exact operator; returns the true relative residual
 static int mx_dot(MixedBase* h, const double* a, const double* b, double* out);
@@ -254,7 +260,7 @@ static int mx_linear_solve(MixedBase* h, const double* b, double* dx, const pgx_
   auto lusolve = [&](const double* rhs, double* out) -> int {
     MxTimer t(h, 3);
     int r2 = mx_lu_solve(h, rhs, out);
-    if (r2) h->err = std::string("direct solver: ") + pgx_nd_last_error(h->lu);
+    if (r2) h->err = std::string("direct solver: ") + h->lin_error();
     return r2;
   };
   if ((rc = lusolve(b, dx))) return rc;
@@ -325,7 +331,7 @@ static int mx_newton_linear(MixedBase* h, const pgx_snes_opts* opts, int newton_
     rc = mx_lu_factor(h);
   }
   if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(h->lu);
+    h->err = std::string("direct solver: ") + h->lin_error();
     h->lu_factored = false;
     return rc;
   }
@@ -491,7 +497,7 @@ static int mx_gmres_lu(MixedBase* h, const double* b, double* dx, double bnorm, 
       {
         MxTimer t(h, 3);
         if ((rc = mx_lu_solve(h, V(j), h->z))) {
-          h->err = std::string("direct solver: ") + pgx_nd_last_error(h->lu);
+          h->err = std::string("direct solver: ") + h->lin_error();
           return rc;
         }
       }
@@ -534,7 +540,7 @@ static int mx_gmres_lu(MixedBase* h, const double* b, double* dx, double bnorm, 
     {
       MxTimer t(h, 3);
       if ((rc = mx_lu_solve(h, h->r, h->z))) {
-        h->err = std::string("direct solver: ") + pgx_nd_last_error(h->lu);
+        h->err = std::string("direct solver: ") + h->lin_error();
         return rc;
       }
     }
@@ -593,7 +599,7 @@ static int mx_newton_solve_bt(MixedBase* h, const pgx_snes_opts* opts, int* reas
       rc = mx_lu_factor(h);
     }
     if (rc) {
-      h->err = std::string("direct solver: ") + pgx_nd_last_error(h->lu);
+      h->err = std::string("direct solver: ") + h->lin_error();
       return rc;
     }
     // dx = y = J^{-1} F (PETSc's direction; the update is x - lambda y)
@@ -764,7 +770,7 @@ static int mx_newton_solve_l2(MixedBase* h, const pgx_snes_opts* opts, int* reas
       rc = mx_lu_factor(h);
     }
     if (rc) {
-      h->err = std::string("direct solver: ") + pgx_nd_last_error(h->lu);
+      h->err = std::string("direct solver: ") + h->lin_error();
       return rc;
     }
     int ns = 0;
@@ -972,7 +978,7 @@ int mx_newton(MixedBase* h, const pgx_snes_opts* opts, int* reason, int* its, in
 
 int mx_profile(MixedBase* h, int enable, double ms[6]) {
   MXNEED(h);
-  pgx_nd_timing(h->lu, enable, nullptr, nullptr);
+  if (h->lu) pgx_nd_timing(h->lu, enable, nullptr, nullptr);
   if (ms)
     for (int i = 0; i < 6; ++i) ms[i] = h->ms[i];
   for (int i = 0; i < 6; ++i) h->ms[i] = 0;

@@ -4,6 +4,9 @@ Stands where the reference configures PETSc with ``"ksp_type": "preonly", "pc_ty
 "pc_factor_mat_solver_type": "mumps"`` (examples/01_obstacle_problem/obstacle_pg.py:129-131,
 examples/06_gradient_constraints/gradient_constraint_dolfinx.py:118-121).  No CPU numeric phase exists: `factor` and
 `solve` raise without a GPU; `device=-1` builds the symbolic structure only (statistics, tests).
+
+`DenseSolver` below mirrors include/pgx_dn.h: a dense LU with partial pivoting for the matrices the sparse solver - which never pivots
+across nodes - cannot take (examples/10_monge_ampere/monge_ampere_dolfinx.py:15-23).
 """
 from __future__ import annotations
 
@@ -130,6 +133,73 @@ class DirectSolver:
     def close(self):
         if self._h:
             self._lib.pgx_nd_destroy(self._h)
+            self._h = L._H()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DenseSolver:
+    """Dense LU with partial pivoting on the GPU - host mirror of include/pgx_dn.h, with the interface of `DirectSolver`.
+
+    For matrices that need row interchanges (the mixed Monge-Ampere Jacobian of examples/10_monge_ampere/monge_ampere_dolfinx.py,
+    which the reference hands to MUMPS, ``:15-23``): the CSR pattern is given once, `factor` scatters the values into an n x n
+    array and computes P A = L U with LAPACK's pivot rule, `solve` substitutes.  n <= 32768."""
+
+    MAX_N = 32768
+    NB = 64
+
+    def __init__(self, indptr, indices, device: int = 0):
+        self._lib = L.load()
+        self._h = L._H()
+        self.indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+        self.indices = np.ascontiguousarray(indices, dtype=np.int32)
+        self.n = len(self.indptr) - 1
+        rc = self._lib.pgx_dn_create(self.n, L.iptr(self.indptr), L.iptr(self.indices), int(device), None, C.byref(self._h))
+        if rc:
+            msg = self._lib.pgx_dn_last_error(None)
+            raise L.PgxError(f"pgx_dn_create failed (code {rc}): {msg.decode() if msg else ''}")
+
+    def _check(self, rc, what):
+        if rc:
+            msg = self._lib.pgx_dn_last_error(self._h)
+            raise L.PgxError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+
+    def stats(self) -> dict:
+        st = L.pgx_dn_stats()
+        self._check(self._lib.pgx_dn_get_stats(self._h, C.byref(st)), "pgx_dn_get_stats")
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def factor(self, data):
+        """Raises PgxError when a column has no nonzero pivot candidate (singular matrix); `stats()["zero_pivots"]` counts them."""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        assert data.shape == (int(self.indptr[-1]),)
+        self._check(self._lib.pgx_dn_factor(self._h, L.dptr(data), 0), "pgx_dn_factor")
+
+    def solve(self, b):
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        assert b.shape == (self.n,)
+        x = np.empty_like(b)
+        self._check(self._lib.pgx_dn_solve(self._h, L.dptr(b), L.dptr(x), 0), "pgx_dn_solve")
+        return x
+
+    def pivots(self) -> np.ndarray:
+        """The pivot vector of the last factorisation, 0-based and LAPACK-style (`scipy.linalg.lu_factor`'s second result)."""
+        piv = np.zeros(self.n, dtype=np.int32)
+        self._check(self._lib.pgx_dn_export_pivots(self._h, L.iptr(piv)), "pgx_dn_export_pivots")
+        return piv
+
+    def timing(self, enable=True):
+        f, s = C.c_double(), C.c_double()
+        self._check(self._lib.pgx_dn_timing(self._h, int(enable), C.byref(f), C.byref(s)), "pgx_dn_timing")
+        return f.value, s.value
+
+    def close(self):
+        if self._h:
+            self._lib.pgx_dn_destroy(self._h)
             self._h = L._H()
 
     def __del__(self):

@@ -45,6 +45,15 @@ def quadrature_rule(cell: str, degree: int, scheme: str | None = None):
         g, w = 0.5 * (g + 1.0), 0.5 * w
         n = len(g)
         return (np.ascontiguousarray(np.stack([np.tile(g, n), np.repeat(g, n)], axis=1)), np.ascontiguousarray(np.repeat(w, n) * np.tile(w, n)))
+    if cell == "triangle" and scheme == "GJ":  # the same collapsed rule on the triangle, (degree // 2 + 1)^2 points, weights sum to 1/2:
+        from scipy.special import roots_jacobi  # any degree (example 10 asks for 4k + 4 up to 60); the default lookup below is unchanged
+
+        n = degree // 2 + 1
+        (x0, w0), (x1, w1) = roots_jacobi(n, 0.0, 0.0), roots_jacobi(n, 1.0, 0.0)
+        a, c = 0.5 * (x1 + 1.0), 0.5 * (x0 + 1.0)
+        A, Cc = np.meshgrid(a, c, indexing="ij")
+        W = (w1 / 4.0)[:, None] * (w0 / 2.0)[None, :]
+        return np.ascontiguousarray(np.stack([(Cc * (1 - A)).ravel(), A.ravel()], axis=1)), np.ascontiguousarray(W.ravel())
     tabs = json.loads(_TABLES.read_text())
     if scheme not in (None, "default"):
         t = tabs.get(scheme)
