@@ -31,8 +31,21 @@
 #ifndef F32_WAVES_EU
 #define F32_WAVES_EU 2
 #endif
+// A/B switch of the six-sweep launches on tiles of 12 rows and more, measured slower at 2049^2 and off: F32_K6_SPLIT = 1 runs the
+// boundary sub-tiles (78 VGPRs) as a launch of their own (k_f_smooth<..., PART = 2>) in front of the interior tiles (PART = 1: 56
+// VGPRs = a fourth workgroup per CU at TY = 12, 67-70 at TY = 16 / 20).  The sub-tiles' launch takes 25-28 us when nothing runs
+// beside it; merged, TY = 20 holds three workgroups per CU either way (LDS) and the solve is 2.5 ms shorter.
+#ifndef F32_K6_SPLIT
+#define F32_K6_SPLIT 0
+#endif
+#ifndef F32_K6_TY_TOP
+#define F32_K6_TY_TOP 20  // tile rows of a six-sweep launch on levels above 513^2 (measured on 1025^2 and 2049^2: 12 / 16 / 20)
+#endif
 #define F32_RR_CYB 2  // coarse rows of a boundary sub-tile of the residual + restriction
 #define F32_TB 2  // rows of a boundary sub-tile of the smoother: image of 2 + 2K <= 8 rows, one per wave
+// ... of a six-sweep launch without the fused restriction: 4.  Its image of TB + 12 rows takes two rows per wave either way (14
+// rows fill 16 slots as badly as 16 do), so four-row sub-tiles are half as many workgroups of the same length.
+__host__ __device__ constexpr int f32_tb(int K, int RR) { return (K == 6 && !RR) ? 4 : F32_TB; }
 
 __device__ __forceinline__ float lane_shr1f(float x) {  // the value of lane - 1 (lane 0 keeps its own)
   int v = __float_as_int(x);
@@ -379,7 +392,7 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
 // (every other vertex takes the uniform constants) - is loaded once, all loads in flight together, and stays in registers for the
 // K sweeps; the mirrored D links come from the neighbours (out-of-grid entries are loaded as 0, and a link that leaves the grid is
 // stored as 0, so no per-link test is left); the 2x2 vertex block is inverted once per launch.  With TB = 2 an image has
-// 2 + 2K <= 8 rows: one row per wave.
+// 2 + 2K <= 8 rows: one row per wave (K <= 3); six sweeps take two rows per wave, and TB = 4 (f32_tb).
 template <class DT, int TY, int TB, int K, bool FIRST, int IO, int CADD, int RR>
 __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2* img0, float2* img1, float2* exch) {
   constexpr int W = 64, HALO = K + (RR ? 2 : 0), TX = W - 2 * HALO, H0 = TB + 2 * HALO, NSUB = TY / TB, NW = F32_BLOCK / 64,
@@ -560,16 +573,20 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
 #undef F_ROWS_G
 }
 
-// ONE launch per smoother call: blocks [0, nbnd) are the boundary sub-tiles - they start first, so their long dependent-load
-// chains overlap with the interior tiles that follow - blocks [nbnd, nbnd + nfast) the interior tiles.
-template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR>
+// ONE launch per smoother call (PART = 0): blocks [0, nbnd) are the boundary sub-tiles - they start first, so their long
+// dependent-load chains overlap with the interior tiles that follow - blocks [nbnd, nbnd + nfast) the interior tiles.  PART = 1 /
+// 2: the interior tiles / the boundary sub-tiles alone (F32_K6_SPLIT); both read the old iterate and write disjoint vertices of
+// the new one, so the order of the two launches is free.
+template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR, int PART = 0>
 __global__ void __launch_bounds__(F32_BLOCK, RR ? 2 : F32_WAVES_EU) k_f_smooth(const FSmoothArgs A) {
-  constexpr int W = 64, H0 = TY + 2 * (K + (RR ? 2 : 0)), PAD = W + 1;
+  constexpr int W = 64, H0 = (PART == 2 ? f32_tb(K, RR) : TY) + 2 * (K + (RR ? 2 : 0)), PAD = W + 1;
   __shared__ float2 img_[3][H0 * W + 2 * PAD];  // guard bands: inactive edge lanes read (and discard) one entry outside a row;
                                                  // [2]: the (D(0,+1), D(+1,+1)) links every image row hands to the row above it
   const int blk = blockIdx.x;
-  if (blk < A.nbnd)
-    f_smooth_bnd<DT, TY, F32_TB, K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+  if (PART == 2 || (PART == 0 && blk < A.nbnd))
+    f_smooth_bnd<DT, TY, f32_tb(K, RR), K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+  else if (PART == 1)
+    f_smooth_fast<DT, TY, K, FIRST, IO, CADD, RR>(xcd_block(blk, gridDim.x, A.remap), A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
   else
     f_smooth_fast<DT, TY, K, FIRST, IO, CADD, RR>(xcd_block(blk - A.nbnd, gridDim.x - A.nbnd, A.remap), A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
 }
@@ -616,36 +633,46 @@ static void launch_f_smooth_rr(hipStream_t st, int first, FSmoothArgs& A, int fa
     launch_f_smooth_rr_t<float4, TY, K>(st, first, A, fast_ok);
 }
 
+template <class DT, int TY, int K, bool FIRST, int IO, int CADD>
+static void launch_f_smooth_k(hipStream_t st, const FSmoothArgs& A, int nfast) {
+  const dim3 block(F32_BLOCK);
+  if constexpr (F32_K6_SPLIT && K == 6 && TY >= 12) {
+    if (A.nbnd) hipLaunchKernelGGL((k_f_smooth<DT, TY, K, FIRST, IO, CADD, 0, 2>), dim3(A.nbnd), block, 0, st, A);
+    if (nfast) hipLaunchKernelGGL((k_f_smooth<DT, TY, K, FIRST, IO, CADD, 0, 1>), dim3(nfast), block, 0, st, A);
+  } else {
+    hipLaunchKernelGGL((k_f_smooth<DT, TY, K, FIRST, IO, CADD, 0>), dim3(A.nbnd + nfast), block, 0, st, A);
+  }
+}
+
 template <class DT, int TY, int K>
 static void launch_f_smooth_t(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
   A.g = rowmap_grid<TY, K>(A.nx, A.ny, fast_ok);
   const int nfast = A.g.nfx * A.g.nfy;
-  A.nbnd = (A.g.ntx * A.g.nty - nfast) * (TY / F32_TB);  // boundary tiles: sub-tiles of F32_TB rows
-  const dim3 grid(A.nbnd + nfast), block(F32_BLOCK);
+  A.nbnd = (A.g.ntx * A.g.nty - nfast) * (TY / f32_tb(K, 0));  // boundary tiles: sub-tiles of f32_tb rows
   if (first) {
     if (A.b32u)
-      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 3, 0, 0>), grid, block, 0, st, A);
+      launch_f_smooth_k<DT, TY, K, true, 3, 0>(st, A, nfast);
     else if (A.b64u)
-      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 1, 0, 0>), grid, block, 0, st, A);
+      launch_f_smooth_k<DT, TY, K, true, 1, 0>(st, A, nfast);
     else
-      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, true, 0, 0, 0>), grid, block, 0, st, A);
+      launch_f_smooth_k<DT, TY, K, true, 0, 0>(st, A, nfast);
     return;
   }
   const int cadd = A.cf ? 1 : (A.cdu ? 2 : 0);
   if (A.y64u) {
     if (cadd == 0)
-      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 2, 0, 0>), grid, block, 0, st, A);
+      launch_f_smooth_k<DT, TY, K, false, 2, 0>(st, A, nfast);
     else if (cadd == 1)
-      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 2, 1, 0>), grid, block, 0, st, A);
+      launch_f_smooth_k<DT, TY, K, false, 2, 1>(st, A, nfast);
     else
-      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 2, 2, 0>), grid, block, 0, st, A);
+      launch_f_smooth_k<DT, TY, K, false, 2, 2>(st, A, nfast);
   } else {
     if (cadd == 0)
-      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 0, 0, 0>), grid, block, 0, st, A);
+      launch_f_smooth_k<DT, TY, K, false, 0, 0>(st, A, nfast);
     else if (cadd == 1)
-      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 0, 1, 0>), grid, block, 0, st, A);
+      launch_f_smooth_k<DT, TY, K, false, 0, 1>(st, A, nfast);
     else
-      hipLaunchKernelGGL((k_f_smooth<DT, TY, K, false, 0, 2, 0>), grid, block, 0, st, A);
+      launch_f_smooth_k<DT, TY, K, false, 0, 2>(st, A, nfast);
   }
 }
 
@@ -657,10 +684,19 @@ static void launch_f_smooth(hipStream_t st, int first, FSmoothArgs& A, int fast_
     launch_f_smooth_t<float4, TY, K>(st, first, A, fast_ok);
 }
 
-static int f32_tile_rows(const GridLevel& L) {
+// Tile rows of a launch of K sweeps.  PGX_F32_TY: 4, 8, 16 for every K; 12 and 20 exist for the six-sweep launches only (images of
+// 24 and 32 rows: three and four per wave) - other launches take the next height below, and a six-sweep image needs TY >= 8.
+static int f32_tile_rows(const GridLevel& L, int K) {
   static PgxTuneInt t_ty("PGX_F32_TY", 0);
   const int ty = t_ty.get();
+  if (K == 6) {
+    if (ty == 8 || ty == 12 || ty == 16 || ty == 20) return ty;
+    if (ty == 4) return 8;
+    return L.n <= 300000 ? 8 : F32_K6_TY_TOP;  // 513^2 and below: launch-latency bound, 8 rows = most workgroups
+  }
   if (ty == 4 || ty == 8 || ty == 16) return ty;
+  if (ty == 12) return 8;
+  if (ty == 20) return 16;
   return L.n >= 2000000 ? 16 : L.n >= 500000 ? 8 : 4;  // as k_st_smoothR (measured there per level size)
 }
 
@@ -701,12 +737,18 @@ void pgxk_f_smooth(hipStream_t st, int K, int first, const GridLevel& L, double 
   A.alpha = (float)alpha;
   A.omega = (float)omega;
   A.sc = make_fconst(L, alpha);
-  const int ty = f32_tile_rows(L);
-  if (K == 6) {  // small levels (launch-latency bound): a whole leg of six sweeps in ONE launch
+  const int ty = f32_tile_rows(L, K);
+  if (K == 6) {  // a whole leg of six sweeps in ONE launch
     if (cbf || cb64u)
       launch_f_smooth_rr<16, 6>(st, first, A, L.interior_free && (!C || C->interior_free));
-    else
+    else if (ty == 8)
       launch_f_smooth<8, 6>(st, first, A, L.interior_free);
+    else if (ty == 12)
+      launch_f_smooth<12, 6>(st, first, A, L.interior_free);
+    else if (ty == 16)
+      launch_f_smooth<16, 6>(st, first, A, L.interior_free);
+    else
+      launch_f_smooth<20, 6>(st, first, A, L.interior_free);
     return;
   }
   if (cbf || cb64u) {
