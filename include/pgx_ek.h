@@ -1,0 +1,93 @@
+/*
+ * pgx_ek.h - C ABI of example 09 inside libpgx.so: the eikonal equation on a Moebius strip, a surface PDE on quadrilaterals embedded
+ * in R^3, i.e. everything below `problem.solve()` in the reference's examples/09_eikonal/eikonal_dolfinx.py plus the vector copy and
+ * the norm of its outer loop (:149-174) and its DG outputs (:84-86, :134-148, :167-170), kept on the device.
+ *
+ *   u in Q1, psi in [Q2]^3 - three AMBIENT Cartesian components, not tangential -, both continuous (:29-32).  Unknowns
+ *   x = [u | psi0 | psi1 | psi2], rows [v | tau0 | tau1 | tau2]; no Dirichlet rows (bcs=[], :78-80).  With psi_prev the psi block of the
+ *   previous LVPP iterate (set_prev / advance_prev, :49-50, :163) the residual is (:52-58)
+ *       R_v   = (div_G psi - div_G psi_prev, v) + alpha (f, v)
+ *       R_tau = (u, div_G tau) + phi (psi / sqrt(1 + |psi|^2), tau)
+ *   and the Jacobian the true derivative (:61), symmetric as assembled: [[0, B], [B^T, D(psi)]], D_ij = the mass form weighted by
+ *   phi (delta_ij / s - psi_i psi_j / s^3), s = sqrt(1 + |psi|^2).  The (u, u) block is structurally zero: NO entry is stored there
+ *   (pgx_dn_create asks for no diagonal).
+ *
+ * Surface operators (UFL's on a manifold): the cell map x(X) is the Q_g interpolant of the cell's (g+1)^2 geometry nodes, g in
+ * {1, 2, 3}; J = dx/dX (3 x 2), G = J^T J, K = G^-1 J^T (the pseudo-inverse), dS = sqrt(det G), grad_G N = (dN/dX) K,
+ * div_G psi = sum_i (grad_G psi_i)_i.  Every term is integrated with the caller's 1-D Gauss rule in tensor form (nq points per
+ * direction, <= 11); DOLFINx's automatic degree is not reproduced.
+ *
+ * Numbering is the caller's (proximalgalerkin_amd.lagrange.numbering_mobius: the seam joins the last column of cells to the first one
+ * upside down); a cell's local nodes run over its (k+1) x (k+1) sub-lattice, first reference direction fastest, and the basis is the
+ * product of the 1-D Lagrange bases on the nodes i / k.  A mesh in which a cell holds one dof twice or two cells share more than two
+ * vertices (fewer than 3 cells around the strip) is refused with PGX_EINVAL.
+ *
+ *   pgx_ek_create            NonlinearProblem(F, u=w, bcs=[], J=J, petsc_options=sp) (:78-80) with the mesh (:27), the spaces (:29-32),
+ *                            f (:44) and phi (:48)
+ *   pgx_ek_set/get_state     w.x.array;  pgx_ek_set/get_prev  w0.x.array;  pgx_ek_advance_prev  w0.x.array[:] = w.x.array (:163)
+ *   pgx_ek_set_alpha         alpha.value = min(2**i, 10) (:152)
+ *   pgx_ek_residual / pgx_ek_jacobian_fill / pgx_ek_csr_export / pgx_ek_spmv   the SNES callbacks and the PETSc Mat (:52-61)
+ *   pgx_ek_newton_solve      problem.solve() (:154): opts->linesearch 2 = l2 (:67), 1 / 3 = bt, every other value: full steps; reason =
+ *                            getConvergedReason (:156), its = getIterationNumber (:155).  ksp preonly + pc lu + MUMPS (:72-76) is the
+ *                            dense LU with partial pivoting of include/pgx_dn.h plus iterative refinement on the exact operator: the
+ *                            zero (u, u) block makes node-block elimination without pivoting (pgx_nd.h) unsafe (element growth 1e7
+ *                            at 944 unknowns).  More than PGX_DN_MAX_N unknowns are refused at create, the message naming the size.
+ *   pgx_ek_l2_increment_u    sqrt(assemble_scalar((u - u0)^2 dx)) (:88-90, :160-161), a fixed-shape two-stage reduction
+ *   pgx_ek_eval_cells        per cell and Q_g interpolation node: u (:84-86, :167), grad_G u (:134-139, :169), psi (:141-142, :170)
+ *   pgx_ek_lu_stats          the pgx_dn_stats of the handle's dense LU (of the last factorisation)
+ *   pgx_ek_profile           device-event times of the phases
+ *
+ * Plain pointers and sizes only.  Returns 0 or a negative PGX_E* code (include/pgx.h); text via pgx_ek_last_error.  No CPU fallback.
+ */
+#ifndef PGX_EK_H
+#define PGX_EK_H
+#include <stdint.h>
+
+#include "pgx.h"
+#include "pgx_dn.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct pgx_ek_handle pgx_ek_handle;
+
+typedef struct {
+  int32_t nc;                 /* cells */
+  int32_t geo_order;          /* g in {1, 2, 3} (the script's mesh: 3) */
+  const double* cell_nodes;   /* [nc][(g+1)^2][3] geometry nodes of every cell, sampled at the cell's own parameters */
+  int32_t n1, n2;             /* dofs of the Q1 and of the Q2 space */
+  const int32_t* cell_dofs_u; /* [nc][4] */
+  const int32_t* cell_dofs_p; /* [nc][9] */
+  int32_t nq;                 /* points of the 1-D Gauss rule (1..11) */
+  const double* qpts;         /* [nq] on [0, 1] */
+  const double* qwts;         /* [nq], sum 1 */
+  double f, phi;              /* :44, :48 */
+} pgx_ek_problem;
+
+int pgx_ek_create(const pgx_ek_problem* p, int device, pgx_ek_handle** out);
+void pgx_ek_destroy(pgx_ek_handle* h);
+const char* pgx_ek_last_error(const pgx_ek_handle* h);
+int pgx_ek_num_dofs(const pgx_ek_handle* h, int64_t* ntot); /* n1 + 3 n2 */
+int pgx_ek_set_state(pgx_ek_handle* h, const double* x);
+int pgx_ek_get_state(pgx_ek_handle* h, double* x);
+int pgx_ek_set_prev(pgx_ek_handle* h, const double* x);
+int pgx_ek_get_prev(pgx_ek_handle* h, double* x);
+int pgx_ek_advance_prev(pgx_ek_handle* h);
+int pgx_ek_set_alpha(pgx_ek_handle* h, double alpha);
+/* F(x) (host arrays; x NULL: the state), fnorm may be NULL */
+int pgx_ek_residual(pgx_ek_handle* h, const double* x, double* F, double* fnorm);
+int pgx_ek_jacobian_fill(pgx_ek_handle* h, const double* x);
+int pgx_ek_csr_export(pgx_ek_handle* h, int64_t* nrows, int64_t* nnz, int32_t* rowptr, int32_t* col, double* vals);
+int pgx_ek_spmv(pgx_ek_handle* h, const double* x, double* y);
+int pgx_ek_newton_solve(pgx_ek_handle* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its);
+int pgx_ek_l2_increment_u(pgx_ek_handle* h, double* out);
+/* out [nc][(g+1)^2][7] (host): u, grad_G u (3), psi (3) at the Q_g interpolation nodes of every cell */
+int pgx_ek_eval_cells(pgx_ek_handle* h, double* out);
+int pgx_ek_lu_stats(const pgx_ek_handle* h, pgx_dn_stats* st);
+/* device-event ms: [0] residual [1] Jacobian fill [2] factorisation [3] solves [4] spmv [5] Newton total */
+int pgx_ek_profile(pgx_ek_handle* h, int enable, double ms[6]);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

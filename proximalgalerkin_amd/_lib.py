@@ -284,6 +284,21 @@ class pgx_ma_problem(C.Structure):  # include/pgx_ma.h
     ]
 
 
+class pgx_ek_problem(C.Structure):  # include/pgx_ek.h
+    _fields_ = [
+        ("nc", C.c_int32),
+        ("geo_order", C.c_int32),
+        ("cell_nodes", c_double_p),
+        ("n1", C.c_int32), ("n2", C.c_int32),
+        ("cell_dofs_u", c_int32_p),
+        ("cell_dofs_p", c_int32_p),
+        ("nq", C.c_int32),
+        ("qpts", c_double_p),
+        ("qwts", c_double_p),
+        ("f", C.c_double), ("phi", C.c_double),
+    ]
+
+
 class pgx_partition(C.Structure):
     _fields_ = [
         ("rank", C.c_int32),
@@ -456,8 +471,14 @@ SYMBOLS = [
     ("pgx_ma_l2_error", C.c_int, [_H, c_double_p, c_double_p]),
     ("pgx_ma_lu_stats", C.c_int, [_H, C.POINTER(pgx_dn_stats)]),
     ("pgx_ma_profile", C.c_int, [_H, C.c_int, c_double_p]),
+    # example 09: the eikonal equation on a Moebius strip, on the dense pivoting LU (include/pgx_ek.h)
+    ("pgx_ek_create", C.c_int, [C.POINTER(pgx_ek_problem), C.c_int, C.POINTER(_H)]),
+    ("pgx_ek_num_dofs", C.c_int, [_H, c_int64_p]),
+    ("pgx_ek_l2_increment_u", C.c_int, [_H, c_double_p]),
+    ("pgx_ek_eval_cells", C.c_int, [_H, c_double_p]),
+    ("pgx_ek_lu_stats", C.c_int, [_H, C.POINTER(pgx_dn_stats)]),
 ]
-# the entry points the seven mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
+# the entry points the eight mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
 _MIXED_COMMON = [
     ("destroy", None, [_H]),
     ("last_error", C.c_char_p, [_H]),
@@ -474,7 +495,7 @@ _MIXED_COMMON = [
     ("newton_solve", C.c_int, [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("profile", C.c_int, [_H, C.c_int, c_double_p]),
 ]
-SYMBOLS += [(f"{prefix}_{suffix}", res, args) for prefix in ("pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic", "pgx_mp", "pgx_fr", "pgx_ev") for suffix, res, args in _MIXED_COMMON]
+SYMBOLS += [(f"{prefix}_{suffix}", res, args) for prefix in ("pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic", "pgx_mp", "pgx_fr", "pgx_ev", "pgx_ek") for suffix, res, args in _MIXED_COMMON]
 
 _lib = None
 _forwarded: dict = {}

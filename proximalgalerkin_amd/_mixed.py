@@ -1,5 +1,5 @@
 """The handle layer the mixed-matrix families share: examples 06 (`pgx_gc_*`), 02 (`pgx_sg_*`), 05 (`pgx_qvi_*`),
-08 (`pgx_ic_*`), 04 (`pgx_mp_*`), 03 (`pgx_fr_*`), 07 (`pgx_ev_*`) and 10 (`pgx_ma_*`, which has no previous iterate and no alpha).  Each family exports the same entry points under its own prefix, all of them forwards to the shared driver
+08 (`pgx_ic_*`), 04 (`pgx_mp_*`), 03 (`pgx_fr_*`), 07 (`pgx_ev_*`), 09 (`pgx_ek_*`) and 10 (`pgx_ma_*`, which has no previous iterate and no alpha).  Each family exports the same entry points under its own prefix, all of them forwards to the shared driver
 (csrc/pgx_mixed.hip).  A subclass names its prefix in `_prefix`; its constructor creates `self._h` and sets `_lib`, `_opts`,
 `solver` and `ndofs` (and `_flags` where its options take `snes_error_if_not_converged`).
 """
@@ -18,7 +18,7 @@ def _vec(x):
 
 
 class _MixedHandle:
-    _prefix = ""  # "pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic", "pgx_mp", "pgx_fr" or "pgx_ev"
+    _prefix = ""  # "pgx_gc", "pgx_sg", "pgx_qvi", "pgx_ic", "pgx_mp", "pgx_fr", "pgx_ev" or "pgx_ek"
     _flags: dict = {}  # {"snes_error_if_not_converged": bool}: solve() raises ConvergenceError only where it is set
     alpha = 1.0  # the value last given to set_alpha (the library's initial value)
 

@@ -66,7 +66,7 @@ struct MixedBase {
   virtual void jacobian_dev(const double* xin) = 0;                // fills Jv at x
   // The linear-solve hook of the Newton drivers: factorise Jv, solve with the factorisation (device pointers, on st), the solver's error
   // text, and its release before the stream goes.  Default (pgx_mixed.hip): the sparse LU `lu` (pgx_nd) through the row flip
-  // lu_flip_from.  pgx_ma overrides it with the dense LU with partial pivoting (pgx_dn): its Newton matrix is not quasi-definite.
+  // lu_flip_from.  pgx_ma and pgx_ek override it with the dense LU with partial pivoting (pgx_dn): their Newton matrices are not quasi-definite.
   virtual int lin_factor();
   virtual int lin_solve(const double* rhs, double* out);
   virtual const char* lin_error() const;

@@ -199,3 +199,24 @@ def exterior_dofs_quad(mesh, k: int) -> np.ndarray:
     ix = np.tile(np.arange(Lx), Ly)
     iy = np.repeat(np.arange(Ly), Lx)
     return np.flatnonzero((ix == 0) | (ix == Lx - 1) | (iy == 0) | (iy == Ly - 1)).astype(np.int32)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# the Moebius strip of example 09 (mesh_generation.create_mobius_strip): Q_k on nu x nv quadrilaterals whose last column of cells is
+# glued to the first one upside down.  The dofs are the points of the k-times refined lattice with columns I = 0 .. k nu - 1 and rows
+# J = 0 .. k nv, dof J (k nu) + I; column k nu IS column 0 with J -> k nv - J (the non-orientable seam).  A cell's local nodes run over
+# its (k+1) x (k+1) sub-lattice as in `numbering_quad`.
+# ----------------------------------------------------------------------------------------------------------------------------------
+def numbering_mobius(nu: int, nv: int, k: int):
+    """-> (n_dofs, cell_dofs (nu nv, (k+1)^2) int32) of Q_k on the nu x nv Moebius strip, cell cy nu + cx.  nu >= 3: with fewer cells
+    around, a cell would meet itself or one neighbour twice."""
+    nu, nv, k = int(nu), int(nv), int(k)
+    if nu < 3 or nv < 1 or k < 1:
+        raise ValueError("numbering_mobius: nu >= 3, nv >= 1 and degree >= 1 are required")
+    Lu = k * nu
+    cx, cy = np.tile(np.arange(nu), nv), np.repeat(np.arange(nv), nu)
+    a, b = np.tile(np.arange(k + 1), k + 1), np.repeat(np.arange(k + 1), k + 1)
+    I, J = k * cx[:, None] + a[None, :], k * cy[:, None] + b[None, :]
+    seam = I == Lu
+    I, J = np.where(seam, 0, I), np.where(seam, k * nv - J, J)
+    return Lu * (k * nv + 1), np.ascontiguousarray(J * Lu + I, dtype=np.int32)

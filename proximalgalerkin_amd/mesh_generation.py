@@ -14,7 +14,48 @@ import numpy as np
 from . import fem
 from .signorini import MeshTags, TetMesh
 
-__all__ = ["create_half_disk", "create_half_sphere", "create_crack_mesh", "CRACK_BOUNDARIES"]
+__all__ = ["create_half_disk", "create_half_sphere", "create_crack_mesh", "CRACK_BOUNDARIES", "create_mobius_strip", "MobiusMesh"]
+
+
+class MobiusMesh:
+    """nu x nv quadrilaterals of geometry order `order` embedded in R^3, the last column of cells glued to the first one upside down.
+    `cell_nodes` (nc, (order+1)^2, 3): the geometry nodes of cell cy nu + cx, local node b (order+1) + a, each cell sampled at its own
+    unwrapped parameters.  The dof numberings on it come from `lagrange.numbering_mobius`."""
+
+    def __init__(self, nu, nv, order, scale, cell_nodes):
+        self.nu, self.nv, self.order, self.scale = int(nu), int(nv), int(order), float(scale)
+        self.cell_nodes = np.ascontiguousarray(cell_nodes, dtype=np.float64)
+        self.num_cells = self.nu * self.nv
+
+    def cell_name(self):
+        return "quadrilateral"
+
+
+def mobius_map(s, t, scale=1.0):
+    """x(s, t) = scale ((1 + rho cos(s / 2)) cos s, (1 + rho cos(s / 2)) sin s, rho sin(s / 2)), rho = (t - 1/2) / 2: the strip of
+    half-width scale / 4 around the circle of radius scale, s in [0, 2 pi], t in [0, 1]; (s + 2 pi, t) and (s, 1 - t) are one point."""
+    rho = 0.5 * (np.asarray(t, dtype=np.float64) - 0.5)
+    a = 1.0 + rho * np.cos(0.5 * s)
+    return scale * np.stack([a * np.cos(s), a * np.sin(s), rho * np.sin(0.5 * s)], axis=-1)
+
+
+def create_mobius_strip(nu: int, nv: int, order: int = 3, scale: float = 1.0) -> MobiusMesh:
+    """The Moebius strip of example 09 meshed natively: the parameter cells [2 pi cx / nu, 2 pi (cx + 1) / nu] x [cy / nv, (cy + 1) / nv]
+    mapped by `mobius_map`, every cell's (order+1)^2 equispaced geometry nodes sampled at its own unwrapped parameters (the nodes two
+    cells share across the seam are one point of R^3 reached through two parameter pairs).  The reference reads a mesh written by MFEM
+    (examples/09_eikonal/eikonal_dolfinx.py:27); this parametrisation is the package's own."""
+    nu, nv, order = int(nu), int(nv), int(order)
+    if nu < 3 or nv < 1:
+        raise ValueError("create_mobius_strip: nu >= 3 (no cell may meet itself or one neighbour twice) and nv >= 1")
+    if order not in (1, 2, 3):
+        raise ValueError("create_mobius_strip: geometry order 1, 2 or 3")
+    if not (scale > 0.0) or not np.isfinite(scale):
+        raise ValueError("create_mobius_strip: scale must be positive")
+    cx, cy = np.tile(np.arange(nu), nv), np.repeat(np.arange(nv), nu)
+    lat = np.arange(order + 1) / order
+    S = 2.0 * np.pi * (cx[:, None] + np.tile(lat, order + 1)[None, :]) / nu
+    T = (cy[:, None] + np.repeat(lat, order + 1)[None, :]) / nv
+    return MobiusMesh(nu, nv, order, scale, mobius_map(S, T, float(scale)))
 
 
 def _ball_map(p):
