@@ -219,6 +219,7 @@ struct FSmoothArgs {
   double bscale;  // IO == 1: the fp64 right-hand side is multiplied by this as it is read (lazily normalised Krylov vectors)
   FConst sc;
   const float *b32u, *b32p;  // IO == 3 (behind sc: the offsets the other instantiations read their arguments at stay put)
+  int bfull;  // the nbnd boundary blocks are whole tiles (f_smooth_bnd_full), not sub-tiles
 };
 
 // the right-hand side at vertex v as the launch's IO reads it
@@ -573,7 +574,251 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
 #undef F_ROWS_G
 }
 
-// ONE launch per smoother call (PART = 0): blocks [0, nbnd) are the boundary sub-tiles - they start first, so their long
+// Boundary tiles at the FULL tile height (FSmoothArgs::bfull: six-sweep launches, with or without the fused restriction, on a level
+// with uniform stencils and no Dirichlet dof inside the grid): ONE workgroup per boundary tile with the interior tiles' image of
+// TY + 2K rows and their rows per wave, instead of TY / 4 sub-tile workgroups that each sweep 16 image rows for 4.  Every in-grid
+// vertex is updated by the interior tiles' pair-summed formula on scalar K / M; only the vertices of the grid's frame (gi in
+// {0, nx}, gj in {0, ny}) have rows of their own, and those do NOT live in per-lane registers (R x 14 of them is what the sub-tile
+// path pays): the alpha K / M rows of the image's frame vertices - at most two image rows and two image columns - are loaded with
+// the launch's first batch, one or two values per thread, and staged in the third image, whose D links move to the second one,
+// free until the first sweep writes it.  A frame vertex's row is then redone from LDS by the seven-slot formula of f_smooth_bnd:
+// a frame row in a wave-uniform branch, a frame column in the one lane that holds it.  Out-of-grid entries and their D links are
+// exact zeros, Dirichlet u reads as 0 and is solved exactly, as in f_smooth_bnd.
+template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR>
+__device__ __forceinline__ void f_smooth_bnd_full(int b, const FSmoothArgs& A, float2* img0, float2* img1, float2* exch) {
+  constexpr int W = 64, HALO = K + (RR ? 2 : 0), TX = W - 2 * HALO, H0 = TY + 2 * HALO, NW = F32_BLOCK / 64, R = (H0 + NW - 1) / NW;
+  // staged rows: slot s holds (aK[0..6], M[0..6]) as seven float2; slots [0, 2W): the frame rows gj = 0 and gj = ny by lane,
+  // [2W, 2W + 2 H0): the frame columns gi = 0 and gi = nx by image row
+  static_assert(7 * (2 * W + 2 * H0) <= H0 * W, "the frame rows' coefficients must fit into the third image");
+  static_assert(14 * H0 <= F32_BLOCK && 14 <= 2 * NW, "one value of a frame column, two of a frame row per thread");
+  const int nx = A.nx, ny = A.ny, sx = nx + 1;
+  const RowmapGrid& g = A.g;
+  int tx, ty;
+  const int side = g.ntx - g.nfx;  // boundary tiles in a row that also holds fast tiles
+  if (b < g.ntx) {
+    tx = b;
+    ty = 0;
+  } else if ((b -= g.ntx) < g.nfy * side) {
+    ty = 1 + b / side;
+    const int r = b % side;
+    tx = r == 0 ? 0 : g.nfx + r;
+  } else {
+    b -= g.nfy * side;
+    ty = g.nfy + 1 + b / g.ntx;
+    tx = b % g.ntx;
+  }
+  const int i0 = tx * TX - HALO, j0 = ty * TY - HALO;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int gi = i0 + lane;
+  const bool own_lane = lane >= HALO && lane < W - HALO;
+  const bool in_x = gi >= 0 && gi <= nx;
+  const DT* const Dq = static_cast<const DT*>(A.Dq);
+  float* const cst = reinterpret_cast<float*>(exch);
+  DT dw[R];
+  float4 dq[R];
+  float2 rb[R], xa[R];
+  bool in[R], bc[R], fr[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    const int lj = wave + NW * k, gj = j0 + lj;
+    in[k] = lj < H0 && in_x && gj >= 0 && gj <= ny;
+    fr[k] = in[k] && (gi == 0 || gi == nx || gj == 0 || gj == ny);
+    bc[k] = false;
+    f_zero_d(dw[k]);
+    rb[k] = xa[k] = make_float2(0.f, 0.f);
+    if (in[k]) {
+      const int v = gj * sx + gi;
+      dw[k] = Dq[v];
+      bc[k] = A.mask[v] != 0;
+      if (lj >= 1 && lj < H0 - 1) rb[k] = f_load_rhs<IO>(A, (unsigned)v);
+      if (!FIRST) xa[k] = f_add_coarse<CADD>(A.xf[v], gi, gj, A.nxc, A.cf, A.cdu, A.cdp);
+    }
+  }
+  // the frame vertices' rows, in flight with the batch above: value t of a row is aK[t] (t < 7) or M[t - 7]
+  double cv[6];
+  int cq[6];  // where the value goes (in floats; -1: none)
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int gj = r ? ny : 0;
+    const bool has = gj >= j0 && gj < j0 + H0 && in_x;  // (ny >= 2: the two rows are different ones)
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const int t = wave + NW * hh, e = 2 * r + hh;
+      cq[e] = -1;
+      cv[e] = 0.0;
+      if (has && t < 14) {
+        cv[e] = (t < 7 ? A.K + (size_t)t * A.n : A.M + (size_t)(t - 7) * A.n)[(size_t)gj * sx + gi];
+        cq[e] = 14 * (r * W + lane) + t;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int gic = c ? nx : 0, lj = (int)threadIdx.x / 14, t = (int)threadIdx.x % 14, gj = j0 + lj, e = 4 + c;
+    cq[e] = -1;
+    cv[e] = 0.0;
+    if (gic >= i0 && gic < i0 + W && lj < H0 && gj >= 0 && gj <= ny) {
+      cv[e] = (t < 7 ? A.K + (size_t)t * A.n : A.M + (size_t)(t - 7) * A.n)[(size_t)gj * sx + gic];
+      cq[e] = 14 * (2 * W + c * H0 + lj) + t;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    const int lj = wave + NW * k;
+    dq[k] = f_unpack_d(dw[k]);
+    if (lj < H0) {
+      if (!FIRST) img0[lj * W + lane] = make_float2(bc[k] ? 0.f : xa[k].x, xa[k].y);  // pre-masked: Dirichlet u reads as 0
+      img1[lj * W + lane] = make_float2(dq[k].z, dq[k].w);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 6; ++e)
+    if (cq[e] >= 0) cst[cq[e]] = cq[e] % 14 < 7 ? A.alpha * (float)cv[e] : (float)cv[e];
+  __syncthreads();
+  // the staged row of image vertex (lj, lane), a frame vertex: a frame row takes precedence over a frame column (corners)
+#define F_FRAME_ROW(lj) \
+  (exch + 7 * ((j0 + (lj) == 0 || j0 + (lj) == ny) ? (j0 + (lj) == 0 ? 0 : W) + lane : 2 * W + (gi == 0 ? 0 : H0) + (lj)))
+  float d2[R], d4[R], d6[R], g0[R], g1[R], g3[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    const int lj = wave + NW * k;
+    d2[k] = d4[k] = d6[k] = g0[k] = g1[k] = g3[k] = 0.f;
+    if (lj >= 1 && lj < H0 - 1) {
+      d2[k] = lane_shr1f(dq[k].y);
+      d4[k] = img1[(lj - 1) * W + lane].x;
+      d6[k] = img1[(lj - 1) * W + lane - 1].y;
+      // damped inverse of the vertex block, once per launch (f_jacobi: a Dirichlet row of u is solved exactly).  The psi row's
+      // factor of su is g1 in either case: omega (-M0 / det) on a free row, 0 on a Dirichlet one
+      float a = A.sc.kc[0], bm = A.sc.mc[0], om_u = A.omega;
+      if (fr[k]) {
+        const float2* const cf = F_FRAME_ROW(lj);
+        a = cf[0].x;
+        bm = cf[3].y;
+      }
+      if (bc[k]) {
+        a = 1.f;
+        bm = 0.f;
+        om_u = 1.f;
+      }
+      const float det = -a * dq[k].x - bm * bm;
+      if (det != 0.f) {
+        const float r = __builtin_amdgcn_rcpf(det);
+        g0[k] = om_u * (-dq[k].x * r);
+        g1[k] = om_u * (-bm * r);
+        g3[k] = A.omega * (a * r);
+      } else if (bc[k]) {
+        g0[k] = 1.f;
+      }
+    }
+  }
+  __syncthreads();  // every wave has taken its D links: the first sweep may write the second image
+  const float k0 = A.sc.k0, k1 = A.sc.k1, k3 = A.sc.k3, k5 = A.sc.k5, m0 = A.sc.m0, m1 = A.sc.m1, m3 = A.sc.m3, m5 = A.sc.m5;
+  // (au, ap) = the two rows of J at image vertex (lj, lane) of row slot k: the interior tiles' pair-summed formula, redone for a
+  // frame vertex (a frame row: the whole wave; a frame column: one lane, every other wave skips the block) with its staged row -
+  // F_ROWS_G's sums in four stages of two LDS reads: all fourteen coefficients in flight at once are what takes the kernel past 80
+  // VGPRs, and only the frame's lanes wait here
+  auto rows = [&](const float2* src, int lj, int k, float& au, float& ap) -> float2 {
+    const int q = lj * W + lane;
+    const float2 x0 = src[q], x1 = src[q + 1], x2 = src[q - 1], x3 = src[q + W], x4 = src[q - W], x5 = src[q + W + 1],
+                 x6 = src[q - W - 1];
+    const float dp = ((dq[k].x * x0.y + dq[k].y * x1.y) + (d2[k] * x2.y + dq[k].z * x3.y)) +
+                     ((d4[k] * x4.y + dq[k].w * x5.y) + d6[k] * x6.y);
+    const float u12 = x1.x + x2.x, u34 = x3.x + x4.x, u56 = x5.x + x6.x;
+    const float p12 = x1.y + x2.y, p34 = x3.y + x4.y, p56 = x5.y + x6.y;
+    au = (k0 * x0.x + k1 * u12) + (k3 * u34 + k5 * u56) + ((m0 * x0.y + m1 * p12) + (m3 * p34 + m5 * p56));
+    ap = ((m0 * x0.x + m1 * u12) + (m3 * u34 + m5 * u56)) - dp;
+    if (fr[k]) {
+      const float2* const cf = F_FRAME_ROW(lj);
+      float2 ca = cf[0], cb = cf[1];
+      const float ku = (ca.x * x0.x + ca.y * x1.x) + (cb.x * x2.x + cb.y * x3.x);
+      __builtin_amdgcn_sched_barrier(0);
+      ca = cf[2], cb = cf[3];
+      au = ku + ((ca.x * x4.x + ca.y * x5.x) + cb.x * x6.x);
+      const float mv0 = cb.y;
+      __builtin_amdgcn_sched_barrier(0);
+      ca = cf[4], cb = cf[5];
+      const float mp = (mv0 * x0.y + ca.x * x1.y) + (ca.y * x2.y + cb.x * x3.y);
+      const float mu = (mv0 * x0.x + ca.x * x1.x) + (ca.y * x2.x + cb.x * x3.x);
+      const float mv4 = cb.y;
+      __builtin_amdgcn_sched_barrier(0);
+      ca = cf[6];
+      au += mp + ((mv4 * x4.y + ca.x * x5.y) + ca.y * x6.y);
+      ap = (mu + ((mv4 * x4.x + ca.x * x5.x) + ca.y * x6.x)) - dp;
+    }
+    return x0;
+  };
+#pragma unroll
+  for (int s = 1; s <= K; ++s) {
+    const float2* const src = ((s - 1) & 1) ? img1 : img0;
+    float2* const dst = (s & 1) ? img1 : img0;
+    const bool act = lane >= s && lane < W - s;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int lj = wave + NW * k;
+      if (lj < s || lj >= H0 - s) continue;  // wave-uniform
+      float au = 0.f, ap = 0.f, xur = 0.f, xpr = 0.f;
+      if (!FIRST || s > 1) {
+        const float2 x0 = rows(src, lj, k, au, ap);
+        xur = x0.x;
+        xpr = x0.y;
+      }
+      if (bc[k]) au = xur;  // (the image holds 0 there: the row reads u = b_u)
+      const float su = rb[k].x - au, sp = rb[k].y - ap;
+      const float ou = xur + fmaf(g0[k], su, g1[k] * sp);
+      const float op = xpr + fmaf(g1[k], su, g3[k] * sp);
+      if (act) {
+        if (s == K && in[k] && lj >= HALO && lj < H0 - HALO && own_lane) {
+          const int v = (j0 + lj) * sx + gi;
+          if (IO == 1 || IO == 3) A.bfo[v] = rb[k];
+          if (IO == 2) {
+            A.y64u[v] = (double)ou;
+            A.y64p[v] = (double)op;
+          } else {
+            A.yf[v] = make_float2(ou, op);
+          }
+        }
+        if (s < K || RR) dst[lj * W + lane] = in[k] ? make_float2(bc[k] ? 0.f : ou, op) : make_float2(0.f, 0.f);
+      }
+    }
+    if (s < K || RR) __syncthreads();
+  }
+  if (RR) {  // residual of the result and its restriction, as in f_smooth_bnd, for the whole tile
+    const float2* const xk = (K & 1) ? img1 : img0;
+    float2* const rim = (K & 1) ? img0 : img1;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const int lj = wave + NW * k;
+      if (lj < K + 1 || lj >= H0 - K - 1) continue;  // wave-uniform
+      float au, ap;
+      rows(xk, lj, k, au, ap);
+      // a Dirichlet row of u holds u = b_u after any sweep: its residual is 0 (the image keeps 0 there for the neighbours)
+      if (lane >= K + 1 && lane < W - K - 1)
+        rim[lj * W + lane] = in[k] ? make_float2(bc[k] ? 0.f : rb[k].x - au, rb[k].y - ap) : make_float2(0.f, 0.f);
+    }
+    __syncthreads();
+    const int sxc = A.nxc + 1, I0 = (tx * TX) >> 1, J0 = (ty * TY) >> 1;
+    for (int cj = wave; cj < TY / 2; cj += NW)
+      if (lane < TX / 2 && I0 + lane <= A.nxc && J0 + cj <= A.nyc) {
+        const int q = (HALO + 2 * cj) * W + HALO + 2 * lane;
+        const float2 r0 = rim[q], r1 = rim[q + 1], r2 = rim[q - 1], r3 = rim[q + W], r4 = rim[q - W], r5 = rim[q + W + 1],
+                     r6 = rim[q - W - 1];
+        float su = r0.x + 0.5f * (((r1.x + r2.x) + (r3.x + r4.x)) + (r5.x + r6.x));
+        const float sp = r0.y + 0.5f * (((r1.y + r2.y) + (r3.y + r4.y)) + (r5.y + r6.y));
+        const int C = (J0 + cj) * sxc + I0 + lane;
+        if (A.mask_c[C]) su = 0.f;
+        if (RR == 2) {
+          A.cb64u[C] = (double)su;
+          A.cb64p[C] = (double)sp;
+        } else {
+          A.cbf[C] = make_float2(su, sp);
+        }
+      }
+  }
+#undef F_FRAME_ROW
+}
+
+// ONE launch per smoother call (PART = 0): blocks [0, nbnd) are the boundary sub-tiles (A.bfull: whole boundary tiles) - they start first, so their long
 // dependent-load chains overlap with the interior tiles that follow - blocks [nbnd, nbnd + nfast) the interior tiles.  PART = 1 /
 // 2: the interior tiles / the boundary sub-tiles alone (F32_K6_SPLIT); both read the old iterate and write disjoint vertices of
 // the new one, so the order of the two launches is free.
@@ -583,6 +828,12 @@ __global__ void __launch_bounds__(F32_BLOCK, RR ? 2 : F32_WAVES_EU) k_f_smooth(c
   __shared__ float2 img_[3][H0 * W + 2 * PAD];  // guard bands: inactive edge lanes read (and discard) one entry outside a row;
                                                  // [2]: the (D(0,+1), D(+1,+1)) links every image row hands to the row above it
   const int blk = blockIdx.x;
+  if constexpr (PART == 0 && K == 6) {
+    if (A.bfull && blk < A.nbnd) {
+      f_smooth_bnd_full<DT, TY, K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+      return;
+    }
+  }
   if (PART == 2 || (PART == 0 && blk < A.nbnd))
     f_smooth_bnd<DT, TY, f32_tb(K, RR), K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
   else if (PART == 1)
@@ -593,12 +844,14 @@ __global__ void __launch_bounds__(F32_BLOCK, RR ? 2 : F32_WAVES_EU) k_f_smooth(c
 
 // last pre-smoothing launch + residual + restriction (no coarse correction, float2 result); TY >= 8: the first interior tile's
 // image (K + 2 halo rows) must start inside the grid
+static bool f32_bnd_full(int n);
 template <class DT, int TY, int K>
 static void launch_f_smooth_rr_t(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
   const int rr = A.cbf ? 1 : 2;
   A.g = rowmap_grid<TY, K + 2>(A.nx, A.ny, fast_ok);
   const int nfast = A.g.nfx * A.g.nfy;
-  A.nbnd = (A.g.ntx * A.g.nty - nfast) * (TY / F32_TB);
+  A.bfull = K == 6 && fast_ok && A.sc.uniform && f32_bnd_full(A.n);  // whole boundary tiles, as in launch_f_smooth_t
+  A.nbnd = (A.g.ntx * A.g.nty - nfast) * (A.bfull ? 1 : TY / F32_TB);
   const dim3 grid(A.nbnd + nfast), block(F32_BLOCK);
   if (first) {
     if (A.b32u) {
@@ -644,11 +897,23 @@ static void launch_f_smooth_k(hipStream_t st, const FSmoothArgs& A, int nfast) {
   }
 }
 
+// Whole boundary tiles on a level of n vertices?  PGX_F32_BND_FULL (A/B switch: 0 = sub-tiles in every launch) and
+// PGX_F32_BND_FULL_MIN: from 513^2 up.  Below, a launch is one round of workgroups and as long as its longest one: a whole tile
+// (three image rows per wave, the staged frame rows, one more barrier) took 9.7-10.8 us where four-row sub-tiles take 7.4-7.9 us
+// (257^2, 129^2, 65^2 levels of the 2048^2 solve), against 13.5 -> 12.0 us on 513^2.
+static bool f32_bnd_full(int n) {
+  static PgxTuneInt t_full("PGX_F32_BND_FULL", 1), t_min("PGX_F32_BND_FULL_MIN", 100000);
+  return t_full.get() != 0 && n >= t_min.get();
+}
+
 template <class DT, int TY, int K>
 static void launch_f_smooth_t(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
   A.g = rowmap_grid<TY, K>(A.nx, A.ny, fast_ok);
   const int nfast = A.g.nfx * A.g.nfy;
-  A.nbnd = (A.g.ntx * A.g.nty - nfast) * (TY / f32_tb(K, 0));  // boundary tiles: sub-tiles of f32_tb rows
+  // boundary tiles: whole (six sweeps, uniform stencils, no Dirichlet dof inside the grid, a level of 513^2 and more) or cut into
+  // sub-tiles of f32_tb rows
+  A.bfull = !F32_K6_SPLIT && K == 6 && fast_ok && A.sc.uniform && f32_bnd_full(A.n);
+  A.nbnd = (A.g.ntx * A.g.nty - nfast) * (A.bfull ? 1 : TY / f32_tb(K, 0));
   if (first) {
     if (A.b32u)
       launch_f_smooth_k<DT, TY, K, true, 3, 0>(st, A, nfast);
@@ -706,6 +971,7 @@ void pgxk_f_smooth(hipStream_t st, int K, int first, const GridLevel& L, double 
                    const float* b32u, const float* b32p) {
   FSmoothArgs A;
   A.bscale = bscale;
+  A.bfull = 0;
   A.b32u = first ? b32u : nullptr;
   A.b32p = first ? b32p : nullptr;
   A.nyc = C ? C->ny : 0;
