@@ -6,6 +6,7 @@
     proximal Galerkin P1 / P2 (reference: obstacle_pg.solve_problem, `double_exponential`, alpha_max 1e2, tol)   the HIP LVPP path
     first-order bound-constrained method (reference: IPOPT without Hessian)   projected gradient (use_hessian=False)
     VI Newton slot (reference: PETSc vinewtonssls)                 primal-dual active set / semismooth Newton
+    interior-point slot (reference: IPOPT with the exact Hessian)  Mehrotra predictor-corrector, device-resident (include/pgx_ipm.h)
 
     python compare_all.py -N 64            (structured [-1,1]^2 mesh)      python compare_all.py --disk 0.05 | -f mesh.msh
 """
@@ -18,7 +19,8 @@ import numpy as np
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parents[2]))
 from proximalgalerkin_amd import fem, io  # noqa: E402
 from proximalgalerkin_amd.obstacle import solve_problem  # noqa: E402
-from proximalgalerkin_amd.optimization import ObstacleProblem, galahad_solver, setup_problem, vi_newton_solver  # noqa: E402
+from proximalgalerkin_amd.optimization import (ObstacleProblem, galahad_solver, ipopt_solver, setup_problem,  # noqa: E402
+                                               vi_newton_solver)
 
 
 def main():
@@ -28,7 +30,7 @@ def main():
     ap.add_argument("-f", "--infile", "-P", "--path", dest="infile", type=pathlib.Path, default=None,
                     help="gmsh .msh or inline-data .xdmf file (-P / --path: the reference's flag, compare_all.py:24-31)")
     ap.add_argument("-O", "--results", dest="result_dir", type=pathlib.Path, default=None,
-                    help="directory for the solutions of the five solvers as VTU files (the reference writes them with VTXWriter, :32-39)")
+                    help="directory for the solutions of the six solvers as VTU files (the reference writes them with VTXWriter, :32-39)")
     ap.add_argument("--max_iter", type=int, default=500)  # compare_all.py:32
     ap.add_argument("--tol", type=float, default=1e-4)  # compare_all.py:31
     ap.add_argument("--first-order-max-iter", type=int, default=20000)
@@ -48,11 +50,15 @@ def main():
     x_f, it_f = galahad_solver(problem, np.zeros(len(f)), bounds, log_level=0, use_hessian=False, max_iter=a.first_order_max_iter,
                                tol=a.tol, coords=coords)
     u_vi, it_vi = vi_newton_solver(S, M @ f, bounds[0], bounds[1], coords=coords)
+    x_ip = ipopt_solver(problem, np.zeros(len(f)), bounds, log_level=0, max_iter=a.max_iter, tol=a.tol, activate_hessian=True,
+                        method="interior_point", coords=coords)
+    it_ip = problem.total_iteration_count  # where the reference reads IPOPT's count (compare_all.py:100-108)
     n = mesh.num_vertices
     print(f"vertices {n}, smallest |u_PG(P1) - u_VI|_inf = {np.abs(u1.x.array[:n] - u_vi).max():.2e}, |u_TR - u_VI|_inf = {np.abs(x_g - u_vi).max():.2e}")
     if a.result_dir is not None:
         a.result_dir.mkdir(parents=True, exist_ok=True)
-        fields = {"galahad": x_g, "llvp_first_order": u1.x.array[:n], "ipopt_slot_first_order_method": x_f, "snes": u_vi}
+        fields = {"galahad": x_g, "llvp_first_order": u1.x.array[:n], "ipopt_slot_first_order_method": x_f, "snes": u_vi,
+                  "ipopt_slot_interior_point": x_ip}
         for nm, v in fields.items():
             io.write_vtu(a.result_dir / f"{nm}.vtu", mesh.geometry, mesh.cells, {nm: np.asarray(v)[:n]})
         io.write_vtu(a.result_dir / "llvp_second_order_at_vertices.vtu", mesh.geometry, mesh.cells, {"llvp_second_order": u2.x.array[:n]})
@@ -62,6 +68,7 @@ def main():
     print(f"{name} llvp iterations: (P=2) {it_p2}")
     print(f"{name} first-order (projected gradient) iterations: {it_f}")
     print(f"{name} VI semismooth Newton (primal-dual active set) iterations: {it_vi}")
+    print(f"{name} interior point (Mehrotra, GPU LDLᵀ) iterations: {it_ip}")
 
 
 if __name__ == "__main__":

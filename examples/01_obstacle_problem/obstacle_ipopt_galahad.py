@@ -1,6 +1,7 @@
 """The obstacle problem as a bound-constrained minimisation, solved in the Galahad and IPOPT slots on the GPU - counterpart of the
 reference's obstacle_ipopt_galahad.py with its flags (:19-41): -P/--path mesh, --ipopt, --galahad, --max-iter, --tol, --hessian,
--o/--output.  `ObstacleProblem` and `setup_problem` (the reference defines them in this file, :46-127) live in
+-o/--output, plus --interior-point: the IPOPT slot then runs the interior-point method of proximalgalerkin_amd.optimization
+(include/pgx_ipm.h; needs --hessian, like the reference's exact-Hessian branch).  `ObstacleProblem` and `setup_problem` (the reference defines them in this file, :46-127) live in
 proximalgalerkin_amd.optimization and are re-exported here, so `from obstacle_ipopt_galahad import ObstacleProblem, setup_problem`
 (compare_all.py:14) keeps working.
 
@@ -37,6 +38,8 @@ if __name__ == "__main__":
     parser.add_argument("--max-iter", type=int, default=200, help="Maximum number of iterations")
     parser.add_argument("--tol", type=float, default=1e-6, help="Convergence tolerance")
     parser.add_argument("--hessian", dest="use_hessian", action="store_true", default=False, help="Use exact hessian")
+    parser.add_argument("--interior-point", dest="interior_point", action="store_true", default=False,
+                        help="IPOPT slot: the primal-dual interior-point method on the GPU (with --hessian)")
     parser.add_argument("--output", "-o", dest="outdir", type=Path, default=Path("results"), help="Output directory")
     args = parser.parse_args()
     S, M, f, bounds, coords, mesh = setup_problem(args.infile)
@@ -50,6 +53,7 @@ if __name__ == "__main__":
         io.write_vtu(args.outdir / "galahad_obstacle.vtu", mesh.geometry, mesh.cells, {"galahad": x[:n]})
     if args.ipopt:
         x = ipopt_solver(problem, np.zeros(len(f)), bounds, max_iter=args.max_iter, tol=args.tol, activate_hessian=args.use_hessian,
-                         coords=coords if args.use_hessian else None)
+                         coords=coords if args.use_hessian else None,
+                         **({"method": "interior_point"} if args.interior_point else {}))
         print(f"ipopt slot: {problem.total_iteration_count} iterations, objective {problem.objective(x):.12e}")
         io.write_vtu(args.outdir / "ipopt_obstacle.vtu", mesh.geometry, mesh.cells, {"ipopt": x[:n]})

@@ -477,6 +477,18 @@ SYMBOLS = [
     ("pgx_ek_l2_increment_u", C.c_int, [_H, c_double_p]),
     ("pgx_ek_eval_cells", C.c_int, [_H, c_double_p]),
     ("pgx_ek_lu_stats", C.c_int, [_H, C.POINTER(pgx_dn_stats)]),
+    # interior-point solver for bound-constrained quadratic programmes (include/pgx_ipm.h)
+    ("pgx_ipm_create", C.c_int,
+     [C.c_int64, C.c_int64, c_int32_p, c_int32_p, c_double_p, C.c_int64, C.c_int32, c_double_p, C.c_int, C.POINTER(_H)]),
+    ("pgx_ipm_destroy", None, [_H]),
+    ("pgx_ipm_last_error", C.c_char_p, [_H]),
+    ("pgx_ipm_set_problem", C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
+    ("pgx_ipm_solve", C.c_int,
+     [_H, c_double_p, C.c_double, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    ("pgx_ipm_history", C.c_int, [_H, c_int64_p, c_double_p]),
+    ("pgx_ipm_profile", C.c_int, [_H, C.c_int, c_double_p]),
+    ("pgx_ipm_eval", C.c_int, [_H, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    ("pgx_ipm_kkt_export", C.c_int, [_H, c_double_p, c_double_p, c_double_p, c_double_p]),
 ]
 # the entry points the eight mixed-matrix families share, each under its own prefix (proximalgalerkin_amd/_mixed.py)
 _MIXED_COMMON = [
