@@ -174,6 +174,13 @@ struct pgx_handle {
   pgx_comm* lu_comm = nullptr;
   double* Jmix = nullptr;  // [4 * s_nnz] values of the mixed CSR matrix in the layout lu was created with
   bool dh_interior = false;
+  // PGX_D_DIRECT (default 1; 0: the launches before it, for A/B): on a single handle of degree 1 with a uniform finest level the
+  // kernels that compute D(psi) store every copy the solver reads - k_resid_fill_grid / k_resid_fill_frame write Dh, Dd4 and Dq of
+  // level 0 (no k_csr_to_stencil_h, k_pack_d4, k_f_pack_d there), k_rap7h writes Dq of the coarse level it produces, and the
+  // coarsenings onto levels of at least rap_lds_min vertices (PGX_RAP_LDS_MIN) stage their fine stencils in LDS.  Same bits.
+  int d_direct = 1;
+  int rap_lds_min = 60000;  // 257^2 and above: staged 7.2 against 9.7 us there, 13.4 / 22 at 513^2, 44 / 101 at 1025^2
+  bool d0_direct = false;  // with dh_interior: the frame rows of lev[0].Dh and lev[0].Dd4 / Dq are in place as well (residual_dev)
   int stag_its = 12;       // PGX_STAG_ITS / PGX_STAG_GAIN: stagnation test of the smoother damping (fgmres)
   double stag_gain = 1e-4;
   int smooth_d32 = 0;      // PGX_SMOOTH_D32=1: the finest-level smoother reads a single-precision copy of the D stencils.  OFF by
@@ -1247,6 +1254,8 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_SPMV_DICT")) h->spmv_dict = atoi(e);
   if (const char* e = pgx_tune("PGX_SPMV_STENCIL")) h->spmv_stencil = atoi(e);
   if (const char* e = pgx_tune("PGX_RESID_GRID")) h->resid_grid = atoi(e);
+  if (const char* e = pgx_tune("PGX_D_DIRECT")) h->d_direct = atoi(e);
+  if (const char* e = pgx_tune("PGX_RAP_LDS_MIN")) h->rap_lds_min = atoi(e);
   if (const char* e = pgx_tune("PGX_K6_MAX")) h->k6_max = atoi(e);
   if (const char* e = pgx_tune("PGX_SMOOTH_D32")) h->smooth_d32 = atoi(e);
   if (const char* e = pgx_tune("PGX_HOST_POLL")) h->host_poll = atoi(e);
@@ -1812,6 +1821,12 @@ static int dev_norm(pgx_handle* h, const double* v, double* out, size_t len = 0)
   return PGX_OK;
 }
 
+// PGX_D_DIRECT applies: single handle, degree 1, uniform finest level through the grid kernels, fp64 stencils without the float copy
+static bool d_direct_on(const pgx_handle* h) {
+  return h->d_direct && !h->dist.on && h->degree == 1 && h->structured && h->resid_grid && !h->lev.empty() && h->lev[0].uniform &&
+         sizeof(dsten_t) == 8 && !h->lev[0].Dh32;
+}
+
 static void residual_dev(pgx_handle* h, const double* x, double* F, int with_d = 0) {
   PhaseTimer t(h, 0);
   if (h->degree == 2) {
@@ -1826,8 +1841,9 @@ static void residual_dev(pgx_handle* h, const double* x, double* F, int with_d =
     // cycle): the interior rows of D go to the stencil only - their CSR form (56 B per vertex, 235 MB at 2048^2) has no reader
     // until the next pgx_jacobian_fill / pgx_csr_export, which refill it (jac_valid is dropped at the end of the solve)
     pgxk_resid_fill_grid(h->st, with_d ? 1 : 0, h->lev[0], h->fill_lds, h->rowptr, h->v2c_ptr, h->v2c_ent, h->v2c_pos, h->cells,
-                         h->coords, h->mask, h->gbc, h->bphi, x, h->xk, h->alpha, h->f, h->q, F, h->Dv, with_d);
+                         h->coords, h->mask, h->gbc, h->bphi, x, h->xk, h->alpha, h->f, h->q, F, h->Dv, with_d, d_direct_on(h), h->colm);
     h->dh_interior = with_d != 0;  // the interior rows of the finest D stencil are in place (consumed by jacobian_dev(have_d))
+    h->d0_direct = with_d != 0 && d_direct_on(h);  // ... and its frame rows, Dd4 and Dq with them
     if (with_d == 2) h->dv_lean = true;
     if (with_d == 1) h->dv_lean = false;  // a full fill of the CSR rows too
     return;
@@ -1850,8 +1866,9 @@ static int jacobian_dev(pgx_handle* h, const double* x, bool have_d = false) {
       // uniform structured mesh: D(psi) comes from the same element kernel the Newton driver uses (its residual output goes to
       // scratch), so pgx_jacobian_fill + pgx_csr_export put THAT kernel under the entry-wise oracle comparison of the parity tests
       pgxk_resid_fill_grid(h->st, 1, h->lev[0], h->fill_lds, h->rowptr, h->v2c_ptr, h->v2c_ent, h->v2c_pos, h->cells, h->coords,
-                           h->mask, h->gbc, h->bphi, x, h->xk, h->alpha, h->f, h->q, h->w, h->Dv, 1);
+                           h->mask, h->gbc, h->bphi, x, h->xk, h->alpha, h->f, h->q, h->w, h->Dv, 1, d_direct_on(h), h->colm);
       h->dh_interior = true;
+      h->d0_direct = d_direct_on(h);
       h->dv_lean = false;  // a full fill: CSR rows and stencil
       have_d = true;
     } else {
@@ -1861,12 +1878,17 @@ static int jacobian_dev(pgx_handle* h, const double* x, bool have_d = false) {
   }
   if (h->structured) {
     PhaseTimer t(h, 2);
-    pgxk_csr_to_stencil_h(h->st, h->n, h->nx + 1, h->rowptr, h->colm, h->Dv, h->lev[0].Dh,
-                          (have_d && h->degree == 1 && h->dh_interior) ? h->lev[0].ny : 0);
+    // direct: the kernels that computed D(psi) stored Dh (frame too), Dd4 and Dq of level 0 - nothing to convert or repack here
+    const bool direct = d_direct_on(h);
+    const bool d0 = direct && have_d && h->dh_interior && h->d0_direct;
+    if (!d0)
+      pgxk_csr_to_stencil_h(h->st, h->n, h->nx + 1, h->rowptr, h->colm, h->Dv, h->lev[0].Dh,
+                            (have_d && h->degree == 1 && h->dh_interior) ? h->lev[0].ny : 0);
     h->dh_interior = false;
+    h->d0_direct = false;
     if (h->lev[0].Dh32) pgxk_to_float(h->st, (size_t)4 * h->n, h->lev[0].Dh, h->lev[0].Dh32);
-    if (h->lev[0].f32) pgxk_f_pack_d(h->st, h->lev[0]);
-    if (h->lev[0].Dd4) pgxk_pack_d4(h->st, h->lev[0]);
+    if (h->lev[0].f32 && !d0) pgxk_f_pack_d(h->st, h->lev[0]);
+    if (h->lev[0].Dd4 && !d0) pgxk_pack_d4(h->st, h->lev[0]);
     const int ld = h->dist.on ? h->dist.ldist : 0;
     for (size_t l = 1; l < h->lev.size(); ++l) {
       if (h->dist.on && (int)l == ld) {  // strip -> replicated level: owned rows + zeros, summed over the ranks
@@ -1882,7 +1904,9 @@ static int jacobian_dev(pgx_handle* h, const double* x, bool have_d = false) {
         if (rc) return rc;
 #endif
       } else {
-        pgxk_rap7h(h->st, h->lev[l - 1], h->lev[l - 1].Dh, h->lev[l], h->lev[l].Dh);
+        // direct: Dq of the coarse level leaves with its values; large levels coarsen from fine stencils staged in LDS
+        pgxk_rap7h(h->st, h->lev[l - 1], h->lev[l - 1].Dh, h->lev[l], h->lev[l].Dh, direct, direct && h->lev[l].n >= h->rap_lds_min);
+        if (direct) continue;
       }
       if (h->lev[l].f32) pgxk_f_pack_d(h->st, h->lev[l]);
     }

@@ -68,7 +68,8 @@ struct GridLevel {
   // the operator apply, the residuals and the Krylov space stay fp64.
   int f32;
   double4* Dd4;  // finest level only (else nullptr): the fp64 D stencil as ONE double4 per vertex for the matrix-free operator apply
-                 // (two 16-byte loads per vertex instead of four 8-byte ones from four arrays); repacked with every Jacobian
+                 // (two 16-byte loads per vertex instead of four 8-byte ones from four arrays); rewritten with every Jacobian, by
+                 // the kernels that compute D(psi) (PGX_D_DIRECT) or from Dh by k_pack_d4
   // Dq: float4 per vertex, or (dbf16 != 0, the default: PGX_F32_DBF16) ONE 8-byte word - the same four values in the same order as
   // two packed bf16 pairs, rounded to nearest even by k_f_pack_d.  The cycle is a preconditioner and does not use the low 16 bits
   // of D: identical Krylov counts on the numpy twin (tools/mg32_study.py), 8 B per vertex less in every launch.
@@ -81,6 +82,24 @@ struct StConst {
   double K[7], M[7];
   int uniform;
 };
+
+// Packing of one vertex's Dq from its four stored D values (GridLevel::Dq): shared by k_f_pack_d (pgx_mg32.hip) and by the kernels
+// that produce D(psi) and store Dq themselves (k_resid_fill_grid, k_resid_fill_frame, k_rap7h*), so both give the same bits.
+// bf16 pairs round to nearest even (v_cvt_pk_bf16_f32): an exact zero stays an exact zero.
+typedef float f_v2f __attribute__((ext_vector_type(2)));
+typedef __bf16 f_v2bf __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t f_pack_bf16x2(float lo, float hi) {
+  const f_v2f f = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, f_v2bf));
+}
+__device__ __forceinline__ void f_pack_d(float4 q, float4& out) { out = q; }
+__device__ __forceinline__ void f_pack_d(float4 q, uint2& out) { out = make_uint2(f_pack_bf16x2(q.x, q.y), f_pack_bf16x2(q.z, q.w)); }
+// values above 1e30 are clamped: an overshot Newton iterate must not put infinities into the preconditioner
+template <class DT>
+__device__ __forceinline__ void f_pack_dq(dsten_t d0, dsten_t d1, dsten_t d2, dsten_t d3, DT& out) {
+  const float big = 1e30f;
+  f_pack_d(make_float4(fminf((float)d0, big), fminf((float)d1, big), fminf((float)d2, big), fminf((float)d3, big)), out);
+}
 
 // fused multigrid tail (k_mg_tail): level descriptors travel in the kernarg segment
 #define PGX_TAIL_MAX 8
@@ -162,7 +181,9 @@ void pgxk_csr_to_stencil(hipStream_t st, int n, int sx, const int32_t* rowptr, c
 void pgxk_csr_to_stencil_h(hipStream_t st, int n, int sx, const int32_t* rowptr, const int32_t* colm,
                            const double* vals, dsten_t* Sh, int frame_ny = 0);
 void pgxk_rap7(hipStream_t st, const GridLevel& f, const double* Sf, const GridLevel& c, double* Sc);
-void pgxk_rap7h(hipStream_t st, const GridLevel& f, const dsten_t* Sfh, const GridLevel& c, dsten_t* Sch);
+// pack != 0: the launch also stores c.Dq of every coarse vertex, packed from the value as stored (no pgxk_f_pack_d after it).
+// staged != 0: a workgroup stages the fine stencils of its coarse rectangle in LDS with coalesced loads (k_rap7h_lds); same bits.
+void pgxk_rap7h(hipStream_t st, const GridLevel& f, const dsten_t* Sfh, const GridLevel& c, dsten_t* Sch, int pack = 0, int staged = 0);
 void pgxk_st_apply(hipStream_t st, int mode, const GridLevel& L, double alpha, const double* xu, const double* xp,
                    const double* bu, const double* bp, double omega, int first, double* yu, double* yp);
 void pgxk_restrict(hipStream_t st, const GridLevel& f, const double* ru, const double* rp, const GridLevel& c,
@@ -271,8 +292,12 @@ void pgxk_resid_fill_p1(hipStream_t st, int write_d, int n, size_t lds_bytes, co
 void pgxk_resid_fill_grid(hipStream_t st, int write_d, const GridLevel& L, size_t lds_bytes, const int32_t* rowptr,
                           const int32_t* v2c_ptr, const int32_t* v2c_ent, const int32_t* v2c_pos, const int32_t* cells,
                           const double* coords, const uint8_t* mask, const double* gbc, const double* bphi, const double* x,
-                          const double* xk, double alpha, double f, QuadTab q, double* F, double* Dout, int write_sh);
+                          const double* xk, double alpha, double f, QuadTab q, double* F, double* Dout, int write_sh,
+                          int direct = 0, const int32_t* colm = nullptr);
 // write_sh: 0 = CSR rows only; 1 = CSR rows + the half-stencil L.Dh of the interior; 2 = half-stencil only (interior CSR rows NOT written)
+// direct != 0 (PGX_D_DIRECT): the frame goes through the compact k_resid_fill_frame (one thread per frame vertex), and with write_d
+// and write_sh both kernels also store L.Dh of the frame and the copies L.Dd4 / L.Dq (where allocated) of every vertex: nothing of
+// level 0 is left for pgxk_csr_to_stencil_h, pgxk_f_pack_d and pgxk_pack_d4.  colm: the CSR columns (the frame's Dh slots).
 // CGS2 with fused passes: (w' = w - V h1; [h2; |w'|^2] = [V,w']^T w') in one pass, then v = (w' - V h2)*scale
 void pgxk_axpy_dot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h1, double* w,
                    double* partials, double* out);

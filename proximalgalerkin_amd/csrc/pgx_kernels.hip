@@ -529,7 +529,7 @@ __global__ void __launch_bounds__(PGX_RF_TX * PGX_RF_TY) k_resid_fill_grid(
     int nx, int ny, int n, const int32_t* __restrict__ rowptr, const double* __restrict__ coords, const uint8_t* __restrict__ mask,
     const double* __restrict__ gbc, const double* __restrict__ bphi, const double* __restrict__ x, const double* __restrict__ xk,
     double alpha, double f, QuadTab q, StConst sc, double* __restrict__ F, double* __restrict__ Dout,
-    dsten_t* __restrict__ Sh) {
+    dsten_t* __restrict__ Sh, double4* __restrict__ Dd4, void* __restrict__ Dq, int dbf16) {
   constexpr int TX = PGX_RF_TX, TY = PGX_RF_TY, IW = TX + 2, IH = TY + 2, SW = TX + 1, SH = TY + 1;
   __shared__ double iu[IH * IW], ip[IH * IW], idp[IH * IW];
   __shared__ double E[2 * SW * SH][6];  // [2 * square + triangle][00, 11, 22, 01, 02, 12]
@@ -608,6 +608,14 @@ __global__ void __launch_bounds__(PGX_RF_TX * PGX_RF_TY) k_resid_fill_grid(
       Sh[2 * (size_t)n + v] = (dsten_t)dN;
       Sh[3 * (size_t)n + v] = (dsten_t)dNE;
     }
+    // the level's other copies of the same four values (direct path: no k_pack_d4 / k_f_pack_d pass over Dh afterwards)
+    if (Dd4) Dd4[v] = make_double4(dC, dE, dN, dNE);
+    if (Dq) {
+      if (dbf16)
+        f_pack_dq((dsten_t)dC, (dsten_t)dE, (dsten_t)dN, (dsten_t)dNE, ((uint2*)Dq)[v]);
+      else
+        f_pack_dq((dsten_t)dC, (dsten_t)dE, (dsten_t)dN, (dsten_t)dNE, ((float4*)Dq)[v]);
+    }
   }
   const int o = (lj + 1) * IW + li + 1;
   const int off[7] = {0, 1, -1, IW, -IW, IW + 1, -IW - 1};
@@ -621,6 +629,107 @@ __global__ void __launch_bounds__(PGX_RF_TX * PGX_RF_TY) k_resid_fill_grid(
   const double load = adet * 2.0 * (q.mref[0] + q.mref[1] + q.mref[2]);  // int phi_i over the six triangles
   F[v] = mask[v] ? x[v] - gbc[v] : alpha * Ku + Mdp - alpha * f * load;
   F[n + v] = Mu - (((dSW + dS) + (dW + dC)) + ((dE + dN) + dNE)) - bphi[v];
+}
+
+// ------------------------------------------------------------------------------------------------
+// Compact twin of k_resid_fill_p1<WRITE_D, true>: one thread per vertex of the boundary frame of an (nx + 1) x (ny + 1) grid,
+// enumerated side by side (bottom row, top row, left column, right column) - 2 (nx + 1) + 2 (ny - 1) threads instead of a
+// launch over all n vertices in which a frame column vertex sits alone in its wave.  The arithmetic is that kernel's, in its
+// order: cells in v2c order, quadrature points in order, the row accumulated at the v2c_pos positions - in the thread's own seven
+// LDS slots (a row of the 7-point stencil has at most seven entries) instead of the block's row image.  One pass writes F, the CSR
+// row and, Sh != nullptr, the vertex's half-stencil slots by the column rule of k_csr_to_stencil_h (offsets 0, 1, sx, sx + 1)
+// with their copies Dd4 / Dq (nullable), packed as k_pack_d4 / k_f_pack_d pack them.
+// ------------------------------------------------------------------------------------------------
+#define PGX_FRAME_BLOCK 64
+template <bool WRITE_D>
+__global__ void __launch_bounds__(PGX_FRAME_BLOCK) k_resid_fill_frame(
+    int nx, int ny, int n, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colm, const int32_t* __restrict__ v2c_ptr,
+    const int32_t* __restrict__ v2c_ent, const int32_t* __restrict__ v2c_pos, const int32_t* __restrict__ cells,
+    const double* __restrict__ coords, const uint8_t* __restrict__ mask, const double* __restrict__ gbc,
+    const double* __restrict__ bphi, const double* __restrict__ x, const double* __restrict__ xk, double alpha, double f, QuadTab q,
+    double* __restrict__ F, double* __restrict__ Dout, dsten_t* __restrict__ Sh, double4* __restrict__ Dd4, void* __restrict__ Dq,
+    int dbf16) {
+  __shared__ double acc[PGX_FRAME_BLOCK * 7];
+  const int sx = nx + 1;
+  const int t = blockIdx.x * PGX_FRAME_BLOCK + threadIdx.x;
+  if (t >= 2 * sx + 2 * (ny - 1)) return;
+  int gi, gj;
+  if (t < sx) {
+    gi = t, gj = 0;
+  } else if (t < 2 * sx) {
+    gi = t - sx, gj = ny;
+  } else if (t < 2 * sx + ny - 1) {
+    gi = 0, gj = 1 + t - 2 * sx;
+  } else {
+    gi = nx, gj = 1 + t - 2 * sx - (ny - 1);
+  }
+  const int i = gj * sx + gi;
+  double* row = acc + threadIdx.x * 7;
+  const int r0 = rowptr[i], rl = min(rowptr[i + 1] - r0, 7);
+  if (WRITE_D)
+    for (int k = 0; k < rl; ++k) row[k] = 0.0;
+  double Fu = 0.0, Fp = 0.0;
+  const int ke = v2c_ptr[i + 1];
+  for (int k = v2c_ptr[i]; k < ke; ++k) {
+    const int e = v2c_ent[k];
+    const int c = e >> 2, a = e & 3;
+    const int v[3] = {cells[3 * c], cells[3 * c + 1], cells[3 * c + 2]};
+    const P1Geom g = p1_geom(coords[2 * v[0]], coords[2 * v[0] + 1], coords[2 * v[1]], coords[2 * v[1] + 1],
+                             coords[2 * v[2]], coords[2 * v[2] + 1]);
+    double u[3], p[3], dp[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      u[b] = mask[v[b]] ? gbc[v[b]] : x[v[b]];
+      p[b] = x[n + v[b]];
+      dp[b] = p[b] - xk[n + v[b]];
+    }
+    double d[3] = {0.0, 0.0, 0.0};
+    for (int k2 = 0; k2 < q.nq; ++k2) {
+      const double pq = p[0] * q.N[k2][0] + p[1] * q.N[k2][1] + p[2] * q.N[k2][2];
+      const double wa = q.w[k2] * exp(pq) * q.N[k2][a];
+      d[0] += wa * q.N[k2][0];
+      d[1] += wa * q.N[k2][1];
+      d[2] += wa * q.N[k2][2];
+    }
+    const double gx = u[0] * g.G[0][0] + u[1] * g.G[1][0] + u[2] * g.G[2][0];
+    const double gy = u[0] * g.G[0][1] + u[1] * g.G[1][1] + u[2] * g.G[2][1];
+    const double Ku = 0.5 * g.adet * (g.G[a][0] * gx + g.G[a][1] * gy);
+    const double Mdp = g.adet * (q.Mref[a][0] * dp[0] + q.Mref[a][1] * dp[1] + q.Mref[a][2] * dp[2]);
+    const double Mu = g.adet * (q.Mref[a][0] * u[0] + q.Mref[a][1] * u[1] + q.Mref[a][2] * u[2]);
+    Fu += alpha * Ku + Mdp - alpha * f * g.adet * q.mref[a];
+    Fp += Mu - g.adet * (d[0] + d[1] + d[2]);
+    if (WRITE_D) {
+      const int pos = v2c_pos[k];
+      row[min(pos & 0xff, 6)] += g.adet * d[0];
+      row[min((pos >> 8) & 0xff, 6)] += g.adet * d[1];
+      row[min((pos >> 16) & 0xff, 6)] += g.adet * d[2];
+    }
+  }
+  F[i] = mask[i] ? x[i] - gbc[i] : Fu;
+  F[n + i] = Fp - bphi[i];
+  if (WRITE_D) {
+    double s[4] = {0, 0, 0, 0};
+    for (int k = 0; k < rl; ++k) {
+      const double val = row[k];
+      Dout[r0 + k] = val;
+      const int o = (colm[r0 + k] & 0x7fffffff) - i;
+      if (o == 0) s[0] = val;
+      else if (o == 1) s[1] = val;
+      else if (o == sx) s[2] = val;
+      else if (o == sx + 1) s[3] = val;
+    }
+    if (Sh) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) Sh[(size_t)k * n + i] = (dsten_t)s[k];
+      if (Dd4) Dd4[i] = make_double4(s[0], s[1], s[2], s[3]);
+      if (Dq) {
+        if (dbf16)
+          f_pack_dq((dsten_t)s[0], (dsten_t)s[1], (dsten_t)s[2], (dsten_t)s[3], ((uint2*)Dq)[i]);
+        else
+          f_pack_dq((dsten_t)s[0], (dsten_t)s[1], (dsten_t)s[2], (dsten_t)s[3], ((float4*)Dq)[i]);
+      }
+    }
+  }
 }
 
 void pgxk_resid_fill_p1(hipStream_t st, int write_d, int n, size_t lds_bytes, const int32_t* rowptr,
@@ -651,24 +760,41 @@ void pgxk_resid_fill_p1(hipStream_t st, int write_d, int n, size_t lds_bytes, co
 void pgxk_resid_fill_grid(hipStream_t st, int write_d, const GridLevel& L, size_t lds_bytes, const int32_t* rowptr,
                           const int32_t* v2c_ptr, const int32_t* v2c_ent, const int32_t* v2c_pos, const int32_t* cells,
                           const double* coords, const uint8_t* mask, const double* gbc, const double* bphi, const double* x,
-                          const double* xk, double alpha, double f, QuadTab q, double* F, double* Dout, int write_sh) {
+                          const double* xk, double alpha, double f, QuadTab q, double* F, double* Dout, int write_sh, int direct,
+                          const int32_t* colm) {
   const int n = L.n, sx = L.nx + 1;
-  dim3 grid((n + PGX_BLOCK - 1) / PGX_BLOCK), block(PGX_BLOCK);
-  if (write_d)
-    hipLaunchKernelGGL((k_resid_fill_p1<true, true>), grid, block, lds_bytes, st, n, rowptr, v2c_ptr, v2c_ent, v2c_pos, cells,
-                       coords, mask, gbc, bphi, x, xk, alpha, f, q, sx, L.ny, F, Dout);
-  else
-    hipLaunchKernelGGL((k_resid_fill_p1<false, true>), grid, block, lds_bytes, st, n, rowptr, v2c_ptr, v2c_ent, v2c_pos, cells,
-                       coords, mask, gbc, bphi, x, xk, alpha, f, q, sx, L.ny, F, Dout);
+  // direct: the stencil copies of level 0 leave with the values (frame and interior); needs the CSR columns for the frame's slots
+  const bool copies = direct && write_d && write_sh && colm;
+  double4* Dd4 = copies ? L.Dd4 : nullptr;
+  void* Dq = copies && L.f32 ? L.Dq : nullptr;
+  if (direct && colm) {
+    const int nframe = 2 * sx + 2 * (L.ny - 1);
+    dim3 grid((nframe + PGX_FRAME_BLOCK - 1) / PGX_FRAME_BLOCK), block(PGX_FRAME_BLOCK);
+    if (write_d)
+      hipLaunchKernelGGL(k_resid_fill_frame<true>, grid, block, 0, st, L.nx, L.ny, n, rowptr, colm, v2c_ptr, v2c_ent, v2c_pos, cells,
+                         coords, mask, gbc, bphi, x, xk, alpha, f, q, F, Dout, copies ? L.Dh : nullptr, Dd4, Dq, L.dbf16);
+    else
+      hipLaunchKernelGGL(k_resid_fill_frame<false>, grid, block, 0, st, L.nx, L.ny, n, rowptr, colm, v2c_ptr, v2c_ent, v2c_pos, cells,
+                         coords, mask, gbc, bphi, x, xk, alpha, f, q, F, Dout, nullptr, nullptr, nullptr, 0);
+  } else {
+    dim3 grid((n + PGX_BLOCK - 1) / PGX_BLOCK), block(PGX_BLOCK);
+    if (write_d)
+      hipLaunchKernelGGL((k_resid_fill_p1<true, true>), grid, block, lds_bytes, st, n, rowptr, v2c_ptr, v2c_ent, v2c_pos, cells,
+                         coords, mask, gbc, bphi, x, xk, alpha, f, q, sx, L.ny, F, Dout);
+    else
+      hipLaunchKernelGGL((k_resid_fill_p1<false, true>), grid, block, lds_bytes, st, n, rowptr, v2c_ptr, v2c_ent, v2c_pos, cells,
+                         coords, mask, gbc, bphi, x, xk, alpha, f, q, sx, L.ny, F, Dout);
+  }
   if (L.nx < 2 || L.ny < 2) return;
   const int ntx = (L.nx - 1 + PGX_RF_TX - 1) / PGX_RF_TX, nty = (L.ny - 1 + PGX_RF_TY - 1) / PGX_RF_TY;
   const StConst sc = make_stconst(L);
   if (write_d)
     hipLaunchKernelGGL(k_resid_fill_grid<true>, dim3(ntx * nty), dim3(PGX_RF_TX * PGX_RF_TY), 0, st, L.nx, L.ny, n, rowptr, coords,
-                       mask, gbc, bphi, x, xk, alpha, f, q, sc, F, write_sh == 2 ? nullptr : Dout, write_sh ? L.Dh : nullptr);
+                       mask, gbc, bphi, x, xk, alpha, f, q, sc, F, write_sh == 2 ? nullptr : Dout, write_sh ? L.Dh : nullptr, Dd4, Dq,
+                       L.dbf16);
   else
     hipLaunchKernelGGL(k_resid_fill_grid<false>, dim3(ntx * nty), dim3(PGX_RF_TX * PGX_RF_TY), 0, st, L.nx, L.ny, n, rowptr, coords,
-                       mask, gbc, bphi, x, xk, alpha, f, q, sc, F, Dout, nullptr);
+                       mask, gbc, bphi, x, xk, alpha, f, q, sc, F, Dout, nullptr, nullptr, nullptr, 0);
 }
 
 void pgxk_fill_rows(hipStream_t st, int mode, int n, size_t lds_bytes, const int32_t* rowptr, const int32_t* v2c_ptr,
@@ -1908,25 +2034,22 @@ void pgxk_csr_to_stencil_h(hipStream_t st, int n, int sx, const int32_t* rowptr,
                      colm, vals, Sh, frame_ny);
 }
 
-// Galerkin coarsening on symmetric-half storage: only the 4 stored coarse slots are produced.
-__global__ void __launch_bounds__(PGX_BLOCK) k_rap7h(int nxf, int nyf, int nf, const dsten_t* __restrict__ Sfh, int nxc,
-                                                     int nyc, int ncv, dsten_t* __restrict__ Sch) {
-  const int C = blockIdx.x * blockDim.x + threadIdx.x;
-  if (C >= ncv) return;
+// Galerkin coarsening on symmetric-half storage: only the 4 stored coarse slots are produced.  The four values of coarse vertex
+// (I, Jc) as they are stored; LD(ax, ay, cf) loads the seven coefficients of fine vertex (ax, ay) with ld7h's zero rules.  Shared by
+// the plain kernel (loads from global memory) and the staged one (from LDS): one loop nest, one order of additions.
+template <class LD>
+__device__ __forceinline__ void rap7h_vertex(LD ld, int I, int Jc, int nxf, int nyf, int nxc, int nyc, dsten_t st4[4]) {
   constexpr int OX[7] = {0, 1, -1, 0, 0, 1, -1};
   constexpr int OY[7] = {0, 0, 0, 1, -1, 1, -1};
   constexpr int KEEP[4] = {0, 1, 3, 5};  // full-stencil slots stored in the half format
-  const int sxc = nxc + 1, sxf = nxf + 1;
-  const int I = C % sxc, Jc = C / sxc;
   double out[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int oa = 0; oa < 7; ++oa) {
     const int ax = 2 * I + OX[oa], ay = 2 * Jc + OY[oa];
     if (ax < 0 || ax > nxf || ay < 0 || ay > nyf) continue;
     const double wa = pw(OX[oa], OY[oa]);
-    const int a = ay * sxf + ax;
     double cf[7];
-    ld7h(Sfh, nf, sxf, a, ax, ay, nxf, nyf, cf);
+    ld(ax, ay, cf);
 #pragma unroll
     for (int os = 0; os < 7; ++os) {
       const double coef = wa * cf[os];
@@ -1942,12 +2065,102 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_rap7h(int nxf, int nyf, int nf, c
   for (int q = 0; q < 4; ++q) {
     const int nx_ = I + OX[KEEP[q]], ny_ = Jc + OY[KEEP[q]];
     const bool ok = nx_ >= 0 && nx_ <= nxc && ny_ >= 0 && ny_ <= nyc;
-    Sch[(size_t)q * ncv + C] = (dsten_t)(ok ? out[q] : 0.0);
+    st4[q] = (dsten_t)(ok ? out[q] : 0.0);
   }
 }
-void pgxk_rap7h(hipStream_t st, const GridLevel& f, const dsten_t* Sfh, const GridLevel& c, dsten_t* Sch) {
+// Dq != nullptr: the level's packed single-precision copy leaves with the values (what k_f_pack_d would read back and pack)
+__device__ __forceinline__ void rap7h_store(const dsten_t st4[4], int ncv, int C, dsten_t* Sch, void* Dq, int dbf16) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) Sch[(size_t)q * ncv + C] = st4[q];
+  if (Dq) {
+    if (dbf16)
+      f_pack_dq(st4[0], st4[1], st4[2], st4[3], ((uint2*)Dq)[C]);
+    else
+      f_pack_dq(st4[0], st4[1], st4[2], st4[3], ((float4*)Dq)[C]);
+  }
+}
+
+__global__ void __launch_bounds__(PGX_BLOCK) k_rap7h(int nxf, int nyf, int nf, const dsten_t* __restrict__ Sfh, int nxc,
+                                                     int nyc, int ncv, dsten_t* __restrict__ Sch, void* __restrict__ Dq, int dbf16) {
+  const int C = blockIdx.x * blockDim.x + threadIdx.x;
+  if (C >= ncv) return;
+  const int sxc = nxc + 1, sxf = nxf + 1;
+  const int I = C % sxc, Jc = C / sxc;
+  dsten_t st4[4];
+  rap7h_vertex([&](int ax, int ay, double cf[7]) { ld7h(Sfh, nf, sxf, ay * sxf + ax, ax, ay, nxf, nyf, cf); }, I, Jc, nxf, nyf, nxc,
+               nyc, st4);
+  rap7h_store(st4, ncv, C, Sch, Dq, dbf16);
+}
+
+// Staged twin for the large levels, where the plain kernel's 49 stride-2 8-byte loads per thread run at a third of the copy rate:
+// a workgroup owns CX x CY coarse vertices and loads the fine stencils they touch - the 2x rectangle plus one fine vertex all round,
+// plus the column and row before it for the negative-direction links - into LDS with coalesced loads, even and odd fine columns in
+// separate halves of an LDS row so that the lanes of a wave (stride 2 in the fine grid) read consecutive words.  Vertices outside the
+// grid are staged as zeros and never used: the loader keeps ld7h's rules on the global coordinates.
+#define PGX_RAPL_CX 32
+#define PGX_RAPL_CY 8
+// A thread issues all its loads (19 or 20 of 8 bytes) before its first LDS store: looped one by one the launch was latency-bound.
+__global__ void __launch_bounds__(PGX_RAPL_CX * PGX_RAPL_CY) k_rap7h_lds(int nxf, int nyf, int nf, const dsten_t* __restrict__ Sfh,
+                                                                         int nxc, int nyc, int ncv, dsten_t* __restrict__ Sch,
+                                                                         void* __restrict__ Dq, int dbf16) {
+  constexpr int CX = PGX_RAPL_CX, CY = PGX_RAPL_CY, FW = 2 * CX + 2, FH = 2 * CY + 2, HW = FW / 2;
+  constexpr int NT = CX * CY, NV = FH * FW, IT = (NV + NT - 1) / NT;
+  __shared__ dsten_t s[4][NV];
+  const int sxc = nxc + 1, sxf = nxf + 1;
+  const int ntx = (sxc + CX - 1) / CX;
+  const int I0 = ((int)blockIdx.x % ntx) * CX, J0 = ((int)blockIdx.x / ntx) * CY;
+  const int fx0 = 2 * I0 - 2, fy0 = 2 * J0 - 2;  // fine vertex of LDS cell (0, 0)
+  dsten_t val[IT][4];
+#pragma unroll
+  for (int k = 0; k < IT; ++k) {
+    const int t = (int)threadIdx.x + k * NT, ly = t / FW, lx = t % FW;
+    const int fx = fx0 + lx, fy = fy0 + ly;
+    val[k][0] = val[k][1] = val[k][2] = val[k][3] = 0;
+    if (t < NV && fx >= 0 && fx <= nxf && fy >= 0 && fy <= nyf) {
+      const size_t a = (size_t)fy * sxf + fx;
+#pragma unroll
+      for (int sl = 0; sl < 4; ++sl) val[k][sl] = Sfh[(size_t)sl * nf + a];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < IT; ++k) {
+    const int t = (int)threadIdx.x + k * NT, ly = t / FW, lx = t % FW;
+    if (t < NV) {
+#pragma unroll
+      for (int sl = 0; sl < 4; ++sl) s[sl][ly * FW + (lx & 1) * HW + (lx >> 1)] = val[k][sl];
+    }
+  }
+  __syncthreads();
+  const int I = I0 + (int)threadIdx.x % CX, Jc = J0 + (int)threadIdx.x / CX;
+  if (I > nxc || Jc > nyc) return;
+  auto at = [&](int lx, int ly) { return ly * FW + (lx & 1) * HW + (lx >> 1); };
+  dsten_t st4[4];
+  rap7h_vertex(
+      [&](int ax, int ay, double cf[7]) {  // ld7h from the staged image: 1 <= lx, ly inside it for every fine vertex of the nest
+        const int lx = ax - fx0, ly = ay - fy0;
+        const int l = at(lx, ly), lw = at(lx - 1, ly), ls = at(lx, ly - 1), lsw = at(lx - 1, ly - 1);
+        cf[0] = s[0][l];
+        cf[1] = (ax < nxf) ? s[1][l] : 0.0;
+        cf[2] = (ax > 0) ? s[1][lw] : 0.0;
+        cf[3] = (ay < nyf) ? s[2][l] : 0.0;
+        cf[4] = (ay > 0) ? s[2][ls] : 0.0;
+        cf[5] = (ax < nxf && ay < nyf) ? s[3][l] : 0.0;
+        cf[6] = (ax > 0 && ay > 0) ? s[3][lsw] : 0.0;
+      },
+      I, Jc, nxf, nyf, nxc, nyc, st4);
+  rap7h_store(st4, ncv, Jc * sxc + I, Sch, Dq, dbf16);
+}
+
+void pgxk_rap7h(hipStream_t st, const GridLevel& f, const dsten_t* Sfh, const GridLevel& c, dsten_t* Sch, int pack, int staged) {
+  void* Dq = (pack && c.f32) ? c.Dq : nullptr;
+  if (staged) {
+    const int ntx = (c.nx + 1 + PGX_RAPL_CX - 1) / PGX_RAPL_CX, nty = (c.ny + 1 + PGX_RAPL_CY - 1) / PGX_RAPL_CY;
+    hipLaunchKernelGGL(k_rap7h_lds, dim3(ntx * nty), dim3(PGX_RAPL_CX * PGX_RAPL_CY), 0, st, f.nx, f.ny, f.n, Sfh, c.nx, c.ny, c.n, Sch,
+                       Dq, c.dbf16);
+    return;
+  }
   hipLaunchKernelGGL(k_rap7h, dim3((c.n + PGX_BLOCK - 1) / PGX_BLOCK), dim3(PGX_BLOCK), 0, st, f.nx, f.ny, f.n, Sfh,
-                     c.nx, c.ny, c.n, Sch);
+                     c.nx, c.ny, c.n, Sch, Dq, c.dbf16);
 }
 
 __global__ void k_coarse_mask(int nxc, int nyc, int ncv, int nxf, const uint8_t* __restrict__ mf,

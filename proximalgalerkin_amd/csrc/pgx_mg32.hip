@@ -56,14 +56,7 @@ __device__ __forceinline__ float lane_shr1f(float x) {  // the value of lane - 1
 // The storage of D(psi) on a single-precision level is a template parameter DT of every reader: float4, or uint2 = two packed bf16
 // pairs (x: D(0,0) low half, D(+1,0) high half; y: D(0,+1), D(+1,+1)).  Packing rounds to nearest even (v_cvt_pk_bf16_f32), so an
 // exact zero stays an exact zero; unpacking is one shift or mask per value.  From f_unpack_d on the readers work on a float4.
-typedef float f_v2f __attribute__((ext_vector_type(2)));
-typedef __bf16 f_v2bf __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t f_pack_bf16x2(float lo, float hi) {
-  const f_v2f f = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, f_v2bf));
-}
-__device__ __forceinline__ void f_pack_d(float4 q, float4& out) { out = q; }
-__device__ __forceinline__ void f_pack_d(float4 q, uint2& out) { out = make_uint2(f_pack_bf16x2(q.x, q.y), f_pack_bf16x2(q.z, q.w)); }
+// The packers (f_pack_bf16x2, f_pack_d, f_pack_dq) live in pgx_internal.h: the kernels that produce D(psi) store Dq themselves.
 __device__ __forceinline__ float4 f_unpack_d(float4 q) { return q; }
 __device__ __forceinline__ float4 f_unpack_d(uint2 w) {
   return make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
@@ -76,10 +69,7 @@ template <class DT>
 __global__ void __launch_bounds__(256) k_f_pack_d(int n, const dsten_t* __restrict__ Dh, DT* __restrict__ Dq) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n) return;
-  const float big = 1e30f;
-  f_pack_d(make_float4(fminf((float)Dh[v], big), fminf((float)Dh[(size_t)n + v], big), fminf((float)Dh[2 * (size_t)n + v], big),
-                       fminf((float)Dh[3 * (size_t)n + v], big)),
-           Dq[v]);
+  f_pack_dq(Dh[v], Dh[(size_t)n + v], Dh[2 * (size_t)n + v], Dh[3 * (size_t)n + v], Dq[v]);
 }
 void pgxk_f_pack_d(hipStream_t st, const GridLevel& L) {
   if (L.dbf16)
