@@ -199,6 +199,30 @@ class pgx_qvi_problem(C.Structure):  # include/pgx_qvi.h
     ]
 
 
+class pgx_qmy_problem(C.Structure):  # include/pgx_qmy.h
+    _fields_ = [
+        ("nq", C.c_int32),
+        ("qpts", c_double_p),
+        ("qwts", c_double_p),
+        ("Phi0", c_double_p),
+        ("phi", c_double_p),
+        ("f", C.c_double),
+        ("q", C.c_double),
+        ("n_bc", C.c_int32),
+        ("bc_dofs", c_int32_p),
+    ]
+
+
+class pgx_qmy_newton_opts(C.Structure):  # include/pgx_qmy.h
+    _fields_ = [
+        ("ftol", C.c_double),
+        ("xtol", C.c_double),
+        ("c1", C.c_double),
+        ("max_it", C.c_int32),
+        ("monitor", C.c_int32),
+    ]
+
+
 class pgx_ic_problem(C.Structure):  # include/pgx_ic.h
     _fields_ = [
         ("n_vertices", C.c_int32),
@@ -419,6 +443,28 @@ SYMBOLS = [
     ("pgx_qvi_create", C.c_int, [C.POINTER(pgx_mesh), C.POINTER(pgx_qvi_problem), C.c_int, C.POINTER(_H)]),
     ("pgx_qvi_num_dofs", C.c_int, [_H, c_int64_p]),
     ("pgx_qvi_h1_increment", C.c_int, [_H, c_double_p]),
+    # example 05, comparison solvers: Moreau-Yosida and fixed point (include/pgx_qmy.h)
+    ("pgx_qmy_create", C.c_int, [C.POINTER(pgx_mesh), C.POINTER(pgx_qmy_problem), C.c_int, C.POINTER(_H)]),
+    ("pgx_qmy_destroy", None, [_H]),
+    ("pgx_qmy_last_error", C.c_char_p, [_H]),
+    ("pgx_qmy_num_dofs", C.c_int, [_H, c_int64_p]),
+    ("pgx_qmy_set_state", C.c_int, [_H, c_double_p]),
+    ("pgx_qmy_get_state", C.c_int, [_H, c_double_p]),
+    ("pgx_qmy_set_prev", C.c_int, [_H, c_double_p]),
+    ("pgx_qmy_get_prev", C.c_int, [_H, c_double_p]),
+    ("pgx_qmy_advance_prev", C.c_int, [_H]),
+    ("pgx_qmy_set_gamma", C.c_int, [_H, C.c_double]),
+    ("pgx_qmy_set_active", C.c_int, [_H, C.c_int]),
+    ("pgx_qmy_residual", C.c_int, [_H, c_double_p, c_double_p, c_double_p]),
+    ("pgx_qmy_residual_inf", C.c_int, [_H, c_double_p, c_double_p]),
+    ("pgx_qmy_jacobian_fill", C.c_int, [_H, c_double_p]),
+    ("pgx_qmy_csr_export", C.c_int, [_H, c_int64_p, c_int64_p, c_int32_p, c_int32_p, c_double_p]),
+    ("pgx_qmy_spmv", C.c_int, [_H, c_double_p, c_double_p]),
+    ("pgx_qmy_newton_solve", C.c_int, [_H, C.POINTER(pgx_qmy_newton_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("pgx_qmy_functionals", C.c_int, [_H, c_double_p, c_double_p]),
+    ("pgx_qmy_cauchy", C.c_int, [_H, c_double_p]),
+    ("pgx_qmy_lu_stats", C.c_int, [_H, C.POINTER(pgx_nd_stats)]),
+    ("pgx_qmy_profile", C.c_int, [_H, C.c_int, c_double_p]),
     # example 08: intersecting constraints (include/pgx_ic.h)
     ("pgx_ic_create", C.c_int, [C.POINTER(pgx_ic_problem), C.c_int, C.POINTER(_H)]),
     ("pgx_ic_num_dofs", C.c_int, [_H, c_int64_p]),

@@ -154,6 +154,14 @@ int mx_spmv(MixedBase* h, const double* x, double* y);
 // every other value
 int mx_newton(MixedBase* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its, bool with_l2);
 int mx_profile(MixedBase* h, int enable, double ms[6]);
+// J dx = b with the factorisation lin_factor() left behind: sparse LU + iterative refinement on the exact operator Jv, GMRES
+// safeguard (o: ksp_rtol, ksp_max_it, monitor).  nsolves counts LU solves, relres is the true relative residual.
+int mx_linear_solve(MixedBase* h, const double* b, double* dx, const pgx_snes_opts* o, int* nsolves, double* relres);
+int mx_absmax(MixedBase* h, const double* v, double* out, int64_t len = 0);  // inf-norm, +inf if an entry is not finite
+int mx_partials_sum(MixedBase* h, const double* partials, double* out);      // sum of MX_RED partials of a family's reduction
+// NLsolve's `newton` with LineSearches.BackTracking(c_1 = c1) (examples/05_obstacle_type_qvi/solver_comparison/*.jl): see
+// pgx_mixed.hip.  reason: 1 ftol, 2 xtol, 0 max_it (not an error), -4 no finite trial; h->x is replaced in every case but -4.
+int mx_newton_nls(MixedBase* h, double ftol, double xtol, int max_it, double c1, int monitor, int* reason, int* its, int* lin_its);
 #pragma GCC visibility pop
 
 // pgx_xx_create*: device check, a new H on `device`, the family's impl(h); on failure `last_err` (what pgx_xx_last_error(NULL)

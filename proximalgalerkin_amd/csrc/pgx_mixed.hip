@@ -245,7 +245,7 @@ static int mx_linear_solve_ok(MixedBase* h, const double* b, const double* dx, d
 // J dx = b by the sparse LU + iterative refinement on the exact operator (the reference: ksp_type preonly + MUMPS).  The LU
 // does not pivot across nodes; where refinement alone cannot bring the true relative residual below 1e-7 (late, extremely
 // ill-conditioned steps on very fine meshes), the same LU preconditions a short GMRES on the exact operator.
-static int mx_linear_solve(MixedBase* h, const double* b, double* dx, const pgx_snes_opts* o, int* nsolves, double* relres) {
+int mx_linear_solve(MixedBase* h, const double* b, double* dx, const pgx_snes_opts* o, int* nsolves, double* relres) {
   double bnorm = 0, rnorm = 0, prev = 1e300;
   int rc = mx_norm(h, b, &bnorm);
   if (rc) return rc;
@@ -864,6 +864,138 @@ int mx_partials_sqrt(MixedBase* h, double* out, bool sync) {
   MXHIP(hipMemcpyAsync(h->h_out, h->d_out, sizeof(double), hipMemcpyDeviceToHost, h->st));
   MXHIP(hipStreamSynchronize(h->st));
   *out = std::sqrt(std::max(h->h_out[0], 0.0));
+  return PGX_OK;
+}
+
+int mx_partials_sum(MixedBase* h, const double* partials, double* out) {
+  hipLaunchKernelGGL(k_mx_final, dim3(1), dim3(256), 0, h->st, MX_RED, partials, h->d_out);
+  {
+    const int rcs = mx_sync_scalar(h);
+    if (rcs) return rcs;
+  }
+  MXHIP(hipMemcpyAsync(h->h_out, h->d_out, sizeof(double), hipMemcpyDeviceToHost, h->st));
+  MXHIP(hipStreamSynchronize(h->st));
+  *out = h->h_out[0];
+  return PGX_OK;
+}
+
+// max_i |v_i|, +inf as soon as one entry is not finite (fmax alone would drop a NaN); fixed-shape two-stage reduction
+static __global__ __launch_bounds__(256) void k_mx_absmax(int64_t len, const double* __restrict__ v, double* __restrict__ partials) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (int64_t)MX_RED * 256) {
+    const double a = fabs(v[i]);
+    s = a <= 1.79769313486231570815e308 ? fmax(s, a) : INFINITY;  // the comparison is false for a NaN too
+  }
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
+}
+int mx_absmax(MixedBase* h, const double* v, double* out, int64_t len) {
+  hipLaunchKernelGGL(k_mx_absmax, dim3(MX_RED), dim3(256), 0, h->st, len ? len : h->ntot, v, h->partials);
+  hipLaunchKernelGGL(k_mx_final_max, dim3(1), dim3(256), 0, h->st, MX_RED, h->partials, h->d_out);
+  {
+    const int rcs = mx_sync_scalar(h);
+    if (rcs) return rcs;
+  }
+  MXHIP(hipMemcpyAsync(h->h_out, h->d_out, sizeof(double), hipMemcpyDeviceToHost, h->st));
+  MXHIP(hipStreamSynchronize(h->st));
+  *out = h->h_out[0];
+  return PGX_OK;
+}
+
+// NLsolve's `newton` with LineSearches.BackTracking(c_1 = c1), as the comparison solvers of example 05 configure it
+// (examples/05_obstacle_type_qvi/solver_comparison/thermoforming_moreau_yosida.jl:130, thermoforming_fixed_point.jl:118-122)
+// [upstream, recalled, not checked against NLsolve's source; tests/thermoforming_comparison_reference.py::newton_nls restates
+// the same rules]:
+//   F = F(x); ||F||_inf <= ftol: converged with 0 iterations.
+//   repeat: J delta = -F by LU + refinement; lambda = 1; while F(x + lambda delta) has a non-finite entry or
+//     1/2 |F(x + lambda delta)|^2 > 1/2 |F|^2 + c1 lambda F . J delta: lambda /= 2 (at most 50 halvings); accept, ++it;
+//     stop on ||F||_inf <= ftol (reason 1) or ||lambda delta||_inf <= xtol (reason 2); stop at max_it (reason 0).
+// With the scripts' c1 = -1e8 the Armijo test never rejects a finite trial (F . J delta = -|F|^2 up to the linear solve's error):
+// only the non-finite guard shrinks lambda.  Reaching max_it is NOT an error - Gridap's solve! does not look at NLsolve's
+// convergence flag - and the last iterate replaces the state, as solve! updates the free values in place.
+int mx_newton_nls(MixedBase* h, double ftol, double xtol, int max_it, double c1, int monitor, int* reason, int* its_out,
+                  int* lin_out) {
+  MXNEED(h);
+  if (!reason) return PGX_EINVAL;
+  PgxSolveScope scope(h->st, h->prof, nullptr);
+  PgxRange range("pgx:newton_solve");
+  const size_t bytes = sizeof(double) * h->ntot;
+  pgx_snes_opts lo{};
+  pgx_default_opts(&lo);
+  // the scripts solve with a direct method (Julia's `\`): refine until the backward error is at the unit roundoff or stagnates
+  lo.ksp_rtol = 1e-15, lo.ksp_max_it = 6, lo.monitor = monitor > 1 ? 2 : 0;
+  int its = 0, lin = 0, rsn = -100, rc = PGX_OK;
+  double fnorm = 0, finf = 0;
+  h->stale_failed = false;
+  MXHIP(hipMemcpyAsync(h->xw, h->x, bytes, hipMemcpyDeviceToDevice, h->st));
+  h->residual_dev(h->xw, h->F);
+  if ((rc = mx_norm(h, h->F, &fnorm))) return rc;
+  if ((rc = mx_absmax(h, h->F, &finf))) return rc;
+  if (monitor) printf("  %5d  |F|_inf %.6e\n", 0, finf);
+  if (finf <= ftol) rsn = 1;
+  while (rsn == -100) {
+    if (its >= max_it) {
+      rsn = 0;
+      break;
+    }
+    h->jacobian_dev(h->xw);
+    {
+      MxTimer t(h, 2);
+      rc = h->lin_factor();
+    }
+    if (rc) {
+      h->err = std::string("direct solver: ") + h->lin_error();
+      return rc;
+    }
+    mx_axpby(h, -1.0, h->F, 0.0, h->rhs);
+    int ns = 0;
+    double relres = 0, slope = 0;
+    if ((rc = mx_linear_solve(h, h->rhs, h->dx, &lo, &ns, &relres))) return rc;
+    lin += ns;
+    mx_spmv_dev(h, h->dx, h->rhs);  // J delta
+    if ((rc = mx_dot(h, h->F, h->rhs, &slope))) return rc;
+    const double f0 = 0.5 * fnorm * fnorm;
+    double lam = 1.0, g = 0;
+    bool finite = false;
+    for (int halvings = 0;; ++halvings) {  // z = xw + lam delta ; r = F(z)
+      mx_axpby(h, 1.0, h->xw, 0.0, h->z);
+      mx_axpby(h, lam, h->dx, 1.0, h->z);
+      h->residual_dev(h->z, h->r);
+      if ((rc = mx_norm(h, h->r, &g))) return rc;
+      finite = std::isfinite(g);
+      if ((finite && !(0.5 * g * g > f0 + c1 * lam * slope)) || halvings >= 50) break;
+      lam *= 0.5;
+    }
+    if (!finite) {
+      rsn = -4;
+      break;
+    }
+    MXHIP(hipMemcpyAsync(h->xw, h->z, bytes, hipMemcpyDeviceToDevice, h->st));
+    MXHIP(hipMemcpyAsync(h->F, h->r, bytes, hipMemcpyDeviceToDevice, h->st));
+    fnorm = g;
+    ++its;
+    double sinf = 0;
+    if ((rc = mx_absmax(h, h->F, &finf))) return rc;
+    if ((rc = mx_absmax(h, h->dx, &sinf))) return rc;
+    if (monitor) printf("  %5d  |F|_inf %.6e  |step|_inf %.6e  lambda %.3e  (LU solves %d, rel residual %.1e)\n", its, finf, lam * sinf, lam, ns, relres);
+    if (finf <= ftol)
+      rsn = 1;
+    else if (lam * sinf <= xtol)
+      rsn = 2;
+  }
+  if (rsn != -4) MXHIP(hipMemcpyAsync(h->x, h->xw, bytes, hipMemcpyDeviceToDevice, h->st));
+  MXHIP(hipStreamSynchronize(h->st));
+  MXHIP(hipGetLastError());
+  if (h->prof) h->ms[5] += scope.stop();
+  *reason = rsn;
+  if (its_out) *its_out = its;
+  if (lin_out) *lin_out = lin;
   return PGX_OK;
 }
 
