@@ -204,6 +204,39 @@ int pgx_tuning_set(const char* key, const char* value);
  * 513^2 vertices) with it.  Same preconditions as pgx_smoother_bench. */
 int pgx_vcycle_bench(pgx_handle* h, int level, int reps, double* avg_ms, int* n_level);
 
+/* ---- Test hooks of the multigrid preconditioner.  They replace nothing in the reference (which factorises the Newton matrix with
+ * MUMPS, obstacle_pg.py:129-131, and has no multigrid cycle): like the pgx_nd_export_* family they exist so that tests can compare
+ * what the device stores and computes with a numpy statement of the same algebra (tests/vcycle_reference.py).  Preconditions of both:
+ * those of pgx_vcycle_bench - a structured single-GPU P1 handle with a hierarchy of at least two levels and a filled Jacobian, not
+ * sharded, the LU preconditioner not active; anything else is PGX_ESTATE with a message, and nothing is launched.  Neither changes
+ * how a solve runs: they read the buffers and make the calls that pgx_vcycle_bench and pgx_spmv_bench make. */
+/* Host copies of what multigrid level `level` (0 = finest .. the coarsest, levels inside the fused tail included) stores after the
+ * last pgx_jacobian_fill; every array may be NULL (sizes only: n = (*nx + 1) * (*ny + 1) vertices, v = j * (*nx + 1) + i).
+ *   Dh4  [4n]  the fp64 D(psi) stencil in its half-stored slot order S[slot * n + v], slots 0:(0,0) 1:(+1,0) 2:(0,+1) 3:(+1,+1)
+ *   Dq4  [4n]  the single-precision cycle's copy of it, decoded to four floats PER VERTEX in the same slot order, Dq4[4 v + slot]:
+ *              bf16 words shifted up (*dbf16 != 0), float4 copied; written only where *f32 != 0
+ *   mask [n]   1 = Dirichlet dof of the u block on this level
+ *   *f32, *dbf16   the level carries single-precision storage / stores Dq as bf16
+ * Copies only, after a synchronisation of the handle's stream.  PGX_EINVAL: no such level. */
+int pgx_mg_level_export(pgx_handle* h, int level, int32_t* nx, int32_t* ny, double* Dh4, float* Dq4, uint8_t* mask, int32_t* f32,
+                        int32_t* dbf16);
+/* z = ONE V(nu, nu) cycle for b, entered on `level` from a zero guess exactly as the solver enters it; b and z are host vectors
+ * [u | psi] of 2 n_level entries.  Level 0 runs through the preconditioner entry of FGMRES (right-hand side in the Krylov scratch,
+ * result in the operator scratch); a level > 0 whose single-precision legs run at this nu takes b as interleaved (u, psi) float
+ * pairs, converted on the host, and returns the float pairs widened; any other level > 0 - the first level of the fused tail
+ * included - takes and returns fp64.  Levels 0 .. the first tail level (the coarsest level where there is no fused tail); beyond:
+ * PGX_EINVAL.  On a level > 0 the u part of b must be 0 on that level's Dirichlet rows, as every restricted residual is (the fused
+ * tail relies on it); PGX_EINVAL otherwise.  On level 0 only:
+ *   in_form  0: the fp64 pair, multiplied by `scale` as the first launch reads it (FGMRES's lazily normalised basis vectors);
+ *            1: the pair of float fields of FGMRES's float basis (the hook converts b and owns the device copy)
+ *   out_form 0: fp64;  1: the interleaved float2 field FGMRES keeps as Z_j, widened - only on handles that run this form
+ *               (PGX_Z_F32 with the matrix-free apply and a single-precision level 0), otherwise PGX_ESTATE
+ * in_form 1 and scale != 1 need the single-precision cycle on level 0 (PGX_EINVAL otherwise: the fp64 cycle reads neither).  nu must
+ * be one the entered single-precision level runs (even, or a multiple of 3 with PGX_FUSED_K3): PGX_EINVAL otherwise, never another
+ * path.  The handle's input / output form state is back at its defaults on return, on every path. */
+int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, int in_form, int out_form, double scale, const double* b,
+                     double* z);
+
 /* One nonlinear solve from device `sol` with proximal centre `sol_k`; on reason>0 `sol` is replaced. */
 int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its);
 /* energy, |complementarity|, feasibility, dual feasibility, H1 increment, latent L2 increment */

@@ -3204,6 +3204,176 @@ extern "C" int pgx_vcycle_bench(pgx_handle* h, int level, int reps, double* avg_
   return PGX_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Test hooks (include/pgx.h): the stored multigrid operators of one level, and ONE V-cycle entered on one level, with the buffers and
+// the call sequence of pgx_vcycle_bench / pgx_spmv_bench.  They launch nothing of their own besides copies.
+// ------------------------------------------------------------------------------------------------
+static int mg_hook_ready(pgx_handle* h, const char* who) {
+  if (!h->jac_valid || !h->structured || h->lev.size() < 2 || h->dist.on || h->degree != 1 || h->lu_active) {
+    h->err = std::string(who) + " needs a structured single-GPU P1 handle with a grid hierarchy, a filled Jacobian and the multigrid preconditioner";
+    return PGX_ESTATE;
+  }
+  return PGX_OK;
+}
+
+extern "C" int pgx_mg_level_export(pgx_handle* h, int level, int* nx, int* ny, double* Dh4, float* Dq4, uint8_t* mask, int* f32,
+                                   int* dbf16) {
+  NEED(h);
+  {
+    const int rc = mg_hook_ready(h, "pgx_mg_level_export");
+    if (rc) return rc;
+  }
+  if (level < 0 || level >= (int)h->lev.size()) {
+    h->err = "pgx_mg_level_export: no such multigrid level";
+    return PGX_EINVAL;
+  }
+  const GridLevel& L = h->lev[level];
+  const size_t n = (size_t)L.n;
+  if (nx) *nx = L.nx;
+  if (ny) *ny = L.ny;
+  if (f32) *f32 = L.f32;
+  if (dbf16) *dbf16 = L.dbf16;
+  HIPCHK(hipStreamSynchronize(h->st));
+  if (Dh4) {
+    std::vector<dsten_t> tmp(4 * n);
+    HIPCHK(hipMemcpy(tmp.data(), L.Dh, sizeof(dsten_t) * 4 * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < 4 * n; ++i) Dh4[i] = (double)tmp[i];
+  }
+  if (Dq4 && L.f32 && L.Dq) {
+    if (L.dbf16) {  // two packed bf16 pairs per vertex: a bf16 word is the upper half of the float with the same value
+      std::vector<uint32_t> tmp(2 * n);
+      HIPCHK(hipMemcpy(tmp.data(), L.Dq, sizeof(uint32_t) * 2 * n, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < 2 * n; ++i) {
+        const uint32_t lo = tmp[i] << 16, hi = tmp[i] & 0xffff0000u;
+        memcpy(Dq4 + 2 * i, &lo, sizeof(float));
+        memcpy(Dq4 + 2 * i + 1, &hi, sizeof(float));
+      }
+    } else {
+      HIPCHK(hipMemcpy(Dq4, L.Dq, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+    }
+  }
+  if (mask) HIPCHK(hipMemcpy(mask, L.mask, n, hipMemcpyDeviceToHost));
+  return PGX_OK;
+}
+
+extern "C" int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, int in_form, int out_form, double scale, const double* b,
+                                double* z) {
+  NEED(h);
+  {
+    const int rc = mg_hook_ready(h, "pgx_vcycle_apply");
+    if (rc) return rc;
+  }
+  const int nl = (int)h->lev.size();
+  const int lmax = h->tail_start > 0 ? h->tail_start : nl - 1;
+  if (!b || !z || nu < 1 || level < 0 || level > lmax || (in_form != 0 && in_form != 1) || (out_form != 0 && out_form != 1)) {
+    h->err = "pgx_vcycle_apply: bad argument (levels 0 .. the first level of the fused tail, forms 0 or 1, nu >= 1)";
+    return PGX_EINVAL;
+  }
+  GridLevel& L = h->lev[level];
+  const size_t n = (size_t)L.n;
+  const bool f32 = f32_cycle_ok(h, level, nu);
+  if (L.f32 && h->fused_legs && level + 1 < nl && !f32) {
+    h->err = "pgx_vcycle_apply: the single-precision legs of this level need an even nu, or a multiple of 3 with PGX_FUSED_K3";
+    return PGX_EINVAL;
+  }
+  if ((in_form != 0 || out_form != 0 || scale != 1.0) && level != 0) {
+    h->err = "pgx_vcycle_apply: input / output forms and the scale factor exist on level 0 only";
+    return PGX_EINVAL;
+  }
+  if ((in_form != 0 || scale != 1.0) && !f32) {
+    h->err = "pgx_vcycle_apply: the float right-hand side and the scale factor are read by the single-precision cycle only";
+    return PGX_EINVAL;
+  }
+  if (out_form == 1 && !z_f32_active(h, nu)) {
+    h->err = "pgx_vcycle_apply: the float2 result needs the handle's float2 Z storage (PGX_Z_F32, matrix-free apply, single-precision level 0)";
+    return PGX_ESTATE;
+  }
+  if (level == 0) {
+    // as fgmres / pgx_spmv_bench enter the preconditioner: right-hand side in h->rhs, result in h->w or, float2, at the head of h->Z
+    int rc = copy_in(h, h->rhs, b);
+    if (rc) return rc;
+    float* b32 = nullptr;
+    if (in_form == 1) {
+      std::vector<float> hb(2 * n);
+      for (size_t i = 0; i < 2 * n; ++i) hb[i] = (float)b[i];
+      if (hipMalloc(&b32, sizeof(float) * 2 * n) != hipSuccess) {
+        h->err = "pgx_vcycle_apply: out of device memory";
+        return PGX_ENOMEM;
+      }
+      if (hipMemcpy(b32, hb.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(b32);
+        h->err = "pgx_vcycle_apply: copy of the float right-hand side failed";
+        return PGX_EHIP;
+      }
+    }
+    float2* const zf = out_form == 1 ? reinterpret_cast<float2*>(h->Z) : nullptr;
+    h->rhs_scale = scale;
+    h->rhs_f32 = b32;
+    h->zf_out = zf;
+    rc = precond(h, h->rhs, h->w, nu, omega);
+    h->rhs_scale = 1.0;
+    h->rhs_f32 = nullptr;
+    h->zf_out = nullptr;
+    hipError_t e = hipStreamSynchronize(h->st);
+    if (e == hipSuccess) e = hipGetLastError();
+    std::vector<float2> hz;
+    if (!rc && e == hipSuccess && zf) {
+      hz.resize(n);
+      e = hipMemcpy(hz.data(), zf, sizeof(float2) * n, hipMemcpyDeviceToHost);
+    }
+    if (b32) (void)hipFree(b32);
+    if (rc) return rc;
+    if (e != hipSuccess) {
+      h->err = std::string("pgx_vcycle_apply: ") + hipGetErrorString(e);
+      return PGX_EHIP;
+    }
+    if (zf) {
+      for (size_t i = 0; i < n; ++i) {
+        z[i] = (double)hz[i].x;
+        z[n + i] = (double)hz[i].y;
+      }
+      return PGX_OK;
+    }
+    return copy_out(h, z, h->w);
+  }
+  {
+    // a level below the finest only ever sees restricted residuals, whose u entries are 0 on Dirichlet rows (k_restrict and its fused
+    // forms mask them), and the fused tail relies on it (k_mg_tail2 does not mask Dirichlet columns): anything else is not a state the
+    // solver can be in
+    std::vector<uint8_t> hm(n);
+    HIPCHK(hipMemcpy(hm.data(), L.mask, n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i)
+      if (hm[i] && b[i] != 0.0) {
+        h->err = "pgx_vcycle_apply: on a level below the finest the u part of b must be 0 on Dirichlet rows (what every restriction delivers)";
+        return PGX_EINVAL;
+      }
+  }
+  if (f32) {  // a single-precision level below the finest: float2 right-hand side in L.bf, the correction in the buffer vcycle_f returns
+    std::vector<float2> hb(n);
+    for (size_t i = 0; i < n; ++i) hb[i] = make_float2((float)b[i], (float)b[n + i]);
+    HIPCHK(hipMemcpyAsync(L.bf, hb.data(), sizeof(float2) * n, hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    const float2* const res = vcycle_f(h, level, nullptr, nullptr, nullptr, nullptr, nu, omega);
+    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(hb.data(), res, sizeof(float2) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+      z[i] = (double)hb[i].x;
+      z[n + i] = (double)hb[i].y;
+    }
+    return PGX_OK;
+  }
+  HIPCHK(hipMemcpyAsync(L.bu, b, sizeof(double) * n, hipMemcpyHostToDevice, h->st));
+  HIPCHK(hipMemcpyAsync(L.bp, b + n, sizeof(double) * n, hipMemcpyHostToDevice, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  vcycle(h, level, L.bu, L.bp, L.xu, L.xp, nu, omega);
+  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(z, L.xu, sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(z + n, L.xp, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return PGX_OK;
+}
+
 static int spmv_bench_impl(pgx_handle* h, int reps, double* avg_ms, double* bytes, bool cold) {
   NEED(h);
   if (reps < 1 || !avg_ms) return PGX_EINVAL;

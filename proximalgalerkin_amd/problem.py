@@ -362,6 +362,55 @@ class NonlinearProblem:
                    "pgx_vcycle_bench")
         return ms.value, nl.value
 
+    def _check_code(self, rc, what):
+        """_lib.check whose PgxError carries the PGX_E* code as `.code` (the tests of the refusals read it)."""
+        try:
+            _lib.check(self._lib, self._h, rc, what)
+        except _lib.PgxError as e:
+            e.code = rc
+            raise
+
+    def mg_levels(self):
+        """Number of levels pgx_mg_level_export serves (the call refuses the first level that does not exist)."""
+        nx, ny, f, d = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        l = 0
+        while self._lib.pgx_mg_level_export(self._h, l, C.byref(nx), C.byref(ny), None, None, None, C.byref(f), C.byref(d)) == 0:
+            l += 1
+        if l == 0:
+            self.mg_level_export(0)  # raises with the library's message
+        return l
+
+    def mg_level_export(self, level):
+        """What multigrid level `level` stores after the last assemble_jacobian (include/pgx.h: pgx_mg_level_export; a test hook):
+        dict(nx, ny, Dh [4, n] fp64 half-stored D stencil, Dq [n, 4] float32 decoded copy of the single-precision cycle or None,
+        mask [n] bool, f32, dbf16)."""
+        lib = self._lib
+        nx, ny, f, d = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check_code(lib.pgx_mg_level_export(self._h, int(level), C.byref(nx), C.byref(ny), None, None, None, C.byref(f), C.byref(d)),
+                         "pgx_mg_level_export")
+        n = (nx.value + 1) * (ny.value + 1)
+        Dh = np.empty((4, n))
+        Dq = np.zeros((n, 4), dtype=np.float32) if f.value else None
+        mask = np.empty(n, dtype=np.uint8)
+        self._check_code(lib.pgx_mg_level_export(self._h, int(level), C.byref(nx), C.byref(ny), _lib.dptr(Dh),
+                                                 None if Dq is None else Dq.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(f), C.byref(d)), "pgx_mg_level_export")
+        return dict(nx=nx.value, ny=ny.value, Dh=Dh, Dq=Dq, mask=mask.astype(bool), f32=f.value, dbf16=d.value)
+
+    def vcycle_apply(self, level, b, nu=6, omega=0.75, in_form=0, out_form=0, scale=1.0):
+        """One V(nu, nu) cycle entered on multigrid level `level` from a zero guess, b and the result [u | psi] of that level
+        (include/pgx.h: pgx_vcycle_apply; a test hook)."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        z = np.empty_like(b)
+        nx, ny = C.c_int32(0), C.c_int32(0)
+        self._check_code(self._lib.pgx_mg_level_export(self._h, int(level), C.byref(nx), C.byref(ny), None, None, None, None, None),
+                         "pgx_vcycle_apply")
+        if b.shape != (2 * (nx.value + 1) * (ny.value + 1),):
+            raise ValueError(f"b must hold [u | psi] of level {level}: {2 * (nx.value + 1) * (ny.value + 1)} entries")
+        self._check_code(self._lib.pgx_vcycle_apply(self._h, int(level), int(nu), float(omega), int(in_form), int(out_form), float(scale),
+                                                    _lib.dptr(b), _lib.dptr(z)), "pgx_vcycle_apply")
+        return z
+
     def observables(self):
         """[energy, |complementarity|, feasibility, dual feasibility, H1 increment, latent L2 increment]
         of obstacle_pg.py:145-152,196-201 in one device pass."""
