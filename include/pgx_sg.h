@@ -1,6 +1,6 @@
 /*
- * pgx_sg.h - C ABI of libpgx.so for the LVPP Newton inner loop of example 02 (Signorini contact of a 3-D linear-elastic
- * body with a rigid plane; latent variable on the contact surface): everything below `solver.solve()` in
+ * pgx_sg.h - C ABI of libpgx.so for the LVPP Newton inner loop of example 02 (Signorini contact of a 3-D - or, through
+ * pgx_sg_create_2d below, plane - linear-elastic body with a rigid plane; latent variable on the contact surface): everything below `solver.solve()` in
  * examples/02_signorini/signorini_dolfinx.py:333, i.e. what the reference delegates to DOLFINx assembly (cell + exterior
  * facet integrals on a submesh, :199-249) + PETSc SNES (newtonls, linesearch none) + MUMPS LU (:271-291).
  *
@@ -65,6 +65,48 @@ typedef struct {
 } pgx_sg_problem;
 
 int pgx_sg_create(const pgx_sg_mesh* mesh, const pgx_sg_problem* prob, int device, pgx_sg_handle** out);
+/* PLANE PROBLEMS: the script with gdim = 2 (`native --dim 2`: create_unit_square(nx, ny, quadrilateral), :376-380; `file`: the half disk
+ * of lvpp.mesh_generation.create_half_disk).  Every expression of the script is written against gdim, so
+ *        x = [u_x (nv) | u_y (nv) | psi (one per contact node, ordered by node id)],   n_g = -e_y,  g = x_y - gap,  f = 0,
+ * Jacobian [[alpha A, +M_G],[-M_G, D(psi)]], BC dofs component * n_nodes + node, and mu, lambda EXACTLY the script's (:234-235) - the
+ * plane-strain operator; plane-stress constants are NOT substituted.  pgx_sg_create_2d returns the same pgx_sg_handle: every call
+ * below works on it with gdim = 2 (pgx_sg_violation: -u_y - (y - gap); pgx_sg_u_increment: over the 2 nv displacement dofs).
+ * pgx_sg_create_dist and pgx_sg_create_curved stay 3-D ONLY: there is no distributed and no curved plane handle.
+ *
+ * Elements, all on AFFINE cells (PGX_EINVAL otherwise: straight-sided triangles with their edge nodes at the midpoints;
+ * quadrilaterals must be parallelograms with their nodes on the lattice, as the hexahedral path requires parallelepipeds):
+ *   cell_type 0, degree 1:  cells [n_cells][3];  contact edges [n_facets][2]
+ *   cell_type 0, degree 2:  cells [n_cells][6]: 3 vertices, then the edge nodes of (0,1) (0,2) (1,2) - the 3-D facet convention; basis
+ *                           L_a (2 L_a - 1), 4 L_a L_b;  contact edges [n_facets][3]: the two vertices, then the midpoint node; basis on
+ *                           t in [0,1]: (1 - t)(1 - 2t), t (2t - 1), 4 t (1 - t)
+ *   cell_type 1, degree 1:  cells [n_cells][4], local nodes lexicographic (xi fastest);  contact edges [n_facets][2]
+ *   cell_type 1, degree 2:  cells [n_cells][9], lexicographic, tensor Lagrange on the nodes k/2 as the hexahedral path;  contact edges
+ *                           [n_facets][3], lexicographic (end, midpoint, end)
+ * n_vertices counts the NODES of the discretisation, coords holds all of them.  Quadrature: contact edges - the caller's rule on
+ * [0,1] (weights sum to 1; the binding passes basix's default for the script's quadrature_degree: Gauss-Legendre with
+ * (degree + 2) / 2 points, 3 at the default 4); the edge length is the surface element.  Cells - triangles: the centroid (degree 1,
+ * constant integrand) / the 3-point degree-2 rule (1/6,1/6) (2/3,1/6) (1/6,2/3), weights 1/6 (degree 2: exact, gradients are affine);
+ * quadrilaterals: Gauss-Legendre (d + 1)^2 on the unit square.  (UFL's own estimate of the cell degree on quadrilaterals is not
+ * reproduced: the rule here is exact for Q1 and Q2 on parallelograms.) */
+typedef struct {
+  int32_t n_vertices, n_cells;
+  const double* coords;    /* [n_vertices][2] */
+  const int32_t* cells;    /* [n_cells][3 | 6 | 4 | 9] */
+  int32_t n_facets;        /* potential-contact edges */
+  const int32_t* facets;   /* [n_facets][2 | 3] node ids */
+  int32_t degree;          /* 0 or 1: degree 1; 2: degree 2 */
+  int32_t cell_type;       /* 0: triangles, 1: quadrilaterals */
+} pgx_sg_mesh2d;
+typedef struct {
+  double E, nu, gap;
+  int32_t nq;              /* edge quadrature, <= 16 points */
+  const double* qpts;      /* [nq] on [0,1] */
+  const double* qwts;      /* [nq], sum 1 */
+  int32_t n_bc;            /* Dirichlet dofs of u: component * n_vertices + node, component 0 or 1 */
+  const int32_t* bc_dofs;
+  const double* bc_vals;   /* NULL = homogeneous */
+} pgx_sg_problem2d;
+int pgx_sg_create_2d(const pgx_sg_mesh2d* mesh, const pgx_sg_problem2d* prob, int device, pgx_sg_handle** out);
 /* ORDER-2 GEOMETRY (round 5): the reference's half sphere is a mesh of 10-node tetrahedra (src/lvpp/mesh_generation.py:88,158
  * `order=2`) and DOLFINx integrates on the curved cells.  With pgx_sg_mesh.degree = 2 the ten nodes of a cell ARE its geometry nodes
  * (`coords` of an edge node = the mesh's mid-edge node instead of the midpoint): the discretisation is isoparametric P2; with degree 1
@@ -118,10 +160,11 @@ int pgx_sg_u_increment(pgx_sg_handle* h, double* out);
 /* sqrt( int_Gamma max(u.n_g - g, 0)^2 ds ), n_g = -e_z, g = x_z - gap, with the facet rule of pgx_sg_problem (:307-314); curved handles:
  * surface element and z from pgx_sg_curved.facet_geo.  Fixed-shape reduction: bitwise reproducible. */
 int pgx_sg_penetration(pgx_sg_handle* h, double* l2);
-/* u.n_g - g = -u_z - (z - gap) at every node (Expression at V's interpolation points, :307-308, 349) */
+/* u.n_g - g = -u_z - (z - gap) (plane handles: -u_y - (y - gap)) at every node (Expression at V's interpolation points, :307-308, 349) */
 int pgx_sg_violation(pgx_sg_handle* h, double* out /* [n_nodes] */);
 /* sqrt(3/2 s:s), s = sigma(u) - tr(sigma(u))/3 I, at the cell's own nodes = DG_degree interpolation (:296-302, 346).  Affine cells of all
- * four element flavours.  LIMITATION: PGX_EINVAL on a handle of pgx_sg_create_curved - it holds the cell geometry at the quadrature
+ * four element flavours.  Plane handles: the SCRIPT'S expression with len(u) = 2, i.e. the 2 x 2 sigma and
+ * s = sigma - tr(sigma)/3 I_2 (:300-301) - this is NOT the plane-strain von Mises stress (no sigma_zz, and the 1/3 stays).  LIMITATION: PGX_EINVAL on a handle of pgx_sg_create_curved - it holds the cell geometry at the quadrature
  * points only, not at the nodes. */
 int pgx_sg_von_mises(pgx_sg_handle* h, double* out /* [n_cells][nodes per cell], the node order of pgx_sg_mesh.cells */);
 int pgx_sg_profile(pgx_sg_handle* h, int enable, double ms[6]);

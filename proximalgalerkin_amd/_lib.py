@@ -175,6 +175,14 @@ class pgx_sg_problem(C.Structure):
     ]
 
 
+class pgx_sg_mesh2d(C.Structure):  # include/pgx_sg.h: plane problems (pgx_sg_create_2d); coords [n][2], facets are edges
+    _fields_ = list(pgx_sg_mesh._fields_)
+
+
+class pgx_sg_problem2d(C.Structure):  # qpts [nq] on [0, 1]
+    _fields_ = list(pgx_sg_problem._fields_)
+
+
 class pgx_sg_curved(C.Structure):  # include/pgx_sg.h: order-2 geometry of a mesh of 10-node tetrahedra
     _fields_ = [
         ("nq", C.c_int32),
@@ -431,6 +439,7 @@ SYMBOLS = [
      [_H, C.POINTER(pgx_gc_points), c_double_p, c_double_p, c_double_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     # example 02: Signorini contact (include/pgx_sg.h)
     ("pgx_sg_create", C.c_int, [C.POINTER(pgx_sg_mesh), C.POINTER(pgx_sg_problem), C.c_int, C.POINTER(_H)]),
+    ("pgx_sg_create_2d", C.c_int, [C.POINTER(pgx_sg_mesh2d), C.POINTER(pgx_sg_problem2d), C.c_int, C.POINTER(_H)]),
     ("pgx_sg_create_dist", C.c_int, [C.POINTER(pgx_sg_mesh), C.POINTER(pgx_sg_problem), _COMM, C.c_int, C.POINTER(_H)]),
     ("pgx_sg_create_curved", C.c_int, [C.POINTER(pgx_sg_mesh), C.POINTER(pgx_sg_problem), C.POINTER(pgx_sg_curved), C.c_int, C.POINTER(_H)]),
     ("pgx_sg_partition_info", C.c_int, [_H, c_int64_p, c_int64_p]),

@@ -6,52 +6,15 @@
 // value array Jc of the mixed CSR pattern: the elasticity block A (constant-strain tetrahedra, 144 entries per cell) and
 // the facet mass coupling +-M_G.  A residual is then one row-parallel pass over Jc (deterministic, no atomics) plus a
 // facet kernel for the exp term; a Jacobian is "scale the A slots by alpha" plus 9 entries of D(psi) per contact facet.
+//
+// The handle lives in pgx_sg_internal.h: pgx_sg_create_2d (pgx_sg2d.hip) builds the same handle with gdim = 2, and the entry points
+// below dispatch the element kernels on h->gdim; k_sg_jac_init and k_sg_resid_rows serve both (they depend on nu = gdim * nv only).
 #include <cstring>
 
-#include "../../include/pgx_sg.h"
-#include "pgx_mixed.h"
-#include "pgx_scatter.h"
+#include "pgx_sg_internal.h"
 
-#define SG_MAXQ 16
-struct SgQuad {
-  double L[SG_MAXQ][3], w[SG_MAXQ];
-  double N[SG_MAXQ][9];  // facet basis at the quadrature points: P1 = L; P2 = L_a (2 L_a - 1), then 4 L_a L_b for (0,1) (0,2) (1,2);
-                         // quadrilateral facets: tensor Lagrange basis, lexicographic
-  int nq;
-  int g[3];              // local nodes spanning the (affine) facet: x = X[g0] + xi (X[g1] - X[g0]) + eta (X[g2] - X[g0])
-};
-
-static thread_local std::string g_sg_error;
+thread_local std::string g_sg_error;
 static thread_local const pgx_sg_curved* g_sg_curved = nullptr;  // set by pgx_sg_create_curved around sg_create
-
-struct pgx_sg_handle : MixedBase {
-  int nv = 0, nc = 0, nf = 0, npsi = 0;  // nv = number of NODES (degree 2: vertices + edge midpoints)
-  int npc = 4, npf = 3;                  // nodes per cell / per contact facet: 4 / 3 (degree 1), 10 / 6 (degree 2)
-  SgQuad Q{};
-  double gap = 0.0, mu = 0.0, lmbda = 0.0;
-  double *coords = nullptr, *gbc = nullptr, *bg = nullptr;
-  double* fgeo = nullptr;  // order-2 geometry (pgx_sg_create_curved): [facet][point][2] = surface element, z of the curved facet; else nullptr
-  int32_t *facets = nullptr, *fpsi = nullptr;
-  // deterministic facet assembly (pgx_scatter.h): k_sg_exp parks [slot * nf + facet]; one thread per destination sums
-  PgxScatter sc_D, sc_b;  // D(psi): 9 slots per facet -> CSR positions; <exp(psi), w>: 3 slots per facet -> residual rows
-  double* stash = nullptr;  // [9 * nf]
-  uint8_t *mask = nullptr, *kind = nullptr;
-  double* Jc = nullptr;
-  std::vector<int32_t> cverts;
-  bool partitioned = false;  // distributed handle: this rank assembled the elasticity blocks of its slab of cells only
-  int nc_owned = 0;
-  // diagnostics (pgx_sg_penetration / violation / von_mises): ALL cells of the mesh, the reference gradients of the cell basis at the
-  // cell's own reference nodes [npc][npc][3], the four local nodes spanning the affine cell, and an output buffer grown on demand
-  int32_t* cells = nullptr;
-  double* vm_tab = nullptr;
-  int vm_g[4] = {0, 1, 2, 3};
-  bool curved = false;
-  double* diag = nullptr;
-  size_t diag_len = 0;
-  pgx_sg_handle() : MixedBase("pgx_sg") {}
-  void residual_dev(const double* xin, double* Fout) override;
-  void jacobian_dev(const double* xin) override;
-};
 
 extern "C" const char* pgx_sg_last_error(const pgx_sg_handle* h) { return h ? h->err.c_str() : g_sg_error.c_str(); }
 
@@ -488,11 +451,13 @@ extern "C" void pgx_sg_destroy(pgx_sg_handle* h) { mx_destroy(h); }
 void pgx_sg_handle::residual_dev(const double* xin, double* Fout) {
   pgx_sg_handle* h = this;
   MxTimer t(h, 0);
-  const int nu = 3 * h->nv;
+  const int nu = h->gdim * h->nv;
   hipLaunchKernelGGL(k_sg_resid_rows, dim3((unsigned)((h->ntot * 16 + 255) / 256)), dim3(256), 0, h->st, h->ntot, nu, h->rowptr,
                      h->col, h->Jc, h->mask, h->gbc, h->bg, xin, h->xk, h->alpha, Fout);
   if (h->nf > 0) {
-    if (h->npf == 6)
+    if (h->gdim == 2)
+      sg2d_exp(h, 1, xin);
+    else if (h->npf == 6)
       hipLaunchKernelGGL(k_sg_exp<6>, dim3((h->nf + 127) / 128), dim3(128), 0, h->st, 1, h->nf, nu, h->facets, h->fpsi, h->coords, xin,
                          h->Q, h->stash, h->fgeo);
     else if (h->npf == 4)
@@ -513,7 +478,9 @@ void pgx_sg_handle::jacobian_dev(const double* xin) {
   hipLaunchKernelGGL(k_sg_jac_init, dim3((unsigned)((h->nnz + 255) / 256)), dim3(256), 0, h->st, h->nnz, h->kind, h->Jc,
                      h->alpha, h->Jv);
   if (h->nf > 0) {
-    if (h->npf == 6)
+    if (h->gdim == 2)
+      sg2d_exp(h, 0, xin);
+    else if (h->npf == 6)
       hipLaunchKernelGGL(k_sg_exp<6>, dim3((h->nf + 127) / 128), dim3(128), 0, h->st, 0, h->nf, 3 * h->nv, h->facets, h->fpsi,
                          h->coords, xin, h->Q, h->stash, h->fgeo);
     else if (h->npf == 4)
@@ -528,17 +495,6 @@ void pgx_sg_handle::jacobian_dev(const double* xin) {
     pgx_scatter_run(h->st, h->sc_D, h->stash, 1.0, 1, h->Jv);
   }
   h->jac_valid = true;
-}
-
-// 1-D Lagrange basis on the equispaced nodes k / d (d = 1, 2): values l[0..d] and derivatives dl[0..d] at t
-static void sg_lagrange1d(int d, double t, double* l, double* dl) {
-  if (d == 1) {
-    l[0] = 1.0 - t, l[1] = t;
-    dl[0] = -1.0, dl[1] = 1.0;
-  } else {
-    l[0] = 2.0 * (t - 0.5) * (t - 1.0), l[1] = -4.0 * t * (t - 1.0), l[2] = 2.0 * t * (t - 0.5);
-    dl[0] = 4.0 * t - 3.0, dl[1] = 4.0 - 8.0 * t, dl[2] = 4.0 * t - 1.0;
-  }
 }
 
 // NPC / NPF: nodes per cell / per contact facet: tetrahedra 4 / 3 (degree 1), 10 / 6 (degree 2); hexahedra 8 / 4 (Q1), 27 / 9 (Q2).
@@ -1074,7 +1030,7 @@ extern "C" int pgx_sg_u_increment(pgx_sg_handle* h, double* out) {
   if (!out) return PGX_EINVAL;
   mx_axpby(h, 1.0, h->x, 0.0, h->r);
   mx_axpby(h, -1.0, h->xk, 1.0, h->r);
-  return mx_norm(h, h->r, out, 3 * (int64_t)h->nv);
+  return mx_norm(h, h->r, out, h->gdim * (int64_t)h->nv);
 }
 
 // grows the diagnostics' output buffer (kept until the handle is destroyed)
@@ -1089,7 +1045,9 @@ extern "C" int pgx_sg_penetration(pgx_sg_handle* h, double* l2) {
   MXNEED(h);
   if (!l2) return PGX_EINVAL;
   const dim3 g(MX_RED), b(256);
-  if (h->npf == 6)
+  if (h->gdim == 2)
+    sg2d_penetration(h);
+  else if (h->npf == 6)
     hipLaunchKernelGGL(k_sg_penetration<6>, g, b, 0, h->st, h->nf, h->nv, h->facets, h->coords, h->x, h->gap, h->Q, h->fgeo, h->partials);
   else if (h->npf == 4)
     hipLaunchKernelGGL(k_sg_penetration<4>, g, b, 0, h->st, h->nf, h->nv, h->facets, h->coords, h->x, h->gap, h->Q, h->fgeo, h->partials);
@@ -1103,7 +1061,10 @@ extern "C" int pgx_sg_violation(pgx_sg_handle* h, double* out) {
   MXNEED(h);
   if (!out) return PGX_EINVAL;
   if (const int rc = sg_diag_buffer(h, (size_t)h->nv)) return rc;
-  hipLaunchKernelGGL(k_sg_violation, dim3((h->nv + 255) / 256), dim3(256), 0, h->st, h->nv, h->coords, h->x, h->gap, h->diag);
+  if (h->gdim == 2)
+    sg2d_violation(h, h->diag);
+  else
+    hipLaunchKernelGGL(k_sg_violation, dim3((h->nv + 255) / 256), dim3(256), 0, h->st, h->nv, h->coords, h->x, h->gap, h->diag);
   MXHIP(hipMemcpyAsync(out, h->diag, sizeof(double) * (size_t)h->nv, hipMemcpyDeviceToHost, h->st));
   MXHIP(hipStreamSynchronize(h->st));
   return PGX_OK;
@@ -1119,7 +1080,9 @@ extern "C" int pgx_sg_von_mises(pgx_sg_handle* h, double* out) {
   if (const int rc = sg_diag_buffer(h, len)) return rc;
   const dim3 g((h->nc + 63) / 64), b(64);
   const int* vg = h->vm_g;
-  if (h->npc == 10)
+  if (h->gdim == 2)
+    sg2d_von_mises(h, h->diag);
+  else if (h->npc == 10)
     hipLaunchKernelGGL(k_sg_von_mises<10>, g, b, 0, h->st, h->nc, h->nv, h->cells, h->coords, h->x, h->mu, h->lmbda, h->vm_tab, vg[0], vg[1],
                        vg[2], vg[3], h->diag);
   else if (h->npc == 8)

@@ -9,12 +9,14 @@ the kind DOLFINx writes are read and written by proximalgalerkin_amd/h5.py, resu
     read_xdmf(path, name)               XDMF with the heavy data in HDF5 (DOLFINx's default: read through the pure-Python reader
                                         proximalgalerkin_amd/h5.py - contiguous, unfiltered datasets, default format bounds) or
                                         INLINE (dolfinx.io.XDMFFile(..., encoding=XDMFFile.Encoding.ASCII))
+    read_tri_mesh / write_xdmf_tri      (fem.Mesh, MeshTags of tagged boundary EDGES) - the plane twins of read_tet_mesh / write_xdmf_tet
+                                        (example 02 with gdim = 2: the half disk); order-2 triangle files are FLATTENED to their vertices
     read_mesh(path) / read_tet_mesh     -> fem.Mesh / (TetMesh, MeshTags) from either format; ORDER-2 geometry (generate_mesh_gmsh.py:31,
                                         mesh_generation.py:88,158): 6-node triangles keep their mid-side nodes (`mesh.midside`:
                                         curved cells in example 01), 10-node tetrahedra their mid-edge nodes
                                         (`TetMesh.midside`: isoparametric P2 in example 02)
     write_vtu(path, points, cells, ...) VTK unstructured grid (XML, ASCII) with point / cell data; linear and quadratic
-                                        triangles, linear tetrahedra
+                                        triangles, linear tetrahedra, hexahedra, quadrilaterals
 """
 from __future__ import annotations
 
@@ -25,7 +27,7 @@ import numpy as np
 # gmsh element type -> (name, nodes)
 _GMSH = {1: ("line", 2), 2: ("triangle", 3), 4: ("tetra", 4), 8: ("line3", 3), 9: ("triangle6", 6), 11: ("tetra10", 10),
          15: ("vertex", 1)}
-_VTK = {"triangle": 5, "triangle6": 22, "tetra": 10, "line": 3, "vertex": 1, "hexahedron": 12}
+_VTK = {"triangle": 5, "triangle6": 22, "tetra": 10, "line": 3, "vertex": 1, "hexahedron": 12, "quad": 9}
 
 
 def read_msh(path):
@@ -259,6 +261,65 @@ def read_tet_mesh(path, name: str = "mesh", tags_name: str = "facet_tags"):
     return mesh, MeshTags(tagged_facets)
 
 
+def read_tri_mesh(path, name: str = "mesh", tags_name: str = "facet_tags"):
+    """(fem.Mesh, MeshTags) of example 02's `file` branch in the plane (signorini_dolfinx.py:406-409 on the half disk of
+    lvpp/mesh_generation.py:11-83): triangles and tagged boundary EDGES (vertex pairs; `MeshTags.find(tag)` -> (m, 2)) from an
+    inline-data XDMF file with a `facet_tags` grid of line cells, or a gmsh .msh file with tagged line elements.  NOTE: an order-2
+    file (6-node triangles, 3-node lines) is FLATTENED to its vertices - plane contact on curved cells is not implemented."""
+    from .signorini import MeshTags
+
+    path = Path(path)
+    if path.suffix.lower() == ".xdmf":
+        pts, cells, tagged = read_xdmf(path, name)
+        if tags_name not in tagged:
+            raise KeyError(f"{path}: no meshtags grid {tags_name!r} (found {sorted(tagged)})")
+        tname, econn, eval_ = tagged[tags_name]
+    else:
+        pts, cells, tags = read_msh(path)
+        tname = "line" if "line" in cells else "line3"
+        if tname not in cells:
+            raise KeyError(f"{path}: no line elements (the tagged boundary edges)")
+        econn, eval_ = cells[tname], tags[tname]
+    if tname not in ("line", "line3"):
+        raise ValueError(f"{path}: {tags_name!r} holds {tname} cells; a plane mesh is tagged on its edges (use read_tet_mesh for 3-D files)")
+    if "triangle" not in cells and "triangle6" not in cells:
+        raise ValueError(f"{path}: no triangles (use read_tet_mesh for 3-D files)")
+    tri = np.asarray(cells["triangle"] if "triangle" in cells else cells["triangle6"])[:, :3]
+    used = np.unique(tri)  # the compact vertex numbering of _triangles
+    remap = np.full(len(pts), -1, dtype=np.int64)
+    remap[used] = np.arange(len(used))
+    mesh = _triangles(pts, cells).flattened()
+    edges = remap[np.asarray(econn)[:, :2]]
+    if np.any(edges < 0):
+        raise ValueError(f"{path}: a tagged edge uses a node that is no vertex of a triangle")
+    return mesh, MeshTags({int(t): np.ascontiguousarray(edges[eval_ == t], dtype=np.int32) for t in np.unique(eval_) if t != 0}, width=2)
+
+
+def write_xdmf_tri(path, mesh, facet_tags, tags=None, name: str = "mesh", tags_name: str = "facet_tags"):
+    """XDMFFile.write_mesh + write_meshtags of `examples/02_signorini/generate_mesh.py:13-17` for a triangular fem.Mesh and its tagged
+    boundary edges - a MeshTags or the {marker: vertex pairs} dict of `mesh_generation.create_half_disk` - with inline data items
+    (affine cells: a curved mesh is written by its vertices)."""
+    path = Path(path)
+    p, t = np.asarray(mesh.geometry), np.asarray(mesh.cells)
+    find = facet_tags.find if hasattr(facet_tags, "find") else (lambda k: facet_tags[k])
+    tags = sorted(facet_tags._t if hasattr(facet_tags, "_t") else facet_tags) if tags is None else list(tags)
+    ec = [np.asarray(find(k)).reshape(-1, 2) for k in tags]
+    alle = np.concatenate(ec) if ec else np.zeros((0, 2), dtype=np.int32)
+    vals = np.concatenate([np.full(len(e), k) for e, k in zip(ec, tags)]) if ec else np.zeros(0, dtype=np.int64)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w") as f:
+        f.write('<?xml version="1.0"?>\n<Xdmf Version="3.0"><Domain>\n<Grid Name="%s" GridType="Uniform">\n' % name)
+        f.write('<Topology TopologyType="Triangle" NumberOfElements="%d" NodesPerElement="3">\n<DataItem Dimensions="%d 3" NumberType="Int" '
+                'Format="XML">\n%s\n</DataItem></Topology>\n' % (len(t), len(t), "\n".join(" ".join(map(str, c)) for c in t)))
+        f.write('<Geometry GeometryType="XY"><DataItem Dimensions="%d 2" Format="XML">\n%s\n</DataItem></Geometry>\n</Grid>\n'
+                % (len(p), "\n".join("%.17g %.17g" % tuple(x) for x in p)))
+        f.write('<Grid Name="%s" GridType="Uniform">\n<Topology TopologyType="PolyLine" NumberOfElements="%d" NodesPerElement="2">\n'
+                '<DataItem Dimensions="%d 2" NumberType="Int" Format="XML">\n%s\n</DataItem></Topology>\n'
+                % (tags_name, len(alle), len(alle), "\n".join(" ".join(map(str, c)) for c in alle)))
+        f.write('<Attribute Name="%s" AttributeType="Scalar" Center="Cell"><DataItem Dimensions="%d 1" Format="XML">\n%s\n'
+                '</DataItem></Attribute>\n</Grid>\n</Domain></Xdmf>\n' % (tags_name, len(vals), "\n".join(map(str, vals))))
+
+
 def write_xdmf_mesh(path, mesh, name: str = "mesh", encoding: str = "ASCII"):
     """XDMFFile.write_mesh (generate_mesh_gmsh.py:41-43) for a triangular fem.Mesh.  encoding "ASCII": inline (Format="XML") data
     items; "HDF5" (DOLFINx's default): the heavy data in `<stem>.h5` as /Mesh/<name>/geometry (float64) and /Mesh/<name>/topology
@@ -324,7 +385,8 @@ def write_xdmf_tet(path, mesh, facet_tags, tags=None, name: str = "mesh", tags_n
 
 def write_vtu(path, points, cells, point_data: dict | None = None, cell_data: dict | None = None, cell_type: str | None = None):
     """VTK XML unstructured grid (ASCII).  cells: (m,3) triangles, (m,6) quadratic triangles in the dof order used here
-    (3 vertices, then the edge midpoint OPPOSITE each vertex - reordered to VTK's edge order) or (m,4) tetrahedra."""
+    (3 vertices, then the edge midpoint OPPOSITE each vertex - reordered to VTK's edge order) or (m,4) tetrahedra; with
+    `cell_type` "hexahedron" (m,8) / "quad" (m,4) in VTK corner order."""
     points = np.asarray(points, dtype=np.float64)
     if points.shape[1] == 2:
         points = np.concatenate([points, np.zeros((len(points), 1))], axis=1)

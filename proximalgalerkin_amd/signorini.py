@@ -8,6 +8,10 @@ reference's signature (:156-174) and loop (:317-358); `SignoriniProblem` stands 
 
 Degrees 1 (BASELINE.json config 5) and 2 (the reference's default, :68-73) on tetrahedra (`TetMesh`) and on the reference's native
 hexahedral box grid (`HexMesh`, :376-383; Q1 / Q2 elements).  The forms-driven `NonlinearProblem` below takes both degrees.
+
+PLANE problems (the script with gdim = 2: `native --dim 2`, the half disk of `mesh_generation.create_half_disk`): a triangular
+`fem.Mesh` or a `fem.QuadMesh` instead of `TetMesh` / `HexMesh`; facets are then EDGES given as vertex pairs, the state is
+[u_x | u_y | psi], the rigid line is y = gap (include/pgx_sg.h: pgx_sg_create_2d).  Declarative driver only.
 """
 from __future__ import annotations
 
@@ -78,14 +82,78 @@ class TetMesh:
 
 
 class MeshTags:
-    """facet_tag of the reference (:384-385): tag -> facets (vertex triples); `.find(tag)` as dolfinx.mesh.MeshTags."""
+    """facet_tag of the reference (:384-385): tag -> facets (vertex triples; `width` = 2: the vertex pairs of a plane mesh's edges);
+    `.find(tag)` as dolfinx.mesh.MeshTags."""
 
-    def __init__(self, tagged: dict):
+    def __init__(self, tagged: dict, width: int = 3):
         self._t = {int(k): np.ascontiguousarray(v, dtype=np.int32) for k, v in tagged.items()}
+        self._width = int(width)
 
     def find(self, tag):
-        return self._t.get(int(tag), np.zeros((0, 3), dtype=np.int32))
+        return self._t.get(int(tag), np.zeros((0, self._width), dtype=np.int32))
 
+
+def _tagged(facet_tag, tags, width):
+    """facets of all `tags`: from a MeshTags or from the {marker: facets} dict `mesh_generation.create_half_disk` returns"""
+    find = facet_tag.find if hasattr(facet_tag, "find") else (lambda t: facet_tag.get(int(t), np.zeros((0, width), dtype=np.int32)))
+    return np.concatenate([np.asarray(find(t), dtype=np.int32).reshape(-1, width) for t in tags])
+
+
+def p2_nodes_tri(mesh: fem.Mesh, *edge_sets):
+    """Degree-2 node numbering of a triangular mesh (include/pgx_sg.h, plane problems): the vertices, then one node per edge in
+    `Mesh.edges()` order, at the edge midpoint.  Returns (node_coords, cells6 - vertices, then the edge nodes of (0,1) (0,2) (1,2) -,
+    [edges3 - the two vertices, then the midpoint node - for every set of edges given as vertex pairs])."""
+    nv = mesh.num_vertices
+    edges, cell_edges = mesh.edges()  # local edge i is OPPOSITE local vertex i
+    cells6 = np.ascontiguousarray(np.concatenate([mesh.cells, nv + cell_edges[:, [2, 1, 0]]], axis=1), dtype=np.int32)
+    coords = np.ascontiguousarray(np.concatenate([mesh.geometry, 0.5 * (mesh.geometry[edges[:, 0]] + mesh.geometry[edges[:, 1]])]))
+    key = edges[:, 0].astype(np.int64) * nv + edges[:, 1]
+    out = []
+    for e in edge_sets:
+        e = np.asarray(e, dtype=np.int64).reshape(-1, 2)
+        k = e.min(axis=1) * nv + e.max(axis=1)
+        pos = np.searchsorted(key, k)
+        if len(e) and not np.array_equal(key[np.minimum(pos, len(key) - 1)], k):
+            raise ValueError("a facet is not an edge of the mesh")
+        out.append(np.ascontiguousarray(np.concatenate([e, (nv + pos)[:, None]], axis=1), dtype=np.int32))
+    return coords, cells6, out
+
+
+def quad_lattice(mesh: fem.QuadMesh, d: int):
+    """(node coordinates, cells [nc][(d+1)^2]) of the Q_d discretisation of a structured quadrilateral grid: the vertex lattice refined
+    d times, nodes and local nodes lexicographic (x fastest)"""
+    nx, ny = mesh.structured
+    (x0, y0), (x1, y1) = mesh.box
+    Nx, Ny = d * nx + 1, d * ny + 1
+    coords = np.ascontiguousarray(np.stack([np.tile(np.linspace(x0, x1, Nx), Ny), np.repeat(np.linspace(y0, y1, Ny), Nx)], axis=1))
+    cy, cx = np.repeat(np.arange(ny), nx), np.tile(np.arange(nx), ny)
+    cells = np.stack([(d * cy + iy) * Nx + d * cx + ix for iy in range(d + 1) for ix in range(d + 1)], axis=1)
+    return coords, np.ascontiguousarray(cells, dtype=np.int32)
+
+
+def quad_edge_nodes(mesh: fem.QuadMesh, edges, d: int):
+    """Q_d nodes (lexicographic along the edge) of grid edges given by their two corner vertices"""
+    nx, ny = mesh.structured
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    Nx = d * nx + 1
+    i, j = e % (nx + 1), e // (nx + 1)
+    n = (d * j) * Nx + d * i  # the corners on the refined lattice
+    lo, hi = n.min(axis=1), n.max(axis=1)
+    if len(e) and not np.all((np.abs(i[:, 0] - i[:, 1]) + np.abs(j[:, 0] - j[:, 1])) == 1):
+        raise ValueError("a facet is not an edge of the grid")
+    return np.ascontiguousarray(np.stack([lo + k * (hi - lo) // d for k in range(d + 1)], axis=1), dtype=np.int32)
+
+
+def boundary_edges_where(mesh, pred):
+    """Exterior edges (vertex pairs) of a triangular fem.Mesh or a fem.QuadMesh whose two vertices satisfy pred(x)
+    (locate_entities_boundary, :369-373)."""
+    c = mesh.cells
+    loc = ((0, 1), (1, 3), (3, 2), (2, 0)) if isinstance(mesh, fem.QuadMesh) else ((0, 1), (1, 2), (2, 0))
+    e = np.concatenate([c[:, list(ab)] for ab in loc])
+    on = pred(mesh.geometry.T)
+    sel = e[on[e].all(axis=1)]
+    _, idx, cnt = np.unique(np.sort(sel, axis=1), axis=0, return_index=True, return_counts=True)
+    return np.ascontiguousarray(sel[np.sort(idx[cnt == 1])], dtype=np.int32)
 
 
 
@@ -203,7 +271,12 @@ def create_unit_cube(nx, ny, nz) -> TetMesh:
 
 
 def native_tags(mesh: TetMesh) -> tuple[MeshTags, dict]:
-    """The `native` branch of the reference's __main__ (:365-386): top (z = 1) tagged 1, bottom (z = 0) tagged 2."""
+    """The `native` branch of the reference's __main__ (:365-386): top (z = 1; the unit square: y = 1) tagged 1, bottom (z = 0; y = 0)
+    tagged 2."""
+    if isinstance(mesh, (fem.Mesh, fem.QuadMesh)):
+        top = boundary_edges_where(mesh, lambda x: np.isclose(x[1], 1.0))
+        bottom = boundary_edges_where(mesh, lambda x: np.isclose(x[1], 0.0))
+        return MeshTags({1: top, 2: bottom}, width=2), {"contact": (2,), "displacement": (1,)}
     top = mesh.facets_where(lambda x: np.isclose(x[2], 1.0))
     bottom = mesh.facets_where(lambda x: np.isclose(x[2], 0.0))
     return MeshTags({1: top, 2: bottom}), {"contact": (2,), "displacement": (1,)}
@@ -241,7 +314,7 @@ def curved_tables(node_coords, cells10, facets6, cell_qpts, facet_qpts):
 
 
 class SignoriniProblem(_MixedHandle):
-    """x = [u_x | u_y | u_z | psi (contact vertices ordered by vertex id)]."""
+    """x = [u_x | u_y | u_z | psi (contact vertices ordered by vertex id)]; on a plane mesh (fem.Mesh / fem.QuadMesh) x = [u_x | u_y | psi]."""
 
     _prefix = "pgx_sg"
 
@@ -256,6 +329,13 @@ class SignoriniProblem(_MixedHandle):
         self._lib = lib = _lib.load()
         self.mesh = mesh
         self.degree = int(degree)
+        self.gdim = 2 if isinstance(mesh, (fem.Mesh, fem.QuadMesh)) else 3
+        if self.gdim == 2:
+            if comm is not None:
+                raise NotImplementedError("plane problems: single handle only (include/pgx_sg.h: pgx_sg_create_dist is 3-D)")
+            self._create_2d(contact_facets, bc_vertices, bc_facets, E, nu, gap, disp, quadrature_degree, device)
+            self._finish()
+            return
         pts, wts = fem.quadrature_rule("triangle", quadrature_degree)
         self.cell_type = 1 if isinstance(mesh, HexMesh) else 0
         if self.cell_type == 1:  # the reference's native mesh: Q_d on the structured box grid
@@ -317,6 +397,52 @@ class SignoriniProblem(_MixedHandle):
         if rc:
             msg = lib.pgx_sg_last_error(None)
             raise _lib.PgxError(f"pgx_sg_create failed (code {rc}): {msg.decode() if msg else ''}")
+        self._finish()
+
+    def _create_2d(self, contact_edges, bc_vertices, bc_edges, E, nu, gap, disp, quadrature_degree, device):
+        """pgx_sg_create_2d: triangles (P1 / P2) or the structured quadrilateral grid (Q1 / Q2); contact and displacement facets are
+        edges given as vertex pairs; Dirichlet data (0, disp) at the nodes of the displacement edges (edge nodes included)."""
+        lib, mesh, d = self._lib, self.mesh, self.degree
+        if d not in (1, 2):
+            raise NotImplementedError("HIP backend: degrees 1 and 2")
+        if bc_edges is None and bc_vertices is None:
+            raise ValueError("plane problems need the Dirichlet nodes or the displacement EDGES")
+        none = np.zeros((0, 2), np.int32)
+        self.cell_type = 1 if isinstance(mesh, fem.QuadMesh) else 0
+        if self.cell_type == 1:
+            coords, cells = quad_lattice(mesh, d)
+            facets = quad_edge_nodes(mesh, contact_edges, d)
+            be = quad_edge_nodes(mesh, none if bc_edges is None else bc_edges, d)
+        else:
+            if mesh.curved:
+                raise NotImplementedError("plane contact on curved (order-2 geometry) triangles is not implemented: pass mesh.flattened()")
+            if d == 2:
+                coords, cells, (facets, be) = p2_nodes_tri(mesh, contact_edges, none if bc_edges is None else bc_edges)
+            else:
+                coords, cells = mesh.geometry, mesh.cells
+                facets = np.ascontiguousarray(np.asarray(contact_edges, dtype=np.int32).reshape(-1, 2))
+                be = np.asarray(none if bc_edges is None else bc_edges, dtype=np.int32).reshape(-1, 2)
+        bv = (np.unique(be.ravel()) if bc_vertices is None else np.asarray(bc_vertices)).astype(np.int64)
+        pts, wts = fem.interval_quadrature(quadrature_degree)  # basix's default on the interval (:211-218 metadata)
+        self.node_coords = coords
+        self.cells, self.facets = cells, facets  # node ids, the orders of include/pgx_sg.h
+        self.E, self.nu, self.gap = float(E), float(nu), float(gap)
+        self.facet_quadrature = (pts, wts)
+        nv = coords.shape[0]
+        bc = np.ascontiguousarray(np.concatenate([bv, nv + bv]), dtype=np.int32)  # all components (:267)
+        vals = np.ascontiguousarray(np.concatenate([np.zeros(len(bv)), np.full(len(bv), float(disp))]))
+        self._keep = (coords, cells, facets, pts, wts, bc, vals)
+        pm = _lib.pgx_sg_mesh2d(nv, cells.shape[0], _lib.dptr(coords), _lib.iptr(cells), facets.shape[0], _lib.iptr(facets), d, self.cell_type)
+        pp = _lib.pgx_sg_problem2d(float(E), float(nu), float(gap), len(wts), _lib.dptr(pts), _lib.dptr(wts), len(bc), _lib.iptr(bc),
+                                   _lib.dptr(vals))
+        self._h = C.c_void_p()
+        rc = lib.pgx_sg_create_2d(C.byref(pm), C.byref(pp), int(device), C.byref(self._h))
+        if rc:
+            msg = lib.pgx_sg_last_error(None)
+            raise _lib.PgxError(f"pgx_sg_create_2d failed (code {rc}): {msg.decode() if msg else ''}")
+
+    def _finish(self):
+        lib, nv = self._lib, self.node_coords.shape[0]
         nt, npsi = C.c_int64(0), C.c_int64(0)
         lib.pgx_sg_num_dofs(self._h, C.byref(nt), C.byref(npsi))
         self.ndofs, self.npsi, self.nv = nt.value, npsi.value, nv
@@ -375,10 +501,12 @@ def solve_contact_problem(mesh: TetMesh, facet_tag: MeshTags, boundary_condition
     only when printed (`verbose`) or collected."""
     if degree not in (1, 2):
         raise NotImplementedError("HIP backend: degrees 1 (BASELINE.json config 5) and 2 (the reference's default)")
-    contact = np.concatenate([facet_tag.find(t) for t in boundary_conditions["contact"]])  # :186-189
-    bc_facets = np.concatenate([facet_tag.find(t) for t in boundary_conditions["displacement"]])  # :265-266
+    plane = isinstance(mesh, (fem.Mesh, fem.QuadMesh))  # gdim = 2 (:204): facets are edges, tagged as vertex pairs
+    width = 2 if plane else (4 if isinstance(mesh, HexMesh) else 3)
+    contact = _tagged(facet_tag, boundary_conditions["contact"], width)  # :186-189
+    bc_facets = _tagged(facet_tag, boundary_conditions["displacement"], width)  # :265-266
     bc_vertices = np.unique(bc_facets.ravel())
-    problem = SignoriniProblem(mesh, contact, bc_vertices if degree == 1 and not isinstance(mesh, HexMesh) else None, E, nu, gap, disp,
+    problem = SignoriniProblem(mesh, contact, bc_vertices if degree == 1 and not plane and not isinstance(mesh, HexMesh) else None, E, nu, gap, disp,
                                quadrature_degree, device=device, comm=comm, degree=degree, bc_facets=bc_facets)
     iterations = []
     normed_diff = -1.0
@@ -419,8 +547,20 @@ def solve_contact_problem(mesh: TetMesh, facet_tag: MeshTags, boundary_condition
         xs = problem.get_state()
         nv = problem.nv
         viol = problem.violation()  # the reference's `violation` Function next to u in uh.bp (:293-294, 349)
-        u3 = np.stack([xs[:nv], xs[nv:2 * nv], xs[2 * nv:3 * nv]], axis=1)
-        if isinstance(mesh, HexMesh):  # all Q_d nodes as a point cloud of first-order cells on the refined lattice
+        u3 = np.stack([xs[k * nv:(k + 1) * nv] for k in range(problem.gdim)], axis=1)
+        cell_name = None
+        if isinstance(mesh, fem.QuadMesh):  # all Q_d nodes, first-order cells on the refined lattice (VTK corner order)
+            co, _ = quad_lattice(mesh, degree)
+            sub = fem.QuadMesh(mesh.box, (degree * mesh.structured[0], degree * mesh.structured[1]))
+            cell_name = "quad"
+            write_vtu(output / "uh.vtu", co, sub.cells[:, [0, 1, 3, 2]], {"displacement": u3, "violation": viol}, cell_type=cell_name)
+            n1 = degree + 1
+            corners = [0, degree, degree * n1 + degree, degree * n1]
+        elif isinstance(mesh, fem.Mesh):
+            nvert = mesh.geometry.shape[0]
+            write_vtu(output / "uh.vtu", mesh.geometry, mesh.cells, {"displacement": u3[:nvert], "violation": viol[:nvert]})
+            corners = [0, 1, 2]
+        elif isinstance(mesh, HexMesh):  # all Q_d nodes as a point cloud of first-order cells on the refined lattice
             co, ce = mesh.lattice(degree)
             sub = HexMesh(degree * mesh.nx, degree * mesh.ny, degree * mesh.nz)
             write_vtu(output / "uh.vtu", co, sub.cells[:, [0, 1, 3, 2, 4, 5, 7, 6]], {"displacement": u3, "violation": viol},
@@ -439,9 +579,9 @@ def solve_contact_problem(mesh: TetMesh, facet_tag: MeshTags, boundary_condition
             nc, k = cn.shape
             write_vtu(output / "von_mises.vtu", problem.node_coords[cn.ravel()], np.arange(nc * k, dtype=np.int32).reshape(nc, k),
                       {"VonMises": problem.von_mises()[:, corners].ravel(), "u": u3[cn.ravel()]},
-                      cell_type="hexahedron" if isinstance(mesh, HexMesh) else None)
+                      cell_type="hexahedron" if isinstance(mesh, HexMesh) else cell_name)
     if verbose:
-        print(f"num_dofs_u={3 * problem.nv}, num_cells={mesh.cells.shape[0]}")
+        print(f"num_dofs_u={problem.gdim * problem.nv}, num_cells={mesh.cells.shape[0]}")
     if return_solution:
         x = problem.get_state()
         cv = problem.contact_vertices.copy()
@@ -466,7 +606,9 @@ class NonlinearProblem:
         mesh = V.mesh
         W = spec.psi.function_space
         if V.degree not in (1, 2) or V.dim != 3 or W.degree != V.degree:
-            raise NotImplementedError("HIP backend: equal degrees 1 or 2 for displacement and latent variable, in 3-D (signorini_dolfinx.py:221-222)")
+            raise NotImplementedError("HIP backend, forms front end: equal degrees 1 or 2 for displacement and latent variable, in 3-D "
+                                      "(signorini_dolfinx.py:221-222); plane problems run through the declarative driver "
+                                      "proximalgalerkin_amd.signorini.solve_contact_problem on a fem.Mesh / fem.QuadMesh")
         if not bcs or len(bcs) != 1:
             raise NotImplementedError("one Dirichlet condition on the displacement surface (signorini_dolfinx.py:255-269)")
         bc = bcs[0]
@@ -504,6 +646,10 @@ def solve_contact_problem_forms(mesh: TetMesh, facet_tag: MeshTags, boundary_con
     measures, the residual form, NonlinearProblem - through the UFL-subset front end.  alpha doubling.  Returns
     (it, iterations, u Function)."""
     from . import ufl
+
+    if isinstance(mesh, (fem.Mesh, fem.QuadMesh)):
+        raise NotImplementedError("HIP backend, forms front end: 3-D only; plane problems run through the declarative driver "
+                                  "proximalgalerkin_amd.signorini.solve_contact_problem on a fem.Mesh / fem.QuadMesh")
 
     def epsilon(w):  # :146-147
         return ufl.sym(ufl.grad(w))
