@@ -41,6 +41,14 @@
 #ifndef F32_K6_TY_TOP
 #define F32_K6_TY_TOP 20  // tile rows of a six-sweep launch on levels above 513^2 (measured on 1025^2 and 2049^2: 12 / 16 / 20)
 #endif
+// A/B switch of the seven-neighbour LDS reads of an image (row sweeps, residual rows of the fused epilogue, restriction gathers):
+// F32_LDS_SINGLE = 1 reads every float2 neighbour as ONE 8-byte ds_read_b64 that the compiler may not merge; 0 leaves the plain
+// loads, which it merges in pairs into ds_read2_b64 - 8 LDS-array cycles per pair where two single reads take 2 + 2 (DESIGN.md
+// section 5b).  The values loaded are the same; that the RESULTS are the same bit for bit is a property of the compiled code (which
+// products the compiler contracts into FMAs), pinned by tests/test_gpu_mg32_lds_reads.py.
+#ifndef F32_LDS_SINGLE
+#define F32_LDS_SINGLE 1
+#endif
 #define F32_RR_CYB 2  // coarse rows of a boundary sub-tile of the residual + restriction
 #define F32_TB 2  // rows of a boundary sub-tile of the smoother: image of 2 + 2K <= 8 rows, one per wave
 // ... of a six-sweep launch without the fused restriction: 4.  Its image of TB + 12 rows takes two rows per wave either way (14
@@ -52,6 +60,24 @@ __device__ __forceinline__ float lane_shr1f(float x) {  // the value of lane - 1
   v = __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false);  // wave_shr:1
   return __int_as_float(v);
 }
+
+// One float2 of an LDS image as one 8-byte read of its own: volatile keeps the compiler from pairing it with a neighbour's; the
+// pointer has to carry the LDS address space itself (a volatile load through the generic pointer is not inferred to LDS and
+// becomes a flat load).
+__device__ __forceinline__ float2 f_lds(const float2* p) {
+  typedef const volatile __attribute__((address_space(3))) unsigned long long lds_u64;
+  const unsigned long long w = *(lds_u64*)p;
+  return make_float2(__uint_as_float((unsigned)w), __uint_as_float((unsigned)(w >> 32)));
+}
+#if F32_LDS_SINGLE
+#define F_LD(src, i) f_lds(&src[i])
+#else
+#define F_LD(src, i) src[i]
+#endif
+// the seven neighbours of image vertex q (row length W) in stencil-slot order
+#define F_LDS7(src, q, W, x0, x1, x2, x3, x4, x5, x6)                                                                              \
+  const float2 x0 = F_LD(src, q), x1 = F_LD(src, (q) + 1), x2 = F_LD(src, (q) - 1), x3 = F_LD(src, (q) + W),                       \
+               x4 = F_LD(src, (q) - W), x5 = F_LD(src, (q) + W + 1), x6 = F_LD(src, (q) - W - 1);
 
 // The storage of D(psi) on a single-precision level is a template parameter DT of every reader: float4, or uint2 = two packed bf16
 // pairs (x: D(0,0) low half, D(+1,0) high half; y: D(0,+1), D(+1,+1)).  Packing rounds to nearest even (v_cvt_pk_bf16_f32), so an
@@ -295,8 +321,7 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
   }
   // (au, ap) = the two rows of J at image vertex q of row slot k
 #define F_ROWS(src, q, k, au, ap, x0)                                                                                              \
-  const float2 x0 = src[q], x1_ = src[q + 1], x2_ = src[q - 1], x3_ = src[q + W], x4_ = src[q - W], x5_ = src[q + W + 1],          \
-               x6_ = src[q - W - 1];                                                                                               \
+  F_LDS7(src, q, W, x0, x1_, x2_, x3_, x4_, x5_, x6_)                                                                              \
   const float u12_ = x1_.x + x2_.x, u34_ = x3_.x + x4_.x, u56_ = x5_.x + x6_.x;                                                    \
   const float p12_ = x1_.y + x2_.y, p34_ = x3_.y + x4_.y, p56_ = x5_.y + x6_.y;                                                    \
   au = (k0 * x0.x + k1 * u12_) + (k3 * u34_ + k5 * u56_) + ((m0 * x0.y + m1 * p12_) + (m3 * p34_ + m5 * p56_));                    \
@@ -359,8 +384,7 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
     for (int cj = wave; cj < TY / 2; cj += NW)
       if (lane < TX / 2) {
         const int q = (HALO + 2 * cj) * W + HALO + 2 * lane;
-        const float2 r0 = rim[q], r1 = rim[q + 1], r2 = rim[q - 1], r3 = rim[q + W], r4 = rim[q - W], r5 = rim[q + W + 1],
-                     r6 = rim[q - W - 1];
+        F_LDS7(rim, q, W, r0, r1, r2, r3, r4, r5, r6)
         const float su = r0.x + 0.5f * (((r1.x + r2.x) + (r3.x + r4.x)) + (r5.x + r6.x));
         const float sp = r0.y + 0.5f * (((r1.y + r2.y) + (r3.y + r4.y)) + (r5.y + r6.y));
         const int C = (J0 + cj) * sxc + I0 + lane;
@@ -485,8 +509,7 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
   }
   // (au, ap) = the two rows of J at image vertex q of row slot k, per-lane K / M coefficients
 #define F_ROWS_G(src, q, k, au, ap, x0)                                                                                            \
-  const float2 x0 = src[q], x1_ = src[q + 1], x2_ = src[q - 1], x3_ = src[q + W], x4_ = src[q - W], x5_ = src[q + W + 1],          \
-               x6_ = src[q - W - 1];                                                                                               \
+  F_LDS7(src, q, W, x0, x1_, x2_, x3_, x4_, x5_, x6_)                                                                              \
   au = ((kv[k][0] * x0.x + kv[k][1] * x1_.x) + (kv[k][2] * x2_.x + kv[k][3] * x3_.x)) +                                            \
        ((kv[k][4] * x4_.x + kv[k][5] * x5_.x) + kv[k][6] * x6_.x) +                                                                \
        (((mv[k][0] * x0.y + mv[k][1] * x1_.y) + (mv[k][2] * x2_.y + mv[k][3] * x3_.y)) +                                           \
@@ -547,8 +570,7 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
     for (int cj = wave; cj < TB / 2; cj += NW)
       if (lane < TX / 2 && I0 + lane <= A.nxc && J0 + cj <= A.nyc) {
         const int q = (HALO + 2 * cj) * W + HALO + 2 * lane;
-        const float2 r0 = rim[q], r1 = rim[q + 1], r2 = rim[q - 1], r3 = rim[q + W], r4 = rim[q - W], r5 = rim[q + W + 1],
-                     r6 = rim[q - W - 1];
+        F_LDS7(rim, q, W, r0, r1, r2, r3, r4, r5, r6)
         float su = r0.x + 0.5f * (((r1.x + r2.x) + (r3.x + r4.x)) + (r5.x + r6.x));
         const float sp = r0.y + 0.5f * (((r1.y + r2.y) + (r3.y + r4.y)) + (r5.y + r6.y));
         const int C = (J0 + cj) * sxc + I0 + lane;
@@ -710,8 +732,7 @@ __device__ __forceinline__ void f_smooth_bnd_full(int b, const FSmoothArgs& A, f
   // VGPRs, and only the frame's lanes wait here
   auto rows = [&](const float2* src, int lj, int k, float& au, float& ap) -> float2 {
     const int q = lj * W + lane;
-    const float2 x0 = src[q], x1 = src[q + 1], x2 = src[q - 1], x3 = src[q + W], x4 = src[q - W], x5 = src[q + W + 1],
-                 x6 = src[q - W - 1];
+    F_LDS7(src, q, W, x0, x1, x2, x3, x4, x5, x6)
     const float dp = ((dq[k].x * x0.y + dq[k].y * x1.y) + (d2[k] * x2.y + dq[k].z * x3.y)) +
                      ((d4[k] * x4.y + dq[k].w * x5.y) + d6[k] * x6.y);
     const float u12 = x1.x + x2.x, u34 = x3.x + x4.x, u56 = x5.x + x6.x;
@@ -791,8 +812,7 @@ __device__ __forceinline__ void f_smooth_bnd_full(int b, const FSmoothArgs& A, f
     for (int cj = wave; cj < TY / 2; cj += NW)
       if (lane < TX / 2 && I0 + lane <= A.nxc && J0 + cj <= A.nyc) {
         const int q = (HALO + 2 * cj) * W + HALO + 2 * lane;
-        const float2 r0 = rim[q], r1 = rim[q + 1], r2 = rim[q - 1], r3 = rim[q + W], r4 = rim[q - W], r5 = rim[q + W + 1],
-                     r6 = rim[q - W - 1];
+        F_LDS7(rim, q, W, r0, r1, r2, r3, r4, r5, r6)
         float su = r0.x + 0.5f * (((r1.x + r2.x) + (r3.x + r4.x)) + (r5.x + r6.x));
         const float sp = r0.y + 0.5f * (((r1.y + r2.y) + (r3.y + r4.y)) + (r5.y + r6.y));
         const int C = (J0 + cj) * sxc + I0 + lane;
@@ -1099,6 +1119,8 @@ __device__ __forceinline__ void f_rr_fast(int tx, int ty, const FRrArgs& A, floa
     if (lj < 1 || lj > HR) continue;  // wave-uniform
     const float d2 = lane_shr1f(dq[k].y), d4 = exch[(lj - 1) * W + lane].x, d6 = exch[(lj - 1) * W + lane - 1].y;
     const int q = lj * W + lane;
+    // plain (merged) reads in these rows and in those of f_rr_bnd: with f_lds the compiler contracts the products of this kernel's
+    // rows into other FMA pairs and the residual changes in its last bits; the gathers below take f_lds
     const float2 x0 = ximg[q], x1 = ximg[q + 1], x2 = ximg[q - 1], x3 = ximg[q + W], x4 = ximg[q - W], x5 = ximg[q + W + 1],
                  x6 = ximg[q - W - 1];
     const float u12 = x1.x + x2.x, u34 = x3.x + x4.x, u56 = x5.x + x6.x;
@@ -1113,8 +1135,7 @@ __device__ __forceinline__ void f_rr_fast(int tx, int ty, const FRrArgs& A, floa
   // row 2w + 1 (image rows start at fine row 2 J0 - 1) and column 2 lane + 2
   if (wave < CY && lane < CX) {
     const int q = (2 * wave + 1) * W + 2 * lane + 2;
-    const float2 r0 = rimg[q], r1 = rimg[q + 1], r2 = rimg[q - 1], r3 = rimg[q + W], r4 = rimg[q - W], r5 = rimg[q + W + 1],
-                 r6 = rimg[q - W - 1];
+    F_LDS7(rimg, q, W, r0, r1, r2, r3, r4, r5, r6)
     const float su = r0.x + 0.5f * (((r1.x + r2.x) + (r3.x + r4.x)) + (r5.x + r6.x));
     const float sp = r0.y + 0.5f * (((r1.y + r2.y) + (r3.y + r4.y)) + (r5.y + r6.y));
     const int C = (J0 + wave) * sxc + I0 + lane;
@@ -1177,7 +1198,7 @@ __device__ __forceinline__ void f_rr_bnd(int tx, int ty, int sub, const FRrArgs&
     const float d2 = lane_shr1f(dq.y), d4 = exch[(lj - 1) * W + lane].x, d6 = exch[(lj - 1) * W + lane - 1].y;
     const int q = lj * W + lane;
     const float2 x0 = ximg[q], x1 = ximg[q + 1], x2 = ximg[q - 1], x3 = ximg[q + W], x4 = ximg[q - W], x5 = ximg[q + W + 1],
-                 x6 = ximg[q - W - 1];
+                 x6 = ximg[q - W - 1];  // plain reads, as in f_rr_fast
     float au = ((kv[0] * x0.x + kv[1] * x1.x) + (kv[2] * x2.x + kv[3] * x3.x)) + ((kv[4] * x4.x + kv[5] * x5.x) + kv[6] * x6.x) +
                (((mv[0] * x0.y + mv[1] * x1.y) + (mv[2] * x2.y + mv[3] * x3.y)) + ((mv[4] * x4.y + mv[5] * x5.y) + mv[6] * x6.y));
     const float ap = (((mv[0] * x0.x + mv[1] * x1.x) + (mv[2] * x2.x + mv[3] * x3.x)) + ((mv[4] * x4.x + mv[5] * x5.x) + mv[6] * x6.x)) -
@@ -1190,8 +1211,7 @@ __device__ __forceinline__ void f_rr_bnd(int tx, int ty, int sub, const FRrArgs&
     const int I = I0 + lane, J = J0 + wave;
     if (I <= A.nxc && J <= A.nyc) {
       const int q = (2 * wave + 1) * W + 2 * lane + 2;
-      const float2 r0 = rimg[q], r1 = rimg[q + 1], r2 = rimg[q - 1], r3 = rimg[q + W], r4 = rimg[q - W], r5 = rimg[q + W + 1],
-                   r6 = rimg[q - W - 1];
+      F_LDS7(rimg, q, W, r0, r1, r2, r3, r4, r5, r6)
       float su = r0.x + 0.5f * (((r1.x + r2.x) + (r3.x + r4.x)) + (r5.x + r6.x));
       const float sp = r0.y + 0.5f * (((r1.y + r2.y) + (r3.y + r4.y)) + (r5.y + r6.y));
       const int C = J * sxc + I;
