@@ -242,6 +242,15 @@ int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* reason, int*
 /* energy, |complementarity|, feasibility, dual feasibility, H1 increment, latent L2 increment */
 int pgx_observables(pgx_handle* h, double out[6]);
 
+/* Test hook: the second stage of the Krylov driver's reductions as a launch of its own against the same stage run by the last
+ * workgroup of the producer launch (run-time option PGX_TICKET_REDUCE).  In the handle's own Krylov storage it fills nv basis
+ * vectors (basis_f32 != 0: stored as float) and a vector of `len` entries from `seed`, and `reps` times, on new data each time,
+ * computes the nv dot products and the projection w' = w - V h with |w'|^2 by both routes from equal inputs.  *mismatches = the
+ * number of 8-byte words - results on the device, results sent to the host, the stored w' - that differ: 0 is the only right
+ * answer.  len even, 2 <= len <= the handle's number of dofs; single handles with the polled read-back only (PGX_EINVAL
+ * otherwise).  Changes no state a solve reads. */
+int pgx_reduce_selfcheck(pgx_handle* h, int nv, int64_t len, int basis_f32, int reps, uint64_t seed, int64_t* mismatches);
+
 /* Accumulated device-time per phase since the last reset, ms (HIP events; only when enabled):
  * [0] residual [1] jacobian fill [2] mg setup [3] spmv (outer Krylov) [4] v-cycle [5] orthogonalisation
  * [6] observables [7] total newton_solve wall */

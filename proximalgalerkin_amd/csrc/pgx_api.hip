@@ -142,6 +142,10 @@ struct pgx_handle {
   // Krylov / Newton driver passes (single handles with host_poll; the last three only with the matrix-free P1 operator: krylov_lean())
   int gs_wide = 16;       // PGX_GS_WIDE=8: Gram-Schmidt launches of at most 8 basis vectors (k_multidot / k_multiaxpy_norm; 16: one pass over w up to 16)
   int fused_publish = 1;  // PGX_FUSED_PUBLISH=0: second reduction stage (k_reduce_rows / k_reduce_partials) and k_publish as two launches
+  int ticket_reduce = 1;  // PGX_TICKET_REDUCE=0: the second stage (and the publish) as a launch of its own behind k_multidot, k_multiaxpy_norm
+                          // and k_axpy_norms; 1: their last block to arrive runs it (PgxTicket).  Only with fused_publish, see ticketed()
+  unsigned long long* d_ticket = nullptr;  // the ticket counters (PGX_TK_WORDS): zeroed when the handle is created, set back to zero by the
+                                           // last block of every ticketed launch, freed with the handle
   int fused_resid = 1;    // PGX_FUSED_RESID=0: true residual of a restart cycle as operator apply + k_scale_copy(-1) + k_axpy(+b)
   int lean_rhs = 1;       // PGX_LEAN_RHS=0: the Newton loop forms rhs = -F as a vector, fgmres zero-fills x and accumulates into it
   int fused_step = 1;     // PGX_FUSED_STEP=0: xw += dx as k_axpy, |dx| and |xw| as two dev_norm calls with a read-back each
@@ -1261,6 +1265,7 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_HOST_POLL")) h->host_poll = atoi(e);
   if (const char* e = pgx_tune("PGX_GS_WIDE")) h->gs_wide = atoi(e) >= 16 ? 16 : 8;
   if (const char* e = pgx_tune("PGX_FUSED_PUBLISH")) h->fused_publish = atoi(e);
+  if (const char* e = pgx_tune("PGX_TICKET_REDUCE")) h->ticket_reduce = atoi(e);
   if (const char* e = pgx_tune("PGX_FUSED_RESID")) h->fused_resid = atoi(e);
   if (const char* e = pgx_tune("PGX_LEAN_RHS")) h->lean_rhs = atoi(e);
   if (const char* e = pgx_tune("PGX_FUSED_STEP")) h->fused_step = atoi(e);
@@ -1544,6 +1549,8 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
     DALLOC(h->d_small, 4 * (h->restart + 2));
     DALLOC(h->partials, (size_t)PGX_RED_BLOCKS * (h->restart + 2));
     DALLOC(h->partials2, ((n2 + PGX_BLOCK - 1) / PGX_BLOCK) * (size_t)62);
+    DALLOC(h->d_ticket, PGX_TK_WORDS);
+    HIPCHK(hipMemsetAsync(h->d_ticket, 0, sizeof(unsigned long long) * PGX_TK_WORDS, h->st));
     {  // small read-backs (norms, the Hessenberg column, observables): pinned + mapped + coherent, one sequence word at the end
       const size_t nsm = 4 * (size_t)(h->restart + 2);
       HIPCHK(hipHostMalloc((void**)&h->h_small, sizeof(double) * (nsm + 2), hipHostMallocMapped | hipHostMallocCoherent));
@@ -1757,6 +1764,28 @@ static int reduce_fetch(pgx_handle* h, int nb, const double* partials, int nrows
   pgxk_reduce_publish(h->st, nb, partials, nrows, dout, h->h_small_dev + hoff_r, (int)n1, dsrc1, h->h_small_dev + hoff1, seq, h->h_seq_dev);
   return wait_published(h, seq);
 }
+// The second stage inside the producer launch (PgxTicket, pgx_internal.h): where reduce_fetch would follow the launch.  Sharded handles,
+// replicas and the copy read-back keep the launches: an all-reduce or a copy sits between the stages there.
+static bool ticketed(const pgx_handle* h) { return h->ticket_reduce && fused_readback(h); }
+// a ticket whose reducer publishes what reduce_fetch(h, ., ., ., ., hoff_r, dsrc1, n1, hoff1) would; the caller waits for *seq
+static PgxTicket ticket_publish(pgx_handle* h, unsigned long long* seq, size_t hoff_r, const double* dsrc1 = nullptr, size_t n1 = 0,
+                                size_t hoff1 = 0) {
+  PgxTicket t;
+  t.ctr = h->d_ticket;
+  t.hout = h->h_small_dev + hoff_r;
+  t.n1 = (int)n1;
+  t.src1 = dsrc1;
+  t.dst1 = h->h_small_dev + hoff1;
+  t.seq = *seq = ++h->seq;
+  t.seqp = h->h_seq_dev;
+  return t;
+}
+// a ticket whose reducer leaves its results on the device only
+static PgxTicket ticket_device(pgx_handle* h) {
+  PgxTicket t;
+  t.ctr = h->d_ticket;
+  return t;
+}
 static int wait_published(pgx_handle* h, unsigned long long seq) {
   // Bounded wait: a collective or a kernel ahead of k_publish that never completes leaves hipStreamQuery at NotReady
   // for ever - after PGX_COMM_TIMEOUT seconds (default 120; the transports' own limit) the call fails with PGX_ECOMM / PGX_EHIP and
@@ -1796,10 +1825,19 @@ static int wait_published(pgx_handle* h, unsigned long long seq) {
 }
 
 static int dev_norm(pgx_handle* h, const double* v, double* out, size_t len = 0) {
-  if (fused_readback(h)) {  // k_reduce_partials (nv = 1) + k_publish as one launch
+  if (fused_readback(h)) {  // k_reduce_partials (nv = 1) + k_publish as one launch, or inside k_multidot's
     const size_t l = len ? len : 2 * (size_t)h->nd;
-    pgxk_multidot(h->st, l, 1, v, 0, v, h->partials, nullptr);
-    const int rc = reduce_fetch(h, pgxk_multidot_blocks(l), h->partials, 1, h->d_small, 0);
+    int rc;
+    if (ticketed(h)) {
+      unsigned long long seq;
+      PgxTicket tk = ticket_publish(h, &seq, 0);
+      const bool done = pgxk_multidot(h->st, l, 1, v, 0, v, h->partials, h->d_small, nullptr, 8, &tk);
+      if (!done) h->err = "dev_norm: k_multidot<1> without its second stage";  // (one vector: every instantiation carries it)
+      rc = done ? wait_published(h, seq) : PGX_EHIP;
+    } else {
+      pgxk_multidot(h->st, l, 1, v, 0, v, h->partials, nullptr);
+      rc = reduce_fetch(h, pgxk_multidot_blocks(l), h->partials, 1, h->d_small, 0);
+    }
     if (rc) return rc;
     *out = std::sqrt(h->h_small[0]);
     return PGX_OK;
@@ -2842,16 +2880,31 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
         const PgxDotScale* const dsc = lazy ? &sc2 : nullptr;
         // pass 1: h1 = V^T w.  passes 2+3 fused: w' = w - V h1 and [h2; |w'|^2] in one sweep over the basis.
         // Sharded: each batch of partial dot products is completed by ONE packed all-reduce, enqueued on the stream.
+        PgxTicket tkd = ticket_device(h);
+        PgxTicket* const tk1 = ticketed(h) ? &tkd : nullptr;  // h1's second stage in the last block of the dot-product launch
         if (vf32)
-          pgxk_multidot_f32(h->st, nk, j + 1, Vf, ldvf, h->w, nullptr, h->partials, d_h1, dsc, h->gs_wide);
+          pgxk_multidot_f32(h->st, nk, j + 1, Vf, ldvf, h->w, nullptr, h->partials, d_h1, dsc, h->gs_wide, tk1);
         else
-          pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h1, dsc, h->gs_wide);
+          pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h1, dsc, h->gs_wide, tk1);
         if (dist && (rc = allreduce_dev(h, d_h1, j + 1))) return rc;
         double wp2, h1h1 = 0.0, hh = 0.0;
         bool second;
         if (h->cgs_selective) {
           // lean second pass: w' = w - V h1 and |w'|^2; V^T w' (for the second projection) only if the test below asks for it
-          if (fused_readback(h)) {  // the norm's second stage and the read-back of [h1; |w'|^2] in one launch
+          if (ticketed(h)) {  // ... in the last block of the projection launch
+            unsigned long long seq;
+            const unsigned long long seq0 = h->seq;
+            PgxTicket tk = ticket_publish(h, &seq, (size_t)(m + 2) + j + 1, d_h1, (size_t)(j + 1), 0);
+            const bool done = vf32 ? pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h1, 0, h->w, vnext, h->partials, d_h2 + j + 1, h->gs_wide, &tk)
+                                   : pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, d_h2 + j + 1, h->gs_wide, &tk);
+            if (done) {
+              rc = wait_published(h, seq);
+            } else {  // an instantiation without the second stage: the launch of its own
+              h->seq = seq0;
+              rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_h2 + j + 1, (size_t)(m + 2) + j + 1, d_h1, (size_t)(j + 1), 0);
+            }
+            if (rc) return rc;
+          } else if (fused_readback(h)) {  // the norm's second stage and the read-back of [h1; |w'|^2] in one launch
             if (vf32)
               pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h1, 0, h->w, vnext, h->partials, nullptr, h->gs_wide);
             else
@@ -2876,10 +2929,12 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
           // first one cancelled most of w, |w'| < eta |w| with |w|^2 = |w'|^2 + |h1|^2
           second = wp2 < h->cgs_eta2 * (wp2 + h1h1);
           if (second) {
+            PgxTicket tkd2 = ticket_device(h);
+            PgxTicket* const tk2 = ticketed(h) ? &tkd2 : nullptr;
             if (vf32)  // against the vector as stored: (float) w', widened
-              pgxk_multidot_f32(h->st, nk, j + 1, Vf, ldvf, nullptr, vnext, h->partials, d_h2, dsc, h->gs_wide);
+              pgxk_multidot_f32(h->st, nk, j + 1, Vf, ldvf, nullptr, vnext, h->partials, d_h2, dsc, h->gs_wide, tk2);
             else
-              pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h2, dsc, h->gs_wide);
+              pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h2, dsc, h->gs_wide, tk2);
             if (dist && (rc = allreduce_dev(h, d_h2, j + 1))) return rc;
             if ((rc = replica_agree(h, d_h2, (size_t)(j + 1)))) return rc;
             if ((rc = fetch_small(h, d_h2, (size_t)(j + 1), (size_t)(m + 2)))) return rc;
@@ -2908,7 +2963,18 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
           // what it stores: hn is the norm of the vector kept (Pythagoras would describe the unrounded one).  One more small read-back,
           // on the rare path only.
           double* const d_n2 = d_h2 + j + 1;
-          if (fused_readback(h)) {
+          if (ticketed(h)) {
+            unsigned long long seq;
+            const unsigned long long seq0 = h->seq;
+            PgxTicket tk = ticket_publish(h, &seq, (size_t)(m + 2) + j + 1);
+            if (pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h2, 1, h->w, vnext, h->partials, d_n2, h->gs_wide, &tk)) {
+              rc = wait_published(h, seq);
+            } else {
+              h->seq = seq0;
+              rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_n2, (size_t)(m + 2) + j + 1);
+            }
+            if (rc) return rc;
+          } else if (fused_readback(h)) {
             pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h2, 1, h->w, vnext, h->partials, nullptr, h->gs_wide);
             if ((rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_n2, (size_t)(m + 2) + j + 1))) return rc;
           } else {
@@ -2997,15 +3063,19 @@ static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts
       for (int k = i + 1; k < j; ++k) s -= H[(size_t)i * m + k] * y[k];
       y[i] = s / H[(size_t)i * m + i];
     }
-    for (int i = 0; i < j; ++i) h->h_small[i] = y[i];
-    HIPCHK(hipMemcpyAsync(h->d_small, h->h_small, sizeof(double) * j, hipMemcpyHostToDevice, h->st));
+    // y travels with the launch as an argument (at most PGX_DOT_SCALE_MAX coefficients; a longer basis - P2 - uploads it as before, and
+    // h_small is then not touched again before that copy is done: the next read-back is ordered behind it on the stream)
+    const double* const y_arg = j <= PGX_DOT_SCALE_MAX ? y.data() : nullptr;
+    if (!y_arg) {
+      for (int i = 0; i < j; ++i) h->h_small[i] = y[i];
+      HIPCHK(hipMemcpyAsync(h->d_small, h->h_small, sizeof(double) * j, hipMemcpyHostToDevice, h->st));
+    }
     if (zf32)
-      pgxk_lincomb_f2(h->st, (size_t)h->nd, j, Zf, (size_t)h->nd, h->d_small, x, x + h->nd, x_unset ? 0 : 1);
+      pgxk_lincomb_f2(h->st, (size_t)h->nd, j, Zf, (size_t)h->nd, h->d_small, x, x + h->nd, x_unset ? 0 : 1, y_arg);
     else
-      pgxk_lincomb(h->st, n2, j, h->Z, n2, h->d_small, x, x_unset ? 0 : 1);
+      pgxk_lincomb(h->st, n2, j, h->Z, n2, h->d_small, x, x_unset ? 0 : 1, y_arg);
     x_unset = false;
-    // (no synchronisation: the loop head recomputes the TRUE residual b - Jx - it decides convergence, not the Arnoldi estimate - and
-    // its read-back is ordered behind the upload of y on the stream, so h_small is not touched again before that copy is done)
+    // (no synchronisation: the loop head recomputes the TRUE residual b - Jx - it decides convergence, not the Arnoldi estimate)
   }
   if (x_unset) pgxk_set(h->st, n2, 0.0, x);  // ksp_max_it == 0: no cycle ran
   *its_out = its;
@@ -3037,6 +3107,111 @@ extern "C" int pgx_residual(pgx_handle* h, const double* x, double* F, double* f
   }
   if (F) return copy_out(h, F, h->F);
   HIPCHK(hipStreamSynchronize(h->st));
+  return PGX_OK;
+}
+
+// Test hook (include/pgx.h): the two-launch route against the ticket route of the Gram-Schmidt reductions, on data of its own in the
+// handle's Krylov storage.  Reads no state of a solve and leaves none behind but scratch contents, and the sequence number.
+extern "C" int pgx_reduce_selfcheck(pgx_handle* h, int nv, int64_t len, int basis_f32, int reps, uint64_t seed, int64_t* mismatches) {
+  NEED(h);
+  if (!mismatches) return PGX_EINVAL;
+  const size_t n2 = 2 * (size_t)h->nd;
+  if (h->dist.on || h->lu_comm || !h->host_poll) {
+    h->err = "pgx_reduce_selfcheck: single handles with the polled read-back only";
+    return PGX_EINVAL;
+  }
+  if (nv < 1 || nv > std::min(h->restart - 1, PGX_DOT_SCALE_MAX) || len < 2 || (len & 1) || (size_t)len > n2 || reps < 1) {
+    h->err = "pgx_reduce_selfcheck: 1 <= nv <= min(restart - 1, " + std::to_string(PGX_DOT_SCALE_MAX) + "), len even, 2 <= len <= 2 nd, reps >= 1";
+    return PGX_EINVAL;
+  }
+  const size_t l = (size_t)len;
+  const size_t ldvf = (l + 3) & ~(size_t)3, ldv = basis_f32 ? ldvf : l;
+  float* const Vf = reinterpret_cast<float*>(h->V);
+  float* const vnext = Vf + (size_t)nv * ldvf;       // float basis: where (float) w' goes
+  double* const wsave = h->Z;                         // the vector as filled
+  double* const wkeep = h->Z + n2;                    // w' of the two-launch route (float basis: vnext, len / 2 words)
+  const size_t wwords = basis_f32 ? l / 2 : l;        // 8-byte words of the stored w'
+  const int m2 = h->restart + 2;
+  double* const d_a = h->d_small;                     // two-launch route: [h (nv); |w'|^2]
+  double* const d_b = h->d_small + m2;                // ticket route
+  std::vector<double> ha(nv + 1), hb(nv + 1), pa(nv + 1), pb(nv + 1), wa(wwords), wb(wwords);
+  int64_t bad = 0;
+  auto differ = [](const double* a, const double* b, size_t n) {
+    int64_t d = 0;
+    for (size_t i = 0; i < n; ++i) {
+      uint64_t x, y;
+      memcpy(&x, a + i, 8);
+      memcpy(&y, b + i, 8);
+      d += x != y;
+    }
+    return d;
+  };
+  auto project = [&](double* out, PgxTicket* tk) {  // w' = w - V h (h: the two-launch route's dot products) and |w'|^2
+    return basis_f32 ? pgxk_multiaxpy_norm_f32(h->st, l, nv, Vf, ldvf, d_a, 0, h->w, vnext, h->partials, out, h->gs_wide, tk)
+                     : pgxk_multiaxpy_norm(h->st, l, nv, h->V, ldv, d_a, h->w, h->partials, out, h->gs_wide, tk);
+  };
+  double* const wres = basis_f32 ? reinterpret_cast<double*>(vnext) : h->w;
+  for (int rep = 0; rep < reps; ++rep) {
+    const unsigned long long sd = (unsigned long long)seed * 1000003ull + (unsigned long long)rep * 65ull;
+    for (int i = 0; i < nv; ++i) {
+      if (basis_f32)
+        pgxk_fill_hash(h->st, l, sd + 1 + i, nullptr, Vf + (size_t)i * ldvf);
+      else
+        pgxk_fill_hash(h->st, l, sd + 1 + i, h->V + (size_t)i * ldv, nullptr);
+    }
+    pgxk_fill_hash(h->st, l, sd, h->w, nullptr);
+    pgxk_scale_copy(h->st, l, 1.0, h->w, wsave);
+    PgxDotScale sc;
+    for (int i = 0; i < PGX_DOT_SCALE_MAX; ++i) sc.s[i] = 1.0 + (double)((i * 7 + rep) % 13) / 16.0;
+    const PgxDotScale* const scp = (rep & 1) ? &sc : nullptr;  // both second-stage kernels, k_reduce_partials and its scaled form
+    // dot products: two launches, then the ticket
+    HIPCHK(hipMemsetAsync(h->d_small, 0xff, sizeof(double) * 2 * (size_t)m2, h->st));
+    if (basis_f32)
+      pgxk_multidot_f32(h->st, l, nv, Vf, ldvf, h->w, nullptr, h->partials, d_a, scp, h->gs_wide);
+    else
+      pgxk_multidot(h->st, l, nv, h->V, ldv, h->w, h->partials, d_a, scp, h->gs_wide);
+    PgxTicket tkd = ticket_device(h);
+    const bool dot_tk = basis_f32 ? pgxk_multidot_f32(h->st, l, nv, Vf, ldvf, h->w, nullptr, h->partials, d_b, scp, h->gs_wide, &tkd)
+                                  : pgxk_multidot(h->st, l, nv, h->V, ldv, h->w, h->partials, d_b, scp, h->gs_wide, &tkd);
+    (void)dot_tk;  // false: this instantiation keeps the second-stage launch and the two routes are one
+    // projection and norm, two launches: the partials, then k_reduce_publish
+    project(nullptr, nullptr);
+    int rc = reduce_fetch(h, pgxk_stream_blocks(l), h->partials, 1, d_a + nv, (size_t)m2 + nv, d_a, (size_t)nv, 0);
+    if (rc) return rc;
+    for (int i = 0; i < nv; ++i) pa[i] = h->h_small[i];
+    pa[nv] = h->h_small[(size_t)m2 + nv];
+    HIPCHK(hipMemcpyAsync(wa.data(), wres, sizeof(double) * wwords, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipMemcpyAsync(ha.data(), d_a, sizeof(double) * (nv + 1), hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    for (int i = 0; i <= nv; ++i) h->h_small[i] = h->h_small[(size_t)m2 + i] = 0.0;
+    // the same inputs again, with the ticket
+    pgxk_scale_copy(h->st, l, 1.0, wsave, h->w);
+    HIPCHK(hipMemsetAsync(wkeep, 0, sizeof(double) * wwords, h->st));
+    if (basis_f32) HIPCHK(hipMemsetAsync(vnext, 0, sizeof(float) * ldvf, h->st));
+    {
+      unsigned long long seq;
+      const unsigned long long seq0 = h->seq;
+      PgxTicket tk = ticket_publish(h, &seq, (size_t)m2 + nv, d_a, (size_t)nv, 0);
+      if (project(d_b + nv, &tk)) {
+        rc = wait_published(h, seq);
+      } else {
+        h->seq = seq0;
+        rc = reduce_fetch(h, pgxk_stream_blocks(l), h->partials, 1, d_b + nv, (size_t)m2 + nv, d_a, (size_t)nv, 0);
+      }
+      if (rc) return rc;
+    }
+    for (int i = 0; i < nv; ++i) pb[i] = h->h_small[i];
+    pb[nv] = h->h_small[(size_t)m2 + nv];
+    HIPCHK(hipMemcpyAsync(wb.data(), wres, sizeof(double) * wwords, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipMemcpyAsync(hb.data(), d_b, sizeof(double) * (nv + 1), hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    bad += differ(ha.data(), hb.data(), (size_t)nv + 1);  // device results: the dot products and the norm
+    bad += differ(pa.data(), pb.data(), (size_t)nv + 1);  // what the host was sent
+    bad += differ(pa.data(), ha.data(), (size_t)nv + 1);  // ... is what the device holds
+    bad += differ(wa.data(), wb.data(), wwords);          // the stored w'
+  }
+  HIPCHK(hipGetLastError());
+  *mismatches = bad;
   return PGX_OK;
 }
 
@@ -3677,7 +3852,14 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
     // it) for the step test below, which then needs one read-back and no further pass
     const bool fstep = h->fused_step && fused_readback(h) && !use_lu && !mg_first && krylov_lean(h);
     int step_nb = 0;
-    if (fstep)
+    // ticketed: the last block of the step's launch sums |dx|^2 and |xw|^2 and publishes them to h_small[2], [3] (the residual norm
+    // read back in between takes h_small[0]); the host reads them below, behind the wait for that norm, without a launch or a wait more
+    const bool fstep_tk = fstep && ticketed(h);
+    if (fstep_tk) {
+      unsigned long long seq;
+      PgxTicket tk = ticket_publish(h, &seq, 2);
+      step_nb = pgxk_axpy_norms(h->st, n2, h->dx, h->xw, h->partials2, h->d_small + 2, &tk);
+    } else if (fstep)
       step_nb = pgxk_axpy_norms(h->st, n2, h->dx, h->xw, h->partials2);
     else
       pgxk_axpy(h->st, n2, 1.0, h->dx, h->xw);
@@ -3700,7 +3882,10 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
       rsn = PGX_SNES_CONVERGED_FNORM_RELATIVE;
     } else {
       double snorm, xnorm;
-      if (fstep) {
+      if (fstep_tk) {  // published by the step's launch, which completed before the residual norm's did
+        snorm = std::sqrt(h->h_small[2]);
+        xnorm = std::sqrt(h->h_small[3]);
+      } else if (fstep) {
         if ((rc = reduce_fetch(h, step_nb, h->partials2, 2, h->d_small, 0))) return rc;
         snorm = std::sqrt(h->h_small[0]);
         xnorm = std::sqrt(h->h_small[1]);

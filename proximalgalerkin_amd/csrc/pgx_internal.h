@@ -147,6 +147,7 @@ void pgxk_scale_copy(hipStream_t st, size_t len, double a, const double* x, doub
 void pgxk_scale_copy_f32(hipStream_t st, size_t len, double a, const double* x, float* y);  // y = (float)(a x)
 void pgxk_set(hipStream_t st, size_t len, double a, double* y);
 void pgxk_to_float(hipStream_t st, size_t len, const double* x, float* y);
+void pgxk_fill_hash(hipStream_t st, size_t len, unsigned long long seed, double* y, float* yf);  // yf != nullptr: floats to yf
 // out[i] = V_i . w, i<nv (V_i = V + i*ldv).  partials: [PGX_RED_BLOCKS * nv] scratch
 #define PGX_RED_BLOCKS 1024
 // scale != nullptr: out[i] = scale->s[i] * (V_i . w)  (nv <= PGX_DOT_SCALE_MAX)
@@ -154,13 +155,34 @@ void pgxk_to_float(hipStream_t st, size_t len, const double* x, float* y);
 struct PgxDotScale {
   double s[PGX_DOT_SCALE_MAX];
 };
+// Second stage of a two-stage reduction inside its producer launch (PGX_TICKET_REDUCE): thread 0 of every block
+// stores the block's partials write-through, then draws a ticket (agent-scope fetch_add, in two levels: pgx_kernels.hip, tk_arrive); the
+// block that draws the last one sums all partials in the shape of the second-stage kernels (k_reduce_partials[_scaled],
+// k_reduce_publish) and writes their results.  No block waits for another.  ctr: PGX_TK_WORDS words, zero when the handle is created
+// and zero again after every launch that ran to its end; launches that share them must share a stream.
+// hout != nullptr: the reducer also does what k_reduce_publish does - results -> hout, src1[0 .. n1) -> dst1 (mapped host memory),
+// then the sequence word.
+#define PGX_TK_SHARDS 64
+#define PGX_TK_STRIDE 16  // words from counter to counter: a 128-byte line each
+#define PGX_TK_WORDS ((PGX_TK_SHARDS + 1) * PGX_TK_STRIDE)
+struct PgxTicket {
+  unsigned long long* ctr = nullptr;  // device; nullptr: no second stage in this launch
+  double* hout = nullptr;
+  int n1 = 0;
+  const double* src1 = nullptr;
+  double* dst1 = nullptr;
+  unsigned long long seq = 0;
+  unsigned long long* seqp = nullptr;
+};
 // wide: vectors per launch (8 or 16); out == nullptr: no second stage, partials[0 .. pgxk_multidot_blocks(len) * nv) stay for the caller
-void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
-                   double* out, const PgxDotScale* scale = nullptr, int wide = 8);
+// tk != nullptr (out too): the last chunk's launch carries the second stage and no launch follows it - returns true; false: the
+// instantiation does not carry it (pgx_kernels.hip, tk_dot_fits) or tk == nullptr, and the second-stage launch has run as without tk
+bool pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
+                   double* out, const PgxDotScale* scale = nullptr, int wide = 8, PgxTicket* tk = nullptr);
 // the same against a FLOAT basis (fgmres: the lean P1 path), widened to fp64 as it is read; ldv in floats, a multiple of 4.  The vector is
 // fp64 (w) or, w == nullptr, a float one (wf: the stored next basis vector, second projection).  Same grid, partials and second stage.
-void pgxk_multidot_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* w, const float* wf, double* partials,
-                       double* out, const PgxDotScale* scale = nullptr, int wide = 8);
+bool pgxk_multidot_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* w, const float* wf, double* partials,
+                       double* out, const PgxDotScale* scale = nullptr, int wide = 8, PgxTicket* tk = nullptr);
 int pgxk_multidot_blocks(size_t len);
 int pgxk_stream_blocks(size_t len);  // grid of the streaming vector kernels (pgxk_multiaxpy_norm's partials)
 // out[r] = sum of row r of partials ([nrows][nb]) in the shape of k_reduce_rows, then out[0 .. nrows) -> hout and src1[0 .. n1) -> dst1
@@ -168,12 +190,14 @@ int pgxk_stream_blocks(size_t len);  // grid of the streaming vector kernels (pg
 void pgxk_reduce_publish(hipStream_t st, int nb, const double* partials, int nrows, double* out, double* hout, int n1, const double* src1,
                          double* dst1, unsigned long long seq, unsigned long long* seqp);
 // y += x; partials <- the block sums of |x|^2 (row 0) and |y + x|^2 (row 1), rows of the returned length
-int pgxk_axpy_norms(hipStream_t st, size_t len, const double* x, double* y, double* partials);
+// tk != nullptr: the launch carries the second stage, out[0 .. 2) <- the two sums (and the publish of tk)
+int pgxk_axpy_norms(hipStream_t st, size_t len, const double* x, double* y, double* partials, double* out = nullptr, PgxTicket* tk = nullptr);
 // w -= sum_i h[i] V_i   (h is a DEVICE pointer to nv doubles)
 void pgxk_multiaxpy(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w);
 // x = sum_i y[i] Z_i  (y device pointer); accumulate!=0 -> x += ...
+// yhost != nullptr (nv <= PGX_DOT_SCALE_MAX): the coefficients travel by value with the launch, y is not read
 void pgxk_lincomb(hipStream_t st, size_t len, int nv, const double* Z, size_t ldz, const double* y, double* x,
-                  int accumulate);
+                  int accumulate, const double* yhost = nullptr);
 
 // multigrid on stencil levels
 void pgxk_csr_to_stencil(hipStream_t st, int n, int sx, const int32_t* rowptr, const int32_t* colm, const double* vals,
@@ -201,7 +225,7 @@ void pgxk_st_spmv(hipStream_t st, const GridLevel& L, double alpha, const double
                   double* yp, const float2* xf = nullptr /* the iterate as ONE interleaved (u, psi) float2 field instead of (xu, xp); uniform levels only */,
                   const double* bu = nullptr, const double* bp = nullptr, double s = 1.0 /* bu: y = s (bu, bp) - J x (uniform levels, xf == nullptr) */);
 void pgxk_lincomb_f2(hipStream_t st, size_t n, int nv, const float2* Zf, size_t ldz, const double* y, double* xu, double* xp,
-                     int accumulate = 1);
+                     int accumulate = 1, const double* yhost = nullptr);
 void pgxk_pack_d4(hipStream_t st, const GridLevel& L);  // Dd4 <- Dh
 void pgxk_st_resid_restrict(hipStream_t st, const GridLevel& L, double alpha, const double* xu, const double* xp,
                             const double* bu, const double* bp, const GridLevel& C, int remap, double* cbu,
@@ -304,13 +328,15 @@ void pgxk_axpy_dot(hipStream_t st, size_t len, int nv, const double* V, size_t l
 void pgxk_multiaxpy_scale(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h,
                           double scale, double* w);
 // w -= V h and out[0] = |w'|^2 in one pass over the basis (selective CGS2: the lean second pass)
-void pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w,
-                         double* partials, double* out, int wide = 8);
+bool pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w,
+                         double* partials, double* out, int wide = 8, PgxTicket* tk = nullptr);
+// (tk != nullptr, out too: true - the last chunk's launch has summed into out and published; false - this instantiation does not carry
+// the second stage, the partials wait for the caller as with out == nullptr)
 // float basis: w' = w - V h leaves as vnext = (float) w' and out[0] = |vnext|^2, the norm of the ROUNDED vector.  More than `wide`
 // vectors: the chunks before the last keep w' in the fp64 scratch w.  from_vnext != 0: the vector projected is vnext itself
 // (second projection), w is scratch only
-void pgxk_multiaxpy_norm_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* h, int from_vnext, double* w,
-                             float* vnext, double* partials, double* out, int wide = 8);
+bool pgxk_multiaxpy_norm_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* h, int from_vnext, double* w,
+                             float* vnext, double* partials, double* out, int wide = 8, PgxTicket* tk = nullptr);
 // ---- single-precision V-cycle legs (pgx_mg32.hip) ----
 // Dq <- Dh (values above 1e30 are clamped: an overshot Newton iterate must not put infinities into the preconditioner)
 void pgxk_f_pack_d(hipStream_t st, const GridLevel& L);

@@ -1390,15 +1390,140 @@ __device__ __forceinline__ void gs_st(float* p, const double* a, double* s) {
   *(vf*)p = v;
 }
 
+// y[i] (or yf[i], as float) = a value in [-1, 1) that depends on (seed, i) only (splitmix64): test data of pgx_reduce_selfcheck
+__global__ void __launch_bounds__(PGX_BLOCK) k_fill_hash(size_t len, unsigned long long seed, double* __restrict__ y, float* __restrict__ yf) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < len; i += (size_t)gridDim.x * blockDim.x) {
+    unsigned long long z = seed * 0x9E3779B97F4A7C15ull + (i + 1) * 0xD1B54A32D192ED03ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    const double v = (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+    if (yf)
+      yf[i] = (float)v;
+    else
+      y[i] = v;
+  }
+}
+void pgxk_fill_hash(hipStream_t st, size_t len, unsigned long long seed, double* y, float* yf) {
+  hipLaunchKernelGGL(k_fill_hash, stream_grid(len), dim3(PGX_BLOCK), 0, st, len, seed, y, yf);
+}
+
+// ---- the second stage of a reduction in the launch that produced the partials (PgxTicket, pgx_internal.h) ----
+// Partials pass from block to block inside ONE launch, and the L2s of the eight XCDs are not coherent: thread 0 stores them
+// write-through (agent scope), waits until they have left, and only then draws the block's ticket; the block that draws the last
+// ticket reads every partial with agent-scope loads, which no L1 serves.  Several blocks share a CU here, so that block also
+// invalidates its CU's L1 once (agent-scope acquire) before it reads.  Nobody waits: a block that is not last is done.
+__device__ __forceinline__ void tk_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double tk_load(const double* p) {
+  return __hip_atomic_load(const_cast<double*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// every thread calls it after thread 0 has stored the block's partials with tk_store; true in all threads of the last block to arrive.
+// Tickets in two levels: one word takes about 88 returning adds per microsecond, which 4096 blocks finishing together would wait 46 us
+// for, so block b draws from shard b % S (S = min(grid, PGX_TK_SHARDS), each shard on a 128-byte line of its own) and only the last
+// block of a shard draws from the top word.  Whoever draws a counter's last ticket sets it back to zero: the next launch is ordered
+// behind this one by the stream and finds all counters as pgx_create left them.
+// sm: the block's block_sum array (its last reader was thread 0; the next block_sum starts behind a barrier)
+__device__ __forceinline__ bool tk_arrive(const PgxTicket& tk, double* sm) {
+  if (threadIdx.x == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partials are out before the ticket is drawn (kept explicit: the compiler
+                                                      // may not see why the wait matters)
+    const unsigned nb = gridDim.x, S = nb < PGX_TK_SHARDS ? nb : PGX_TK_SHARDS, sh = blockIdx.x % S;
+    const unsigned long long quota = nb / S + (sh < nb % S ? 1u : 0u);
+    unsigned long long* const shard = tk.ctr + (size_t)(1 + sh) * PGX_TK_STRIDE;
+    bool last = false;
+    if (__hip_atomic_fetch_add(shard, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == quota - 1) {
+      __hip_atomic_store(shard, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (__hip_atomic_fetch_add(tk.ctr, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned long long)S - 1) {
+        __hip_atomic_store(tk.ctr, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = true;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the invalidate has completed before the barrier releases the other waves
+      }
+    }
+    sm[0] = last ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  return sm[0] != 0.0;
+}
+// The rows of a [nrows][nb] array (rs = nb, bs = 1) or the columns of a [nb][nrows] one (bs = nrows, rs = 1) -> out[0 .. nrows), each
+// times sc.s[r] where scaled.  Row by row in the shape of k_reduce_partials / k_reduce_rows / k_reduce_publish: thread t adds p[t],
+// p[t + 256], ... in that order, then block_sum.  nb <= K * 256 (the caps of the grids); the D * K loads of D rows are in flight
+// together.  Element b of row r sits at p[b * bs + r * rs] (32-bit byte offsets: one register per address; a lane past the row's end
+// re-reads the row's last element and does not add it, so the loads stand in straight-line code).
+// With tk.hout the results and tk.src1 go to the host and the sequence word is set, all as k_reduce_publish does it.  Called by every
+// thread of the last block.
+template <int D, int K>
+__device__ __forceinline__ void tk_finish(const PgxTicket& tk, int nb, const double* p, unsigned bs, unsigned rs, int nrows,
+                                          int scaled, const PgxDotScale& sc, double* out, double* sm) {
+  unsigned tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));  // nothing below is computed ahead of the producer's streaming loop, where it would hold registers
+  for (int r0 = 0; r0 < nrows; r0 += D) {
+    double x[D][K];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const unsigned r = min(r0 + d, nrows - 1);  // (a row past the end: the last one again, not summed)
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const unsigned b = min(tid + k * PGX_BLOCK, (unsigned)nb - 1u);
+        x[d][k] = tk_load((const double*)((const char*)p + (b * bs + r * rs) * (unsigned)sizeof(double)));
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const int r = r0 + d;
+      if (r >= nrows) break;  // uniform
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if ((int)(tid + k * PGX_BLOCK) < nb) s += x[d][k];
+      double t = block_sum(s, sm);
+      if (threadIdx.x == 0) {
+        if (scaled) t *= sc.s[r];
+        out[r] = t;
+        if (tk.hout) __hip_atomic_store(tk.hout + r, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+  }
+  if (!tk.hout || threadIdx.x >= WAVE) return;
+  for (int i = threadIdx.x; i < tk.n1; i += WAVE) __hip_atomic_store(tk.dst1 + i, tk.src1[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __threadfence_system();  // one wave: every lane's stores are ordered before lane 0's flag store below
+  if (threadIdx.x == 0) __hip_atomic_store(tk.seqp, tk.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+template <int D, int K>
+__device__ __forceinline__ void tk_finish(const PgxTicket& tk, int nb, const double* p, unsigned bs, unsigned rs, int nrows, double* out,
+                                          double* sm) {
+  tk_finish<D, K>(tk, nb, p, bs, rs, nrows, 0, PgxDotScale(), out, sm);
+}
+
 // out[i] = V_i . w : each block streams a slice of w ONCE for NV vectors (Gram-Schmidt is the
 // second-largest HBM consumer of the Newton solve; batching cuts its traffic from 2 to 1+1/NV
 // vector reads per dot product).  Two-stage, fixed grid -> bitwise reproducible.
 // VT: element type of the basis (fp64, or the float basis of the lean P1 path); WT: that of w.  Products and sums are fp64.
 // ng = len / G groups, tail = len - G ng (0 or 2; always 0 for an fp64 basis), ldv in elements.
-template <int NV, class VT, class WT>
+// TK (tk.ctr != nullptr): the last block to arrive sums ALL pstride columns of partials (those of earlier chunk launches are ordered
+// by the stream) into out, times sc.s[v] where scaled: what k_reduce_partials[_scaled] would leave.  Without TK the four arguments
+// behind poff are not read and the code is the two-launch kernel's.
+#define PGX_TK_D 4  // rows of partials in flight in the second stage of k_multidot
+// Which instantiations carry the second stage: those it costs neither a wave per SIMD nor the SGPR budget of eight workgroups per CU
+// (<= 80).  With a float basis and more than 10 vectors k_multidot's streaming loop is scheduled into 66-82 VGPRs (48-58 without) and
+// k_multiaxpy_norm takes 84-92 SGPRs (66-74): those launches keep the second-stage launch.
+template <class VT>
+static constexpr bool tk_fits(int nv) {
+  return std::is_same<VT, double>::value || nv <= 10;
+}
+// k_multidot on top of that: thread 0 stores one partial per vector and the last block reads 1024 per vector, which grows with the
+// number of vectors where the launch it replaces (k_reduce_partials_scaled, one block per vector) does not.  In the trace of a 2048^2
+// solve the ticketed launch is 3.0-4.3 us longer up to 4 vectors and 5.9-10.8 us from 5 to 10, against 4.7 us of that launch and its
+// boundary: up to 4 vectors.
+template <class VT>
+static constexpr bool tk_dot_fits(int nv) {
+  return tk_fits<VT>(nv) && nv <= 4;
+}
+template <int NV, class VT, class WT, bool TK>
 __global__ void __launch_bounds__(PGX_BLOCK) k_multidot(size_t ng, int tail, const VT* __restrict__ V, size_t ldv,
                                                         const WT* __restrict__ w,
-                                                        double* __restrict__ partials, int pstride, int poff) {
+                                                        double* __restrict__ partials, int pstride, int poff, double* out, int scaled,
+                                                        PgxDotScale sc, PgxTicket tk) {
   constexpr int G = GsLane<VT>::G;
   __shared__ double sm[PGX_BLOCK / WAVE];
   double acc[NV];
@@ -1430,8 +1555,16 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_multidot(size_t ng, int tail, con
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     const double r = block_sum(acc[v], sm);
-    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * pstride + poff + v] = r;
+    if (threadIdx.x == 0) {
+      double* const pv = partials + (size_t)blockIdx.x * pstride + poff + v;
+      if (TK)
+        tk_store(pv, r);
+      else
+        *pv = r;
+    }
   }
+  if constexpr (TK)
+    if (tk_arrive(tk, sm)) tk_finish<PGX_TK_D, PGX_RED_BLOCKS / PGX_BLOCK>(tk, (int)gridDim.x, partials, (unsigned)pstride, 1u, pstride, scaled, sc, out, sm);
 }
 
 __global__ void __launch_bounds__(PGX_BLOCK) k_reduce_partials(int nblocks, int nv, const double* __restrict__ p,
@@ -1461,8 +1594,8 @@ int pgxk_multidot_blocks(size_t len) {
 }
 
 template <class VT, class WT>
-static void multidot_t(hipStream_t st, size_t len, int nv, const VT* V, size_t ldv, const WT* w, double* partials, double* out,
-                       const PgxDotScale* scale, int wide) {
+static bool multidot_t(hipStream_t st, size_t len, int nv, const VT* V, size_t ldv, const WT* w, double* partials, double* out,
+                       const PgxDotScale* scale, int wide, PgxTicket* tk) {
   constexpr int G = GsLane<VT>::G;
   const size_t ng = len / G;
   const int tail = (int)(len - G * ng);
@@ -1470,14 +1603,27 @@ static void multidot_t(hipStream_t st, size_t len, int nv, const VT* V, size_t l
   dim3 grid((unsigned)nb), block(PGX_BLOCK);
   const int cap = wide > 16 ? 16 : wide < 1 ? 1 : wide;
   int done = 0;
+  static const PgxDotScale no_scale = {};
+  const PgxDotScale& sc = scale ? *scale : no_scale;
+  const int last_take = nv % cap ? nv % cap : cap;
+  const bool ticketed = tk && out && nv > 0 && tk_dot_fits<VT>(last_take);
   while (done < nv) {
     const int rem = nv - done;
     const VT* Vp = V + (size_t)done * ldv;
+    PgxTicket t;  // ctr == nullptr: no second stage in this launch
+    if (ticketed && rem <= cap) t = *tk;
     // one launch per chunk of at most `wide` (8 or 16) vectors, the last chunk of EXACTLY the remaining size: w is read once per
     // chunk (the 8/4/2/1 split of rounds 1-3 read it up to three times); the per-vector partials do not depend on the grouping
 #define PGX_MD(N)                                                                                                          \
   case N:                                                                                                                  \
-    hipLaunchKernelGGL((k_multidot<N, VT, WT>), grid, block, 0, st, ng, tail, Vp, ldv, w, partials, nv, done);             \
+    if constexpr (tk_dot_fits<VT>(N))                                                                                      \
+      if (t.ctr) {                                                                                                         \
+        hipLaunchKernelGGL((k_multidot<N, VT, WT, true>), grid, block, 0, st, ng, tail, Vp, ldv, w, partials, nv, done, out,  \
+                           scale ? 1 : 0, sc, t);                                                                          \
+        break;                                                                                                             \
+      }                                                                                                                    \
+    hipLaunchKernelGGL((k_multidot<N, VT, WT, false>), grid, block, 0, st, ng, tail, Vp, ldv, w, partials, nv, done, out, 0,  \
+                       no_scale, t);                                                                                       \
     break
     const int take = rem >= cap ? cap : rem;
     switch (take) {
@@ -1501,22 +1647,21 @@ static void multidot_t(hipStream_t st, size_t len, int nv, const VT* V, size_t l
 #undef PGX_MD
     done += take;
   }
-  if (!out) return;  // the caller runs the second stage itself (pgxk_reduce_publish)
+  if (!out || ticketed) return ticketed;  // the caller runs the second stage itself (pgxk_reduce_publish) / the last launch has run it
   if (scale)
     hipLaunchKernelGGL(k_reduce_partials_scaled, dim3(nv), block, 0, st, (int)nb, nv, partials, *scale, out);
   else
     hipLaunchKernelGGL(k_reduce_partials, dim3(nv), block, 0, st, (int)nb, nv, partials, out);
+  return false;
 }
-void pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
-                   double* out, const PgxDotScale* scale, int wide) {
-  multidot_t(st, len, nv, V, ldv, w, partials, out, scale, wide);
+bool pgxk_multidot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* w, double* partials,
+                   double* out, const PgxDotScale* scale, int wide, PgxTicket* tk) {
+  return multidot_t(st, len, nv, V, ldv, w, partials, out, scale, wide, tk);
 }
-void pgxk_multidot_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* w, const float* wf,
-                       double* partials, double* out, const PgxDotScale* scale, int wide) {
-  if (w)
-    multidot_t(st, len, nv, V, ldv, w, partials, out, scale, wide);
-  else
-    multidot_t(st, len, nv, V, ldv, wf, partials, out, scale, wide);
+bool pgxk_multidot_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* w, const float* wf,
+                       double* partials, double* out, const PgxDotScale* scale, int wide, PgxTicket* tk) {
+  if (w) return multidot_t(st, len, nv, V, ldv, w, partials, out, scale, wide, tk);
+  return multidot_t(st, len, nv, V, ldv, wf, partials, out, scale, wide, tk);
 }
 
 // The second stage of a two-stage reduction and the read-back of its result in ONE one-block launch: rows of nb partials are
@@ -1551,8 +1696,10 @@ void pgxk_reduce_publish(hipStream_t st, int nb, const double* partials, int nro
 // y += x and the block's shares of |x|^2 and |y'|^2 in one pass (the Newton update and the two norms of its step test).  Grid,
 // per-thread order and block_sum are those of k_multidot<1>, the element update is k_axpy's with a = 1: both sums and y are
 // bitwise what k_axpy followed by two k_multidot<1> give.  partials: [2][gridDim.x], rows for pgxk_reduce_publish.
+// TK (tk.ctr != nullptr): the last block to arrive sums the two rows into out[0 .. 2) and publishes them, as k_reduce_publish would
+template <bool TK>
 __global__ void __launch_bounds__(PGX_BLOCK) k_axpy_norms(size_t len2, double a, const double2* __restrict__ x, double2* __restrict__ y,
-                                                          double* __restrict__ partials) {
+                                                          double* __restrict__ partials, double* out, PgxTicket tk) {
   __shared__ double sm[PGX_BLOCK / WAVE];
   double accx = 0.0, accy = 0.0;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < len2; i += (size_t)gridDim.x * blockDim.x) {
@@ -1566,13 +1713,25 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_axpy_norms(size_t len2, double a,
   const double rx = block_sum(accx, sm);
   const double ry = block_sum(accy, sm);
   if (threadIdx.x == 0) {
-    partials[blockIdx.x] = rx;
-    partials[gridDim.x + blockIdx.x] = ry;
+    if (TK) {
+      tk_store(partials + blockIdx.x, rx);
+      tk_store(partials + gridDim.x + blockIdx.x, ry);
+    } else {
+      partials[blockIdx.x] = rx;
+      partials[gridDim.x + blockIdx.x] = ry;
+    }
   }
+  if constexpr (TK)
+    if (tk_arrive(tk, sm)) tk_finish<2, PGX_RED_BLOCKS / PGX_BLOCK>(tk, (int)gridDim.x, partials, 1u, gridDim.x, 2, out, sm);
 }
-int pgxk_axpy_norms(hipStream_t st, size_t len, const double* x, double* y, double* partials) {
+int pgxk_axpy_norms(hipStream_t st, size_t len, const double* x, double* y, double* partials, double* out, PgxTicket* tk) {
   const int nb = pgxk_multidot_blocks(len);
-  hipLaunchKernelGGL(k_axpy_norms, dim3(nb), dim3(PGX_BLOCK), 0, st, len / 2, 1.0, (const double2*)x, (double2*)y, partials);
+  PgxTicket t;
+  if (tk && out) t = *tk;
+  if (t.ctr)
+    hipLaunchKernelGGL(k_axpy_norms<true>, dim3(nb), dim3(PGX_BLOCK), 0, st, len / 2, 1.0, (const double2*)x, (double2*)y, partials, out, t);
+  else
+    hipLaunchKernelGGL(k_axpy_norms<false>, dim3(nb), dim3(PGX_BLOCK), 0, st, len / 2, 1.0, (const double2*)x, (double2*)y, partials, out, t);
   return nb;
 }
 
@@ -1727,11 +1886,11 @@ void pgxk_multiaxpy_scale(hipStream_t st, size_t len, int nv, const double* V, s
 // updated in place.  With a float basis the vector is read as WT from win and leaves as OT: the LAST chunk (NORM) stores (float) w' -
 // the next basis vector - and sums the squares of the ROUNDED values, so the norm is that of the vector stored; a chunk before it
 // leaves w' in fp64 (the scratch w), whatever it read: the result does not depend on the chunking.  WT == OT: in place, win unused.
-template <int NV, bool NORM, class VT, class WT>
+template <int NV, bool NORM, class VT, class WT, bool TK = false>
 __global__ void __launch_bounds__(PGX_BLOCK) k_multiaxpy_norm(size_t ng, int tail, const VT* __restrict__ V, size_t ldv,
                                                               const double* __restrict__ h, const WT* __restrict__ win,
                                                               typename std::conditional<NORM && std::is_same<VT, float>::value, float, double>::type* __restrict__ wout,
-                                                              double* __restrict__ partials) {
+                                                              double* __restrict__ partials, double* out, PgxTicket tk) {
   typedef typename std::conditional<NORM && std::is_same<VT, float>::value, float, double>::type OT;
   constexpr int G = GsLane<VT>::G;
   const WT* const wi = std::is_same<WT, OT>::value ? (const WT*)wout : win;
@@ -1772,47 +1931,72 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_multiaxpy_norm(size_t ng, int tai
   }
   if (NORM) {
     const double r = block_sum(acc, sm);
-    if (threadIdx.x == 0) partials[blockIdx.x] = r;
+    if (threadIdx.x == 0) {
+      if (TK)
+        tk_store(partials + blockIdx.x, r);
+      else
+        partials[blockIdx.x] = r;
+    }
+    // TK (tk.ctr != nullptr): the last block to arrive leaves |w'|^2 in out[0] and publishes it with tk.src1 (h1), as k_reduce_publish
+    // would; without TK out and tk are not read
+    if constexpr (TK)
+      if (tk_arrive(tk, sm)) tk_finish<1, 16>(tk, (int)gridDim.x, partials, 1u, gridDim.x, 1, out, sm);
   }
 }
 int pgxk_stream_blocks(size_t len) { return (int)stream_grid(len / 2).x; }
 // one chunk of N vectors; inf: the vector is read as float from wf (the stored next basis vector: second projection), else as fp64 from w
 template <int N, class VT>
 static void launch_multiaxpy_norm(hipStream_t st, dim3 grid, size_t ng, int tail, const VT* Vp, size_t ldv, const double* h, bool last,
-                                  bool inf, double* w, float* wf, double* partials) {
+                                  bool inf, double* w, float* wf, double* partials, double* out, const PgxTicket& tk) {
   const dim3 block(PGX_BLOCK);
   if constexpr (std::is_same<VT, double>::value) {
-    if (last)
-      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, double, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials);
-    else
-      hipLaunchKernelGGL((k_multiaxpy_norm<N, false, double, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials);
-  } else {
-    if (last && inf)
-      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, float, float>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const float*)nullptr, wf, partials);
+    if (last && tk.ctr)  // (tk_fits: every N)
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, double, double, true>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials, out, tk);
     else if (last)
-      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, float, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)w, wf, partials);
-    else if (inf)
-      hipLaunchKernelGGL((k_multiaxpy_norm<N, false, float, float>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const float*)wf, w, partials);
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, double, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials, out, tk);
     else
-      hipLaunchKernelGGL((k_multiaxpy_norm<N, false, float, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials);
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, false, double, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials, out, tk);
+  } else {
+    if constexpr (tk_fits<VT>(N))
+      if (last && tk.ctr) {
+        if (inf)
+          hipLaunchKernelGGL((k_multiaxpy_norm<N, true, float, float, true>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const float*)nullptr, wf, partials, out, tk);
+        else
+          hipLaunchKernelGGL((k_multiaxpy_norm<N, true, float, double, true>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)w, wf, partials, out, tk);
+        return;
+      }
+    if (last && inf)
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, float, float>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const float*)nullptr, wf, partials, out, tk);
+    else if (last)
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, true, float, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)w, wf, partials, out, tk);
+    else if (inf)
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, false, float, float>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const float*)wf, w, partials, out, tk);
+    else
+      hipLaunchKernelGGL((k_multiaxpy_norm<N, false, float, double>), grid, block, 0, st, ng, tail, Vp, ldv, h, (const double*)nullptr, w, partials, out, tk);
   }
 }
 template <class VT>
-static void multiaxpy_norm_t(hipStream_t st, size_t len, int nv, const VT* V, size_t ldv, const double* h, bool inf, double* w, float* wf,
-                             double* partials, double* out, int wide) {
+static bool multiaxpy_norm_t(hipStream_t st, size_t len, int nv, const VT* V, size_t ldv, const double* h, bool inf, double* w, float* wf,
+                             double* partials, double* out, int wide, PgxTicket* tk) {
   constexpr int G = GsLane<VT>::G;
   const size_t ng = len / G;
   const int tail = (int)(len - G * ng);
   dim3 grid = stream_grid(len / 2);
   const int cap = wide > 16 ? 16 : wide < 1 ? 1 : wide;
   int done = 0;
+  bool ticketed = false;
   while (done < nv) {
     const int step = std::min(cap, nv - done);
     const bool last = done + step == nv;
     const VT* Vp = V + (size_t)done * ldv;
+    PgxTicket t;  // ctr == nullptr: no second stage in this launch
+    if (tk && out && last && tk_fits<VT>(step)) {
+      ticketed = true;
+      t = *tk;
+    }
 #define PGX_MAN(N)                                                                                                     \
   case N:                                                                                                              \
-    launch_multiaxpy_norm<N>(st, grid, ng, tail, Vp, ldv, h + done, last, inf && done == 0, w, wf, partials);          \
+    launch_multiaxpy_norm<N>(st, grid, ng, tail, Vp, ldv, h + done, last, inf && done == 0, w, wf, partials, out, t);  \
     break
     switch (step) {
       PGX_MAN(16);
@@ -1830,22 +2014,23 @@ static void multiaxpy_norm_t(hipStream_t st, size_t len, int nv, const VT* V, si
       PGX_MAN(4);
       PGX_MAN(3);
       PGX_MAN(2);
-      default: launch_multiaxpy_norm<1>(st, grid, ng, tail, Vp, ldv, h + done, last, inf && done == 0, w, wf, partials); break;
+      default: launch_multiaxpy_norm<1>(st, grid, ng, tail, Vp, ldv, h + done, last, inf && done == 0, w, wf, partials, out, t); break;
     }
 #undef PGX_MAN
     done += step;
   }
-  if (out) hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(PGX_BLOCK), 0, st, (int)grid.x, partials, out);
+  if (out && !tk) hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(PGX_BLOCK), 0, st, (int)grid.x, partials, out);
+  return ticketed;  // tk != nullptr and false: the block partials wait for the caller's second stage, as with out == nullptr
 }
 // out[0] = |w - V h|^2, w updated in place.  partials: >= pgxk_stream_blocks(len) doubles.  out == nullptr: the block partials
 // stay in partials[0 .. pgxk_stream_blocks(len)) for the caller's own second stage (pgxk_reduce_publish)
-void pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w,
-                         double* partials, double* out, int wide) {
-  multiaxpy_norm_t(st, len, nv, V, ldv, h, false, w, nullptr, partials, out, wide);
+bool pgxk_multiaxpy_norm(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w,
+                         double* partials, double* out, int wide, PgxTicket* tk) {
+  return multiaxpy_norm_t(st, len, nv, V, ldv, h, false, w, nullptr, partials, out, wide, tk);
 }
-void pgxk_multiaxpy_norm_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* h, int from_vnext, double* w,
-                             float* vnext, double* partials, double* out, int wide) {
-  multiaxpy_norm_t(st, len, nv, V, ldv, h, from_vnext != 0, w, vnext, partials, out, wide);
+bool pgxk_multiaxpy_norm_f32(hipStream_t st, size_t len, int nv, const float* V, size_t ldv, const double* h, int from_vnext, double* w,
+                             float* vnext, double* partials, double* out, int wide, PgxTicket* tk) {
+  return multiaxpy_norm_t(st, len, nv, V, ldv, h, from_vnext != 0, w, vnext, partials, out, wide, tk);
 }
 
 void pgxk_multiaxpy(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h, double* w) {
@@ -1871,15 +2056,17 @@ void pgxk_multiaxpy(hipStream_t st, size_t len, int nv, const double* V, size_t 
   }
 }
 
-// x (+)= sum_i y[i] Z_i
+// x (+)= sum_i y[i] Z_i.  BYVAL: the coefficients are yc.s[0 .. nv), arguments of the launch (as PgxDotScale is passed), and y is not
+// read: no upload of y ahead of the launch
+template <bool BYVAL>
 __global__ void __launch_bounds__(PGX_BLOCK) k_lincomb(size_t len2, int nv, const double2* __restrict__ Z,
-                                                       size_t ldz2, const double* __restrict__ y,
+                                                       size_t ldz2, const double* __restrict__ y, PgxDotScale yc,
                                                        double2* __restrict__ x, int accumulate) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < len2; i += (size_t)gridDim.x * blockDim.x) {
     double2 s = accumulate ? x[i] : make_double2(0.0, 0.0);
     for (int v = 0; v < nv; ++v) {
       const double2 a = Z[v * ldz2 + i];
-      const double yv = y[v];
+      const double yv = BYVAL ? yc.s[v] : y[v];
       s.x += yv * a.x;
       s.y += yv * a.y;
     }
@@ -1887,14 +2074,15 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_lincomb(size_t len2, int nv, cons
   }
 }
 // (xu, xp)[v] (+)= sum_i y[i] Zf_i[v] for float2-interleaved Z_i (see st_load_x): the solution update of a cycle whose Z_j are float
+template <bool BYVAL>
 __global__ void __launch_bounds__(PGX_BLOCK) k_lincomb_f2(size_t n, int nv, const float2* __restrict__ Zf, size_t ldz,
-                                                          const double* __restrict__ y, double* __restrict__ xu, double* __restrict__ xp,
-                                                          int accumulate) {
+                                                          const double* __restrict__ y, PgxDotScale yc, double* __restrict__ xu,
+                                                          double* __restrict__ xp, int accumulate) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     double su = accumulate ? xu[i] : 0.0, sp = accumulate ? xp[i] : 0.0;
     for (int v = 0; v < nv; ++v) {
       const float2 a = Zf[v * ldz + i];
-      const double yv = y[v];
+      const double yv = BYVAL ? yc.s[v] : y[v];
       su += yv * (double)a.x;
       sp += yv * (double)a.y;
     }
@@ -1902,16 +2090,32 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_lincomb_f2(size_t n, int nv, cons
     xp[i] = sp;
   }
 }
+static PgxDotScale coef_arg(int nv, const double* yhost) {
+  PgxDotScale yc = {};
+  if (yhost) std::copy(yhost, yhost + nv, yc.s);
+  return yc;
+}
 void pgxk_lincomb_f2(hipStream_t st, size_t n, int nv, const float2* Zf, size_t ldz, const double* y, double* xu, double* xp,
-                     int accumulate) {
+                     int accumulate, const double* yhost) {
   const unsigned grid = (unsigned)std::min<size_t>((n + PGX_BLOCK - 1) / PGX_BLOCK, 256 * 32);
-  hipLaunchKernelGGL(k_lincomb_f2, dim3(grid), dim3(PGX_BLOCK), 0, st, n, nv, Zf, ldz, y, xu, xp, accumulate);
+  if (yhost && nv > PGX_DOT_SCALE_MAX) yhost = nullptr;
+  const PgxDotScale yc = coef_arg(nv, yhost);
+  if (yhost)
+    hipLaunchKernelGGL(k_lincomb_f2<true>, dim3(grid), dim3(PGX_BLOCK), 0, st, n, nv, Zf, ldz, y, yc, xu, xp, accumulate);
+  else
+    hipLaunchKernelGGL(k_lincomb_f2<false>, dim3(grid), dim3(PGX_BLOCK), 0, st, n, nv, Zf, ldz, y, yc, xu, xp, accumulate);
 }
 
 void pgxk_lincomb(hipStream_t st, size_t len, int nv, const double* Z, size_t ldz, const double* y, double* x,
-                  int accumulate) {
-  hipLaunchKernelGGL(k_lincomb, stream_grid(len / 2), dim3(PGX_BLOCK), 0, st, len / 2, nv, (const double2*)Z,
-                     ldz / 2, y, (double2*)x, accumulate);
+                  int accumulate, const double* yhost) {
+  if (yhost && nv > PGX_DOT_SCALE_MAX) yhost = nullptr;
+  const PgxDotScale yc = coef_arg(nv, yhost);
+  if (yhost)
+    hipLaunchKernelGGL(k_lincomb<true>, stream_grid(len / 2), dim3(PGX_BLOCK), 0, st, len / 2, nv, (const double2*)Z, ldz / 2, y, yc,
+                       (double2*)x, accumulate);
+  else
+    hipLaunchKernelGGL(k_lincomb<false>, stream_grid(len / 2), dim3(PGX_BLOCK), 0, st, len / 2, nv, (const double2*)Z, ldz / 2, y, yc,
+                       (double2*)x, accumulate);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1120,7 +1120,8 @@ __device__ __forceinline__ void f_rr_fast(int tx, int ty, const FRrArgs& A, floa
     const float d2 = lane_shr1f(dq[k].y), d4 = exch[(lj - 1) * W + lane].x, d6 = exch[(lj - 1) * W + lane - 1].y;
     const int q = lj * W + lane;
     // plain (merged) reads in these rows and in those of f_rr_bnd: with f_lds the compiler contracts the products of this kernel's
-    // rows into other FMA pairs and the residual changes in its last bits; the gathers below take f_lds
+    // rows into other FMA pairs and the residual changes in its last bits.  The gathers below are plain too:
+    // single reads there made this kernel slower (1.7 us on level 0), so k_f_resid_restrict is as it was before F32_LDS_SINGLE
     const float2 x0 = ximg[q], x1 = ximg[q + 1], x2 = ximg[q - 1], x3 = ximg[q + W], x4 = ximg[q - W], x5 = ximg[q + W + 1],
                  x6 = ximg[q - W - 1];
     const float u12 = x1.x + x2.x, u34 = x3.x + x4.x, u56 = x5.x + x6.x;
@@ -1135,7 +1136,8 @@ __device__ __forceinline__ void f_rr_fast(int tx, int ty, const FRrArgs& A, floa
   // row 2w + 1 (image rows start at fine row 2 J0 - 1) and column 2 lane + 2
   if (wave < CY && lane < CX) {
     const int q = (2 * wave + 1) * W + 2 * lane + 2;
-    F_LDS7(rimg, q, W, r0, r1, r2, r3, r4, r5, r6)
+    const float2 r0 = rimg[q], r1 = rimg[q + 1], r2 = rimg[q - 1], r3 = rimg[q + W], r4 = rimg[q - W], r5 = rimg[q + W + 1],
+                 r6 = rimg[q - W - 1];
     const float su = r0.x + 0.5f * (((r1.x + r2.x) + (r3.x + r4.x)) + (r5.x + r6.x));
     const float sp = r0.y + 0.5f * (((r1.y + r2.y) + (r3.y + r4.y)) + (r5.y + r6.y));
     const int C = (J0 + wave) * sxc + I0 + lane;
@@ -1211,7 +1213,8 @@ __device__ __forceinline__ void f_rr_bnd(int tx, int ty, int sub, const FRrArgs&
     const int I = I0 + lane, J = J0 + wave;
     if (I <= A.nxc && J <= A.nyc) {
       const int q = (2 * wave + 1) * W + 2 * lane + 2;
-      F_LDS7(rimg, q, W, r0, r1, r2, r3, r4, r5, r6)
+      const float2 r0 = rimg[q], r1 = rimg[q + 1], r2 = rimg[q - 1], r3 = rimg[q + W], r4 = rimg[q - W], r5 = rimg[q + W + 1],
+                   r6 = rimg[q - W - 1];
       float su = r0.x + 0.5f * (((r1.x + r2.x) + (r3.x + r4.x)) + (r5.x + r6.x));
       const float sp = r0.y + 0.5f * (((r1.y + r2.y) + (r3.y + r4.y)) + (r5.y + r6.y));
       const int C = J * sxc + I;

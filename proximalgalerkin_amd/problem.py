@@ -419,6 +419,14 @@ class NonlinearProblem:
         _lib.check(self._lib, self._h, self._lib.pgx_observables(self._h, _lib.dptr(out)), "pgx_observables")
         return out
 
+    def reduce_selfcheck(self, nv, length, basis_f32=False, reps=1, seed=0):
+        """Number of 8-byte words in which the two routes of the Krylov driver's reductions differ (include/pgx.h:
+        pgx_reduce_selfcheck); 0 is the only right answer."""
+        bad = C.c_int64(-1)
+        _lib.check(self._lib, self._h, self._lib.pgx_reduce_selfcheck(self._h, int(nv), int(length), int(bool(basis_f32)), int(reps),
+                                                                      int(seed), C.byref(bad)), "pgx_reduce_selfcheck")
+        return bad.value
+
     def owned_edge_range(self):
         """(offset, count): owned EDGE dofs within each field block of a P2 local vector (include/pgx.h: pgx_owned_edge_range)."""
         off, cnt = C.c_int64(0), C.c_int64(0)
