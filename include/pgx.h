@@ -237,6 +237,44 @@ int pgx_mg_level_export(pgx_handle* h, int level, int32_t* nx, int32_t* ny, doub
 int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, int in_form, int out_form, double scale, const double* b,
                      double* z);
 
+/* (pgx_mg_level_export also serves structured P2 handles: their levels are the P1 hierarchy below the P2 level, level 0 holding
+ * D = T^T D_P2 T, the coarse space of the two-level cycle.  pgx_vcycle_apply keeps its P1 precondition.) */
+
+/* ---- Test hooks of the P2 two-level preconditioner (pgx_api.hip: pcycle_p2_patch; pgx_patch.hip): patch_nu additive vertex-star
+ * sweeps | restriction to the P1 hierarchy | one P1 V-cycle | prolongation | patch_nu sweeps.  They replace nothing in the reference
+ * (which factorises the P2 Newton matrix as well, obstacle_pg.py:68-70,129-131): they let tests compare what the device stores and
+ * computes, stage by stage, with a numpy statement of the same algebra (tests/p2_cycle_reference.py).  Preconditions of all three: a
+ * single-GPU P2 handle with a patch smoother (vertex degree <= 7, PGX_P2_PATCH on), a filled Jacobian, not sharded, the sparse LU
+ * not active; anything else is PGX_ESTATE with a message, and nothing is launched.  None changes how a solve runs: they make the
+ * calls the cycle makes, on the cycle's own buffers. */
+/* out = { [0] slots per patch NN (7 or 8; a patch matrix has 2 NN rows),
+ *         [1] storage form of the inverses: 0 double full rows, 1 float full rows, 2 float symmetric packing, 3 bf16 symmetric packing,
+ *         [2] patch_nu (sweeps per leg),
+ *         [3] 1: the residual inside the cycle reads the float copy of D(psi),
+ *         [4] residual kernel of the cycle: 2 structured apply (interior) + CSR rows (frame), 1 nnz-balanced CSR, 0 plain CSR,
+ *         [5] Newton solves since create in which the patch cycle stagnated (p2_fallback_its Krylov iterations without convergence)
+ *             and the sparse LU took over,
+ *         [6] 1: kernel [4] = 1 reads K and M through its dictionary (values on a grid of 2^-40 of the largest entry),
+ *         [7] 1: the handle has the P1 grid hierarchy the whole cycle needs (stage 0 below) };  *patch_omega (may be NULL): damping
+ * of the sweeps.  Brings the patch data up to date for the current Jacobian, as the first cycle of a solve does. */
+int pgx_p2_cycle_info(pgx_handle* h, int32_t out[8], double* patch_omega);
+/* Host copies of the patch data of the current Jacobian (either may be NULL); nv patches, patch p = vertex p:
+ *   pdof [nv][NN]         dofs of the scalar space in the patch, slot 0 the vertex, then its edge dofs, -1 = unused slot
+ *   Ainv [nv][2NN][2NN]   the stored inverse, decoded exactly as k_patch_apply decodes it: entry (l, j) is the factor of r_j in row l,
+ *                         rows / columns = (u slots, psi slots).  Symmetric packing: the chunks at or left of a row's diagonal block
+ *                         as stored, the rest as the kernel mirrors them; bf16 words shifted up; float and double cast. */
+int pgx_p2_patch_export(pgx_handle* h, int32_t* pdof, double* Ainv);
+/* One stage of the cycle on host vectors ([u | psi] of the P2 space, 2 nd entries, unless stated), through the launches of the cycle:
+ *   stage 1  one sweep, z = x0 + sweep(b - J x0): the cycle's residual kernel, then the patch sweep; x0 == NULL: the first sweep of
+ *            a cycle (x = 0, r = b, no residual launch)
+ *   stage 2  the residual inside the cycle alone, z = b - J x0
+ *   stage 3  z [2 nv] = T^T b, the restriction to the P1 space (u rows of Dirichlet vertices 0)
+ *   stage 4  z = x0 + T b with b [2 nv] (x0 == NULL: 0), the prolongation
+ *   stage 0  the whole preconditioner, entered exactly as FGMRES enters it, with a V(nu, nu) cycle of damping omega below; needs
+ *            the grid hierarchy (PGX_ESTATE otherwise); x0 must be NULL
+ * nu and omega are read by stage 0 only (the sweeps use patch_nu and patch_omega of the handle). */
+int pgx_p2_cycle_apply(pgx_handle* h, int stage, int nu, double omega, const double* b, const double* x0, double* z);
+
 /* One nonlinear solve from device `sol` with proximal centre `sol_k`; on reason>0 `sol` is replaced. */
 int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* reason, int* its, int* lin_its);
 /* energy, |complementarity|, feasibility, dual feasibility, H1 increment, latent L2 increment */

@@ -370,6 +370,9 @@ SYMBOLS = [
     ("pgx_mg_level_export", C.c_int,
      [_H, C.c_int, c_int32_p, c_int32_p, c_double_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), c_int32_p, c_int32_p]),
     ("pgx_vcycle_apply", C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p]),
+    ("pgx_p2_cycle_info", C.c_int, [_H, c_int32_p, c_double_p]),
+    ("pgx_p2_patch_export", C.c_int, [_H, c_int32_p, c_double_p]),
+    ("pgx_p2_cycle_apply", C.c_int, [_H, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p]),
     ("pgx_spmv_select", C.c_int, [_H, C.c_int, C.POINTER(C.c_int)]),
     ("pgx_p2_stencil_info", C.c_int, [_H, C.POINTER(C.c_int32)]),
     ("pgx_comm_counts", C.c_int, [_H, C.POINTER(C.c_int64), C.c_int]),

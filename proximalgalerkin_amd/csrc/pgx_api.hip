@@ -2424,24 +2424,38 @@ static int ensure_patches(pgx_handle* h) {
   return PGX_OK;
 }
 
+// The two launches of a sweep of the cycle below, shared by it and by the test hook pgx_p2_cycle_apply.
+// Residual kernel of the cycle: 2 structured apply (pgx_p2st.hip; refreshes its copies of D once per Jacobian), 1 nnz-balanced CSR,
+// 0 plain CSR
+static int p2_cycle_resid_kind(pgx_handle* h) {
+  if (h->spmv_bal && p2st_ready(h)) return 2;
+  return (h->spmv_bal && h->s_blk) ? 1 : 0;
+}
+// (p2_ru, p2_rp) = b - J x
+static void p2_cycle_resid(pgx_handle* h, int kind, const double* xu, const double* xp, const double* bu, const double* bp) {
+  const int nd = h->nd;
+  if (kind == 2)
+    p2st_apply(h, xu, xp, bu, bp, h->p2_ru, h->p2_rp, true);
+  else if (kind == 1)
+    pgxk_bspmv_bal(h->st, nd, h->s_nblk, h->s_blk, h->s_rowptr, h->s_colm, h->s_K, h->s_M, h->s_code, h->s_tab, h->s_D, h->alpha, h->mask, xu, xp, bu,
+                   bp, h->xcd_remap ? 1 : 0, h->p2_ru, h->p2_rp, h->s_Df);
+  else
+    pgxk_bspmv(h->st, 1, nd, h->s_rowptr, h->s_colm, h->s_K, h->s_M, h->s_D, h->alpha, xu, xp, bu, bp, 0.0, h->xcd_remap,
+               h->p2_ru, h->p2_rp);
+}
+// x += patch_omega * (averaged patch solves of r)
+static void p2_cycle_patch(pgx_handle* h, const double* ru, const double* rp, double* xu, double* xp) {
+  const int nd = h->nd, nv = h->n;
+  pgxk_patch_sweep(h->st, nv, h->patch_nn, nv, nd, h->pdof, h->edge_ends, h->pinv, h->patch_f32, h->patch_sym, ru, rp, h->patch_omega, xu, xp, h->p2_su, h->p2_sp);
+}
+
 // Two-level cycle with the vertex-star patch smoother (round 3): patch_nu additive sweeps | P1 hierarchy on T^T (b - J x) |
 // patch_nu sweeps.  A sweep = residual (block-CSR SpMV) + one pass over the patch inverses.
 static void pcycle_p2_patch(pgx_handle* h, const double* bu, const double* bp, double* xu, double* xp, int nu, double omega) {
-  const int nd = h->nd, nv = h->n, NN = h->patch_nn;
-  const bool st_apply = h->spmv_bal && p2st_ready(h);
-  auto resid = [&]() {
-    if (st_apply)
-      p2st_apply(h, xu, xp, bu, bp, h->p2_ru, h->p2_rp, true);
-    else if (h->spmv_bal && h->s_blk)
-      pgxk_bspmv_bal(h->st, nd, h->s_nblk, h->s_blk, h->s_rowptr, h->s_colm, h->s_K, h->s_M, h->s_code, h->s_tab, h->s_D, h->alpha, h->mask, xu, xp, bu,
-                     bp, h->xcd_remap ? 1 : 0, h->p2_ru, h->p2_rp, h->s_Df);
-    else
-      pgxk_bspmv(h->st, 1, nd, h->s_rowptr, h->s_colm, h->s_K, h->s_M, h->s_D, h->alpha, xu, xp, bu, bp, 0.0, h->xcd_remap,
-                 h->p2_ru, h->p2_rp);
-  };
-  auto patch = [&](const double* ru, const double* rp) {
-    pgxk_patch_sweep(h->st, nv, NN, nv, nd, h->pdof, h->edge_ends, h->pinv, h->patch_f32, h->patch_sym, ru, rp, h->patch_omega, xu, xp, h->p2_su, h->p2_sp);
-  };
+  const int nd = h->nd, nv = h->n;
+  const int kind = p2_cycle_resid_kind(h);
+  auto resid = [&]() { p2_cycle_resid(h, kind, xu, xp, bu, bp); };
+  auto patch = [&](const double* ru, const double* rp) { p2_cycle_patch(h, ru, rp, xu, xp); };
   hipMemsetAsync(xu, 0, sizeof(double) * nd, h->st);
   hipMemsetAsync(xp, 0, sizeof(double) * nd, h->st);
   patch(bu, bp);  // x = 0: the residual is b
@@ -3383,9 +3397,12 @@ extern "C" int pgx_vcycle_bench(pgx_handle* h, int level, int reps, double* avg_
 // Test hooks (include/pgx.h): the stored multigrid operators of one level, and ONE V-cycle entered on one level, with the buffers and
 // the call sequence of pgx_vcycle_bench / pgx_spmv_bench.  They launch nothing of their own besides copies.
 // ------------------------------------------------------------------------------------------------
-static int mg_hook_ready(pgx_handle* h, const char* who) {
-  if (!h->jac_valid || !h->structured || h->lev.size() < 2 || h->dist.on || h->degree != 1 || h->lu_active) {
-    h->err = std::string(who) + " needs a structured single-GPU P1 handle with a grid hierarchy, a filled Jacobian and the multigrid preconditioner";
+// p2_too: the export also serves structured P2 handles, whose levels are the P1 hierarchy below the P2 level
+static int mg_hook_ready(pgx_handle* h, const char* who, bool p2_too = false) {
+  const bool degree_ok = h->degree == 1 || (p2_too && h->degree == 2);
+  if (!h->jac_valid || !h->structured || h->lev.size() < 2 || h->dist.on || !degree_ok || h->lu_active) {
+    h->err = std::string(who) + " needs a structured single-GPU " + (p2_too ? "" : "P1 ") +
+             "handle with a grid hierarchy, a filled Jacobian and the multigrid preconditioner";
     return PGX_ESTATE;
   }
   return PGX_OK;
@@ -3395,7 +3412,7 @@ extern "C" int pgx_mg_level_export(pgx_handle* h, int level, int* nx, int* ny, d
                                    int* dbf16) {
   NEED(h);
   {
-    const int rc = mg_hook_ready(h, "pgx_mg_level_export");
+    const int rc = mg_hook_ready(h, "pgx_mg_level_export", true);
     if (rc) return rc;
   }
   if (level < 0 || level >= (int)h->lev.size()) {
@@ -3547,6 +3564,124 @@ extern "C" int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, 
   HIPCHK(hipMemcpy(z, L.xu, sizeof(double) * n, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(z + n, L.xp, sizeof(double) * n, hipMemcpyDeviceToHost));
   return PGX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Test hooks of the P2 two-level cycle (include/pgx.h): what the patch smoother stores, and the stages of pcycle_p2_patch one at a
+// time through the functions the cycle itself calls (p2_cycle_resid, p2_cycle_patch, pgxk_p2_restrict, pgxk_p2_prolong_add, precond).
+// ------------------------------------------------------------------------------------------------
+static int p2_hook_ready(pgx_handle* h, const char* who) {
+  if (h->degree != 2 || !h->patch_nn || !h->p2_patch || !h->jac_valid || h->dist.on || h->lu_comm || h->lu_active) {
+    h->err = std::string(who) + " needs a single-GPU P2 handle with the vertex-star patch smoother (vertex degree <= 7, PGX_P2_PATCH on), "
+                                "a filled Jacobian and the sparse LU not active";
+    return PGX_ESTATE;
+  }
+  return PGX_OK;
+}
+
+extern "C" int pgx_p2_cycle_info(pgx_handle* h, int32_t out[8], double* patch_omega) {
+  NEED(h);
+  if (!out) return PGX_EINVAL;
+  int rc = p2_hook_ready(h, "pgx_p2_cycle_info");
+  if (rc) return rc;
+  if ((rc = ensure_patches(h))) return rc;  // allocates the float copy of D the CSR residual may read
+  const int kind = p2_cycle_resid_kind(h);
+  out[0] = h->patch_nn;
+  out[1] = !h->patch_f32 ? 0 : (!h->patch_sym ? 1 : (h->patch_f32 == 2 ? 3 : 2));
+  out[2] = h->patch_nu;
+  out[3] = kind == 2 ? (h->p2st.Dstf != nullptr) : (kind == 1 ? (h->s_Df != nullptr) : 0);
+  out[4] = kind;
+  out[5] = h->p2_fallbacks;
+  out[6] = (kind == 1 && h->s_code && h->s_tab) ? 1 : 0;
+  out[7] = (h->structured && h->lev.size() > 1) ? 1 : 0;
+  if (patch_omega) *patch_omega = h->patch_omega;
+  HIPCHK(hipStreamSynchronize(h->st));
+  return PGX_OK;
+}
+
+extern "C" int pgx_p2_patch_export(pgx_handle* h, int32_t* pdof, double* Ainv) {
+  NEED(h);
+  int rc = p2_hook_ready(h, "pgx_p2_patch_export");
+  if (rc) return rc;
+  if ((rc = ensure_patches(h))) return rc;
+  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(hipGetLastError());
+  const int nv = h->n, NN = h->patch_nn;
+  if (pdof) HIPCHK(hipMemcpy(pdof, h->pdof, sizeof(int32_t) * (size_t)nv * NN, hipMemcpyDeviceToHost));
+  if (Ainv) {
+    std::vector<uint8_t> raw(pgxk_patch_inverse_bytes(nv, NN, h->patch_f32, h->patch_sym));
+    HIPCHK(hipMemcpy(raw.data(), h->pinv, raw.size(), hipMemcpyDeviceToHost));
+    pgxk_patch_decode(nv, NN, h->patch_f32, h->patch_sym, raw.data(), Ainv);
+  }
+  return PGX_OK;
+}
+
+extern "C" int pgx_p2_cycle_apply(pgx_handle* h, int stage, int nu, double omega, const double* b, const double* x0, double* z) {
+  NEED(h);
+  int rc = p2_hook_ready(h, "pgx_p2_cycle_apply");
+  if (rc) return rc;
+  if (!b || !z || stage < 0 || stage > 4 || (stage == 2 && !x0) || (stage == 0 && (nu < 1 || x0))) {
+    h->err = "pgx_p2_cycle_apply: bad argument (stages 0 .. 4; stage 2 needs x0, stage 0 takes none and nu >= 1)";
+    return PGX_EINVAL;
+  }
+  if (stage == 0 && !(h->structured && h->lev.size() > 1)) {
+    h->err = "pgx_p2_cycle_apply: the whole cycle needs the P1 grid hierarchy of a structured mesh";
+    return PGX_ESTATE;
+  }
+  if ((rc = ensure_patches(h))) return rc;
+  const size_t nd = (size_t)h->nd, nv = (size_t)h->n;
+  double *xu = h->w, *xp = h->w + nd;
+  auto finish = [&]() -> int {
+    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipGetLastError());
+    return PGX_OK;
+  };
+  if (stage == 0) {  // as fgmres enters the preconditioner: right-hand side in the Krylov scratch, result in the operator scratch
+    if ((rc = copy_in(h, h->rhs, b))) return rc;
+    if ((rc = precond(h, h->rhs, h->w, nu, omega))) return rc;
+    if ((rc = finish())) return rc;
+    return copy_out(h, z, h->w);
+  }
+  if (stage == 3) {  // z[2 nv] = T^T b, u rows of Dirichlet vertices 0
+    HIPCHK(hipMemcpyAsync(h->p2_ru, b, sizeof(double) * nd, hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipMemcpyAsync(h->p2_rp, b + nd, sizeof(double) * nd, hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    pgxk_p2_restrict(h->st, (int)nv, (int)nd, h->v2e_ptr, h->v2e, h->mask, h->p2_ru, h->p2_rp, h->c1_bu, h->c1_bp);
+    if ((rc = finish())) return rc;
+    HIPCHK(hipMemcpy(z, h->c1_bu, sizeof(double) * nv, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(z + nv, h->c1_bp, sizeof(double) * nv, hipMemcpyDeviceToHost));
+    return PGX_OK;
+  }
+  // the iterate the stage starts from
+  if (x0) {
+    if ((rc = copy_in(h, h->w, x0))) return rc;
+  } else {
+    HIPCHK(hipMemsetAsync(h->w, 0, sizeof(double) * 2 * nd, h->st));
+  }
+  if (stage == 4) {  // z = x0 + T b, b of length 2 nv
+    HIPCHK(hipMemcpyAsync(h->c1_xu, b, sizeof(double) * nv, hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipMemcpyAsync(h->c1_xp, b + nv, sizeof(double) * nv, hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    pgxk_p2_prolong_add(h->st, (int)nv, (int)nd, h->edge_ends, h->c1_xu, h->c1_xp, xu, xp);
+    if ((rc = finish())) return rc;
+    return copy_out(h, z, h->w);
+  }
+  if ((rc = copy_in(h, h->rhs, b))) return rc;
+  const double *bu = h->rhs, *bp = h->rhs + nd;
+  if (stage == 2 || x0) p2_cycle_resid(h, p2_cycle_resid_kind(h), xu, xp, bu, bp);
+  if (stage == 2) {  // z = b - J x0 by the cycle's residual kernel
+    if ((rc = finish())) return rc;
+    HIPCHK(hipMemcpy(z, h->p2_ru, sizeof(double) * nd, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(z + nd, h->p2_rp, sizeof(double) * nd, hipMemcpyDeviceToHost));
+    return PGX_OK;
+  }
+  // stage 1: one sweep; from x = 0 the residual is b and no residual is launched (the cycle's first sweep)
+  if (x0)
+    p2_cycle_patch(h, h->p2_ru, h->p2_rp, xu, xp);
+  else
+    p2_cycle_patch(h, bu, bp, xu, xp);
+  if ((rc = finish())) return rc;
+  return copy_out(h, z, h->w);
 }
 
 static int spmv_bench_impl(pgx_handle* h, int reps, double* avg_ms, double* bytes, bool cold) {

@@ -288,6 +288,8 @@ void pgxk_patch_sweep(hipStream_t st, int np, int NN, int nv, int nd, const int3
                       const void* pinv, int f32, int sym, const double* ru, const double* rp, double omega, double* xu, double* xp,
                       double* su, double* sp);
 size_t pgxk_patch_inverse_bytes(int np, int NN, int f32, int sym);  // sym: symmetric packing (float form only)
+// host decode of a copy of pinv into full [np][2 NN][2 NN] matrices, as k_patch_apply reads them (test hook pgx_p2_patch_export)
+void pgxk_patch_decode(int np, int NN, int f32, int sym, const void* raw, double* out);
 // structured P2 operator apply (pgx_p2st.hip): the 46 entries of an interior group's four rows (vertex: 19, three edges: 9 each)
 struct P2StTab {
   int delta[46];             // neighbour dof = (isedge ? first edge dof of the group : vertex index of the group) + delta

@@ -20,6 +20,7 @@
 // float, 1792 B in double).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "pgx_internal.h"
 
@@ -298,6 +299,56 @@ void pgxk_patch_invert(hipStream_t st, int np, int NN, const int32_t* pdof, cons
     else if (f32 && sym) PGX_INV(8, float, true); else if (f32) PGX_INV(8, float, false); else PGX_INV(8, double, false);
   }
 #undef PGX_INV
+}
+
+// Host side of the test hook pgx_p2_patch_export: out [np][P][P], entry (l, j) = the factor k_patch_apply's lane l multiplies r_j
+// with, from a host copy `raw` of pinv.  Full rows: [patch][chunk q][row l][4].  Symmetric packing: a row's chunks at or left of its
+// diagonal block land at (l, 4q + t), those strictly left of it at (4q + t, l) as well - the LDS rebuild, statement for statement.
+namespace {
+template <typename PT>
+double patch_host_value(PT v) {
+  return (double)v;
+}
+template <>
+double patch_host_value<pgx_bf16>(pgx_bf16 v) {
+  const uint32_t u = (uint32_t)v << 16;
+  float f;
+  memcpy(&f, &u, sizeof(f));
+  return (double)f;
+}
+template <typename PT>
+void patch_decode(int np, int P, bool sym, const PT* raw, double* out) {
+  const int PQ = (P + 3) / 4;
+  const size_t per = sym ? (size_t)patch_sym_vecs(P) * 4 : (size_t)PQ * P * 4;
+  for (int p = 0; p < np; ++p) {
+    const PT* in = raw + (size_t)p * per;
+    double* A = out + (size_t)p * P * P;
+    for (int j = 0; j < P * P; ++j) A[j] = 0.0;
+    for (int l = 0; l < P; ++l)
+      for (int q = 0; q < PQ; ++q) {
+        if (!sym) {
+          for (int t = 0; t < 4; ++t)
+            if (4 * q + t < P) A[l * P + 4 * q + t] = patch_host_value<PT>(in[((size_t)q * P + l) * 4 + t]);
+        } else if (4 * q <= l) {
+          const PT* v = in + (size_t)(patch_sym_off(P, q) + l - 4 * q) * 4;
+          for (int t = 0; t < 4; ++t)
+            if (4 * q + t < P) A[l * P + 4 * q + t] = patch_host_value<PT>(v[t]);
+          if (4 * q + 4 <= (l & ~3))
+            for (int t = 0; t < 4; ++t) A[(4 * q + t) * P + l] = patch_host_value<PT>(v[t]);
+        }
+      }
+  }
+}
+}  // namespace
+
+void pgxk_patch_decode(int np, int NN, int f32, int sym, const void* raw, double* out) {
+  const int P = NN <= 7 ? 14 : 16;
+  if (f32 == 2 && sym)
+    patch_decode<pgx_bf16>(np, P, true, (const pgx_bf16*)raw, out);
+  else if (f32)
+    patch_decode<float>(np, P, sym != 0, (const float*)raw, out);
+  else
+    patch_decode<double>(np, P, false, (const double*)raw, out);
 }
 
 void pgxk_patch_sweep(hipStream_t st, int np, int NN, int nv, int nd, const int32_t* pdof, const int32_t* edge_ends,

@@ -411,6 +411,48 @@ class NonlinearProblem:
                                                     _lib.dptr(b), _lib.dptr(z)), "pgx_vcycle_apply")
         return z
 
+    P2_PATCH_FORMS = ("double", "float", "float-sym", "bf16-sym")
+    P2_RESID_KERNELS = ("csr", "csr-balanced", "structured")
+
+    def p2_cycle_info(self):
+        """What the P2 two-level cycle of this handle runs (include/pgx.h: pgx_p2_cycle_info; a test hook): dict(patch_nn, form,
+        patch_nu, patch_omega, resid_f32, resid_kernel, fallbacks, km_dict, hierarchy)."""
+        out = np.zeros(8, dtype=np.int32)
+        om = C.c_double(0)
+        self._check_code(self._lib.pgx_p2_cycle_info(self._h, _lib.iptr(out), C.byref(om)), "pgx_p2_cycle_info")
+        return dict(patch_nn=int(out[0]), form=self.P2_PATCH_FORMS[out[1]], patch_nu=int(out[2]), patch_omega=om.value,
+                    resid_f32=bool(out[3]), resid_kernel=self.P2_RESID_KERNELS[out[4]], fallbacks=int(out[5]), km_dict=bool(out[6]),
+                    hierarchy=bool(out[7]))
+
+    def p2_patch_export(self):
+        """(pdof [nv, NN] int32, Ainv [nv, 2 NN, 2 NN]) of the vertex-star patches at the last assemble_jacobian, the inverses decoded
+        as the sweep kernel decodes them (include/pgx.h: pgx_p2_patch_export; a test hook)."""
+        NN = self.p2_cycle_info()["patch_nn"]
+        nv = self._keep[0].shape[0]  # mesh vertices
+        pdof = np.empty((nv, NN), dtype=np.int32)
+        Ainv = np.empty((nv, 2 * NN, 2 * NN))
+        self._check_code(self._lib.pgx_p2_patch_export(self._h, _lib.iptr(pdof), _lib.dptr(Ainv)), "pgx_p2_patch_export")
+        return pdof, Ainv
+
+    def p2_cycle_apply(self, stage, b, x0=None, nu=6, omega=0.75):
+        """One stage of the P2 two-level cycle on host vectors (include/pgx.h: pgx_p2_cycle_apply; a test hook): 1 one sweep from x0
+        (None: the first sweep of a cycle), 2 the residual b - J x0, 3 restriction (result [u | psi] of the P1 space), 4 x0 + T b
+        (b of the P1 space), 0 the whole preconditioner."""
+        nv = self._keep[0].shape[0]  # mesh vertices
+        n_in = 2 * nv if stage == 4 else self.ndofs
+        n_out = 2 * nv if stage == 3 else self.ndofs
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (n_in,):
+            raise ValueError(f"stage {stage} takes b of {n_in} entries")
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            if x0.shape != (self.ndofs,):
+                raise ValueError(f"x0 must hold [u | psi] of the P2 space: {self.ndofs} entries")
+        z = np.empty(n_out)
+        self._check_code(self._lib.pgx_p2_cycle_apply(self._h, int(stage), int(nu), float(omega), _lib.dptr(b), _lib.dptr(x0), _lib.dptr(z)),
+                         "pgx_p2_cycle_apply")
+        return z
+
     def observables(self):
         """[energy, |complementarity|, feasibility, dual feasibility, H1 increment, latent L2 increment]
         of obstacle_pg.py:145-152,196-201 in one device pass."""

@@ -1,0 +1,540 @@
+"""The P2 two-level preconditioner (csrc/pgx_api.hip: pcycle_p2_patch; csrc/pgx_patch.hip) as an OPERATOR, stage by stage, against
+tests/p2_cycle_reference.py.
+
+No assertion on a solve can see this code go wrong: FGMRES runs on the exact fp64 operator, a worse preconditioner costs Krylov
+iterations, and after 60 of them the Newton solve switches to the sparse LU - same Newton counts, same field.  Here a case creates a
+handle under one set of tuning keys, fills ONE Jacobian per state and reads what the patch smoother stores (pgx_p2_patch_export) or
+runs one stage of the cycle on host vectors (pgx_p2_cycle_apply), and compares with the numpy statement built from the exported blocks
+(K, M, D, alpha, the Dirichlet set) and the oracle's edges.
+
+Meshes: (12, 12) - the structured apply has an interior, 169 patches = 10 * 16 + 9, the last block has idle groups; (16, 10) - not
+square, with a hierarchy; (9, 6) - no structured interior, the CSR residual alone, 70 patches; (15, 15) - 256 patches, exactly 16
+blocks (tables, inverses, sweep); the 8 x 8 mesh with permuted numbering of test_gpu_p2.py - a general mesh, 7 slots; fem.create_disk
+(0.2) - 95 vertices, one of degree 7: 8 slots, 16 x 16 patch matrices.
+
+States: iterates of the oracle's settings-B run on the same mesh - iterate 1 with alpha 1, the middle one with alpha 10, the last but
+one with alpha 100 - and one random state of test_gpu_p2._iterates' form with its large factor at 20 (at 200 independent jumps give
+patch matrices with a diagonally scaled condition number beyond 1e23, where no comparison of inverses means anything).
+
+Bounds (DESIGN.md section 5c tabulates the largest ratios measured):
+  inverses, double form   e(Y) = max_ij sqrt |A_ii A_jj| |Y_ij - X_ij| against the 60-digit inverse X of the reference patch matrix;
+                          e(device) <= 16 (E_p + 4 eps max_ij sqrt |A_ii A_jj| |X_ij|), E_p = e(float64 twin of the elimination),
+                          for EVERY patch; 16 as in test_gpu_vcycle_operator.py
+  other storage forms     exact statements: float = float32(double export); symmetric = the float rows in the stored chunks and their
+                          transpose in the mirrored entries; bf16 = bf16_round of the float value
+  residual in the cycle   1e-13 (|J~| |x| + |b|)_i per row, J~ with D rounded to float32 where the handle reads the float copy
+  one sweep               reference sweep on the EXPORTED inverses; s_i = omega sum_j |Ainv_ij| |r_j|: vertex dofs 1e-13 s_i, edge dofs
+                          omega 2^-23 max(|y_a|, |y_b|) + 1e-13 s_i (one float rounding flip of a parked contribution)
+  transfers               1e-15 times the sum of the absolute terms of an entry; masked u rows of the restriction exactly 0
+  level-0 D               mg_level_export(0).Dh against half_stencil(T^T D T) within 1e-12 of its largest entry
+  whole cycle             E = |reference with float stash and float D - the same in float64| (max norm, per block); the device within
+                          16 E + 1e-12 max |z| of the former
+Every figure is printed before it is asserted (`P2OP ...` lines)."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+from oracle import pg_oracle as O
+from tests import p2_cycle_reference as PR
+from tests import vcycle_reference as VR
+
+pytestmark = pytest.mark.gpu
+DOMAIN = ((-1.0, -1.0), (1.0, 1.0))
+PGX_EINVAL, PGX_EHIP, PGX_ESTATE = -1, -2, -5
+EXPLICIT = {"PGX_NU_COARSE": 0, "PGX_COARSE_SWEEPS": 10, "PGX_TAIL_VERTS": 1100, "PGX_MG_MIN_NX": 4}
+NU, OMEGA = 6, 0.75
+MARGIN = 16.0
+MESHES = ["12x12", "16x10", "9x6", "15x15", "perm8", "disk"]
+STATES = ["it1-a1", "mid-a10", "late-a100", "random-a3.5"]
+FORMS = {"double": {"PGX_P2_PATCH_F32": 0}, "float": {"PGX_P2_PATCH_F32": 1, "PGX_P2_PATCH_SYM": 0},
+         "float-sym": {"PGX_P2_PATCH_F32": 1, "PGX_P2_PATCH_SYM": 1}, "bf16-sym": {"PGX_P2_PATCH_F32": 2, "PGX_P2_PATCH_SYM": 1}}
+
+_live = None  # ONE live handle: tuning keys are process-wide
+_oracle, _cases, _exact = {}, {}, {}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# meshes, states, handles
+# ---------------------------------------------------------------------------------------------------------------------
+def _mesh(name):
+    from proximalgalerkin_amd import fem
+
+    if name == "disk":
+        return fem.create_disk(0.2), None
+    if name == "perm8":  # test_gpu_p2.py: test_p2_unstructured_numbering
+        coords, cells = O.create_rectangle(8, 8)
+        rng = np.random.default_rng(9)
+        perm = rng.permutation(len(coords))
+        inv = np.argsort(perm)
+        return fem.Mesh(coords[inv], perm[cells].astype(np.int32)[rng.permutation(len(cells))]), None
+    nx, ny = (int(v) for v in name.split("x"))
+    return fem.create_rectangle(DOMAIN, (nx, ny)), (nx, ny)
+
+
+def _random_state(n2, seed):
+    """test_gpu_p2._iterates with the large factor at 20"""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal(n2) * 0.1
+    n = n2 // 2
+    x[n:] = -np.abs(rng.standard_normal(n)) * np.where(rng.random(n) < 0.3, 20.0, 2.0)
+    return x
+
+
+def _oracle_of(name):
+    """(mesh, grid, oracle problem, {state: (x, x_prev, alpha)}): the oracle's settings-B run on the mesh, once per module."""
+    if name not in _oracle:
+        msh, grid = _mesh(name)
+        prob = O.ObstacleLagrange(msh.geometry, msh.cells, 2)
+        its = []
+        O.solve_problem(prob, 100, "double_exponential", 1e2, 1e-4, iterates=its)
+        assert len(its) >= 5, len(its)
+        mid = len(its) // 2
+        states = {"it1-a1": (its[1], its[0], 1.0), "mid-a10": (its[mid], its[mid - 1], 10.0),
+                  "late-a100": (its[-2], its[-3], 100.0), "random-a3.5": (_random_state(2 * prob.n, 21), np.zeros(2 * prob.n), 3.5)}
+        _oracle[name] = (msh, grid, prob, states)
+    return _oracle[name]
+
+
+class _Handle:
+    def __init__(self, name, keys):
+        from proximalgalerkin_amd import _lib
+        from proximalgalerkin_amd.obstacle import setup_problem
+
+        self.name, self.keys, self.key = name, dict(EXPLICIT, **keys), (name, tuple(sorted(keys.items())))
+        self.msh, self.grid, self.prob, self.states = _oracle_of(name)
+        self.problem = None
+        for k, v in self.keys.items():
+            _lib.tuning_set(k, v)
+        try:
+            self.problem, self.sol, self.sol_k, self.alpha = setup_problem(self.msh, 2)
+            assert self.sol.function_space.block_size == self.prob.n
+        except BaseException:
+            self.close()
+            raise
+
+    def fill(self, state):
+        """One Jacobian at the state; returns (case, info): the reference data of (mesh, state), shared by every handle - the
+        exported blocks must be the same bits on each - and what this handle's cycle runs."""
+        x, x_prev, alpha = self.states[state]
+        self.alpha.value = alpha
+        self.sol_k.x.array[:] = x_prev
+        self.problem.assemble_jacobian(x)
+        info = self.problem.p2_cycle_info()
+        rowptr, col, K, M, D = self.problem.export_blocks()
+        pdof, _ = self.problem.p2_patch_export()
+        k = (self.name, state)
+        if k not in _cases:
+            prob = self.prob
+            assert np.array_equal(rowptr, prob.indptr_s.astype(np.int32)) and np.array_equal(col, prob.indices_s)
+            _check_table(prob, pdof, info["patch_nn"])
+            mk = lambda v: sp.csr_matrix((v, col, rowptr), shape=(prob.n, prob.n))  # noqa: E731
+            vc = None
+            if info["hierarchy"]:
+                vc = dict(n_levels=self.problem.mg_levels(), min_nx=EXPLICIT["PGX_MG_MIN_NX"], coarse_sweeps=EXPLICIT["PGX_COARSE_SWEEPS"])
+            ref = PR.P2CycleReference(mk(K), mk(M), mk(D), alpha, prob.isbc, prob.edges, prob.nv, patch_nu=info["patch_nu"],
+                                      patch_omega=info["patch_omega"], grid=self.grid, vcycle=vc, table=pdof)
+            _cases[k] = dict(ref=ref, blocks=(K, M, D), pdof=pdof, x=x, F=prob.residual(x, x_prev, alpha))
+        case = _cases[k]
+        for got, want in zip((K, M, D), case["blocks"]):
+            assert np.array_equal(got, want), "the exported blocks differ between two handles on the same mesh and state"
+        assert np.array_equal(pdof, case["pdof"])
+        assert info["patch_nu"] == case["ref"].patch_nu and info["patch_omega"] == case["ref"].patch_omega
+        return case, info
+
+    def close(self):
+        from proximalgalerkin_amd import _lib
+
+        if self.problem is not None:
+            self.problem.close()
+        for k in self.keys:
+            _lib.tuning_set(k, None)
+
+
+def _handle(name, keys):
+    global _live
+    key = (name, tuple(sorted(keys.items())))
+    if _live is not None and _live.key == key:
+        return _live
+    _drop()
+    _live = _Handle(name, keys)
+    return _live
+
+
+def _drop():
+    global _live
+    if _live is not None:
+        live, _live = _live, None
+        live.close()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _close_last_handle():
+    yield
+    _drop()
+
+
+def _stage(h, stage, b, x0=None):
+    """pgx_p2_cycle_apply; a HIP runtime error ends the session (nothing more is launched on a device that reported one)."""
+    from proximalgalerkin_amd._lib import PgxError
+
+    try:
+        return h.problem.p2_cycle_apply(stage, b, x0, nu=NU, omega=OMEGA)
+    except PgxError as e:
+        if getattr(e, "code", 0) == PGX_EHIP:
+            pytest.exit(f"HIP error in pgx_p2_cycle_apply: {e}", returncode=3)
+        raise
+
+
+def _float_d_rows(h, info):
+    """Which psi rows of the cycle's residual read the float copy of D: none, all (CSR kernel), or - the structured apply - the rows
+    of its interior groups, while its frame rows go through k_p2_rows_csr and the fp64 D."""
+    if not info["resid_f32"]:
+        return False
+    if info["resid_kernel"] != "structured":
+        return True
+    state, i0, ni, j0, nj = h.problem.p2_stencil_info()
+    assert state == 2 and ni > 0 and nj > 0
+    return PR.structured_interior_rows(*h.grid, i0, ni, j0, nj)
+
+
+def _check_table(prob, pdof, NN):
+    """Slot 0 is the vertex, the other live slots are exactly the incident edge dofs (as sets), the rest is -1."""
+    want = PR.star_table(prob.edges, prob.nv)
+    assert NN == PR.patch_slots(want.shape[1]) and pdof.shape == (prob.nv, NN)
+    for v in range(prob.nv):
+        live = pdof[v] >= 0
+        k = int(live.sum())
+        assert pdof[v, 0] == v and live[:k].all() and not live[k:].any() and (pdof[v, k:] == -1).all(), (v, pdof[v])
+        assert len(set(pdof[v, 1:k])) == k - 1 and set(pdof[v, 1:k]) == set(want[v][want[v] >= 0][1:]), (v, pdof[v], want[v])
+
+
+def _exact_inverse(name, state, A):
+    """60-digit inverses of the reference patch matrices with the twin's error, once per mesh and state."""
+    k = (name, state)
+    if k not in _exact:
+        X = PR.exact_inverse(A)
+        Ep = PR.inverse_error(A, PR.gauss_jordan_inverse(A), X)
+        _exact[k] = (A.copy(), X, Ep, PR.inverse_size(A, X))
+    assert np.array_equal(_exact[k][0], A)
+    return _exact[k][1:]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. tables, 2. inverses in the double form, 3. the other storage forms
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", MESHES)
+def test_star_tables(require_gpu, name):
+    """pgx_p2_patch_export's dof table under the default keys (checked in fill())."""
+    h = _handle(name, {})
+    case, info = h.fill("it1-a1")
+    hist = np.bincount((case["pdof"] >= 0).sum(axis=1) - 1, minlength=8)
+    print(f"P2OP table {name}: NN {info['patch_nn']} form {info['form']} vertex degree histogram {hist.tolist()}")
+    assert info["form"] == "float-sym" and info["patch_nn"] == (8 if name == "disk" else 7)
+    if name == "disk":
+        assert hist.tolist() == [0, 0, 0, 6, 25, 1, 62, 1]
+
+
+@pytest.mark.parametrize("state", STATES)
+@pytest.mark.parametrize("name", MESHES)
+def test_stored_inverses_in_every_form(require_gpu, name, state):
+    """The double form against 60-digit inverses, every patch; the float, symmetric and bf16 forms as exact functions of it."""
+    out = {}
+    for form, keys in FORMS.items():
+        h = _handle(name, keys)
+        case, info = h.fill(state)
+        assert info["form"] == form, (info, form)
+        out[form] = h.problem.p2_patch_export()[1]
+        assert np.isfinite(out[form]).all()
+    ref = case["ref"]
+    A = ref.patch_matrices()
+    X, Ep, size = _exact_inverse(name, state, A)
+    bound = MARGIN * (Ep + 4.0 * PR.EPS * size)
+    e = PR.inverse_error(A, out["double"], X)
+    ratio = e / (Ep + 4.0 * PR.EPS * size)
+    print(f"P2OP inverse {name} {state}: max E_p {Ep.max():.2e} max e(device) {e.max():.2e} worst e / bracket {ratio.max():.2f} "
+          f"max scaled |X| {size.max():.2e} max |X| {np.abs(X[0]).max():.2e}")
+    assert np.all(e <= bound), (name, state, int(np.argmax(ratio)), ratio.max())
+    # float full rows = float32(double), entry for entry
+    with np.errstate(over="ignore"):
+        f32 = out["double"].astype(np.float32)
+    full = out["float"].astype(np.float32)
+    assert np.array_equal(full.astype(np.float64), out["float"])  # the export holds float values
+    ulps = np.abs(full.view(np.int32).astype(np.int64) - f32.view(np.int32).astype(np.int64))
+    print(f"P2OP forms {name} {state}: float vs float32(double): {int((ulps > 0).sum())} entries differ, at most {int(ulps.max())} ulp")
+    assert np.array_equal(full.view(np.uint32), f32.view(np.uint32))
+    # symmetric packing = the float rows in the stored chunks, their transpose in the mirrored entries
+    P = A.shape[1]
+    mir = PR.sym_mirrored(P)[None]
+    fullT = np.swapaxes(out["float"], 1, 2)
+    assert np.array_equal(out["float-sym"], np.where(mir, fullT, out["float"]))
+    # bf16 = bf16_round(float value), in the same packing
+    b16 = VR.bf16_round(full).astype(np.float64)
+    assert np.array_equal(out["bf16-sym"], np.where(mir, np.swapaxes(b16, 1, 2), b16))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. the residual inside the cycle
+# ---------------------------------------------------------------------------------------------------------------------
+# (PGX_P2_RESID_F32, PGX_P2_STENCIL, PGX_SPMV_BAL, PGX_SPMV_DICT): each of the first three on and off; the nnz-balanced kernel also
+# without its K / M dictionary
+RESID_FORMS = [(r, s, b, 1) for r in (1, 0) for s in (1, 0) for b in (1, 0)] + [(1, 0, 1, 0), (0, 0, 1, 0)]
+
+
+@pytest.mark.parametrize("rf32,stencil,bal,dct", RESID_FORMS)
+@pytest.mark.parametrize("name", ["12x12", "16x10", "9x6", "perm8", "disk"])
+def test_residual_inside_the_cycle(require_gpu, name, rf32, stencil, bal, dct):
+    """Stage 2, z = b - J~ x with x the state and b random, through the kernel the cycle uses under these keys: the structured apply
+    with CSR frame rows, the nnz-balanced CSR kernel (with or without its K / M dictionary) or the plain CSR kernel, reading the
+    float or the fp64 D.  The float-D kernels widen D and compute in float64, so J~ is a float64 operator: D rounded to float32 on
+    the rows that read the float copy (_float_d_rows), and - the nnz-balanced kernel on a uniform mesh - K and M as its one-byte
+    dictionary stores them, on a grid of 2^-40 of the largest entry (the unrounded operator is then 3e-13 ... 1.1e-12 away,
+    printed; with PGX_SPMV_DICT=0 the same kernel meets 1e-13 against the unrounded operator)."""
+    h = _handle(name, {"PGX_P2_RESID_F32": rf32, "PGX_P2_STENCIL": stencil, "PGX_SPMV_BAL": bal, "PGX_SPMV_DICT": dct})
+    interior = name in ("12x12", "16x10")
+    for state in STATES:
+        case, info = h.fill(state)
+        ref = case["ref"]
+        want_kernel = "structured" if (interior and stencil and bal) else ("csr-balanced" if bal else "csr")
+        assert info["resid_kernel"] == want_kernel, (info, want_kernel)
+        assert info["resid_f32"] == bool(rf32 and bal), info  # the plain CSR kernel has no float-D form
+        # (the permuted 8 x 8 mesh has the uniform mesh's few distinct (K, M) pairs and gets a dictionary, the disk does not)
+        assert info["km_dict"] == bool(want_kernel == "csr-balanced" and dct and name != "disk"), info
+        x = case["x"]
+        b = np.random.default_rng(5).standard_normal(x.shape)
+        z = _stage(h, 2, b, x)
+        assert np.array_equal(z, _stage(h, 2, b, x))  # reproducible
+        rows = _float_d_rows(h, info)
+        scale = ref.residual_scale(x, b, rows)
+        plain = (np.abs(z - ref.residual(x, b, rows)) / scale).max()
+        stored = (np.abs(z - ref.residual(x, b, rows, info["km_dict"])) / scale).max()
+        print(f"P2OP resid {name} {state} kernel {info['resid_kernel']} float-D {info['resid_f32']} dict {info['km_dict']}: "
+              f"max row error / (|J||x| + |b|) = {stored:.2e} (against the unrounded K, M: {plain:.2e})")
+        assert stored <= 1e-13, (name, state, info, stored)
+        if not info["km_dict"]:
+            assert plain == stored
+        if info["resid_f32"]:  # the comparison is sharp enough to tell the float D from the fp64 one
+            assert (np.abs(z - ref.residual(x, b, False)) / scale).max() > 1e-13
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. one sweep
+# ---------------------------------------------------------------------------------------------------------------------
+def _check_sweep(tag, ref, z, zref, s, ymax, omega):
+    n, nv = ref.n, ref.nv
+    edge = np.tile(np.arange(n) >= nv, 2)
+    bound = 1e-13 * s + np.where(edge, omega * 2.0 ** -23 * ymax, 0.0)
+    err = np.abs(z - zref)
+    tiny = np.finfo(np.float64).tiny
+    rv = (err[~edge] / np.maximum(1e-13 * s[~edge], tiny)).max()
+    re = (err[edge] / np.maximum(bound[edge], tiny)).max()
+    flips = int((err[edge] > 1e-13 * s[edge]).sum())
+    print(f"P2OP sweep {tag}: vertex dofs error / bound {rv:.2e}, edge dofs {re:.2e} ({flips} beyond 1e-13 s: float rounding flips)")
+    assert np.all(err <= bound), (tag, rv, re)
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("name", MESHES)
+def test_one_sweep(require_gpu, name, form):
+    """Stage 1 from x = 0 (the cycle's first sweep: no residual launch) and from a random x0 (residual by the cycle's kernel, then the
+    sweep), against the reference sweep on the inverses this handle exports - storage rounding is not in the comparison, the LDS
+    rebuild, the idle groups of the last block and the float stash are.  From x0 the reference starts from the residual the device
+    reports for the same (b, x0) in stage 2 - reproducible bit for bit, and checked on its own above -, so that the bound is about
+    the sweep alone.  x0 = the first sweep's result times (1 + U(-1/2, 1/2)) per dof: the size of iterate a second sweep meets."""
+    h = _handle(name, FORMS[form])
+    for state in STATES:
+        case, info = h.fill(state)
+        ref = case["ref"]
+        omega = info["patch_omega"]
+        Ainv = h.problem.p2_patch_export()[1]
+        rng = np.random.default_rng(17)
+        for bname, b in (("random", rng.standard_normal(2 * ref.n)), ("-F", -case["F"])):
+            z = _stage(h, 1, b)
+            s, ymax = ref.sweep_scales(b, Ainv)
+            zref = ref.sweep(np.zeros_like(b), b, Ainv, stash_f32=True)
+            _check_sweep(f"{name} {form} {state} {bname} first", ref, z, zref, s, ymax, omega)
+            x0 = zref * (1.0 + rng.uniform(-0.5, 0.5, len(zref)))
+            r = _stage(h, 2, b, x0)
+            z = _stage(h, 1, b, x0)
+            s, ymax = ref.sweep_scales(r, Ainv)
+            _check_sweep(f"{name} {form} {state} {bname} from x0", ref, z, ref.sweep(x0, r, Ainv, stash_f32=True), s, ymax, omega)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. transfers, 7. the D of the P1 hierarchy
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["12x12", "16x10", "9x6", "perm8", "disk"])
+def test_transfers(require_gpu, name):
+    """Stages 3 and 4 against T^T and T in extended precision: 1e-15 times the sum of the absolute terms of each entry (a vertex
+    collects up to 8 terms: 7 float64 additions, 7.8e-16); the u rows of Dirichlet vertices of the restriction exactly 0."""
+    h = _handle(name, {})
+    case, info = h.fill("mid-a10")
+    ref = case["ref"]
+    n, nv = ref.n, ref.nv
+    rng = np.random.default_rng(23)
+    for tag, r in (("random", rng.standard_normal(2 * n) * np.exp(rng.uniform(-20, 20, 2 * n))), ("-F", -case["F"])):
+        z = _stage(h, 3, r)
+        want = ref.restrict(r, np.longdouble)
+        err = np.abs(z - want).astype(np.float64)
+        scale = ref.restrict_scale(r)
+        ratio = (err / np.maximum(scale, np.finfo(np.float64).tiny)).max()
+        print(f"P2OP restrict {name} {tag}: max error / sum |terms| = {ratio:.2e}")
+        assert np.all(err <= 1e-15 * scale)
+        assert ref.isbc[:nv].any() and np.all(z[:nv][ref.isbc[:nv]] == 0.0) and np.any(scale[:nv][ref.isbc[:nv]] > 0.0)
+        c = rng.standard_normal(2 * nv) * np.exp(rng.uniform(-20, 20, 2 * nv))
+        for x0 in (None, r):
+            z = _stage(h, 4, c, x0)
+            xx = np.zeros(2 * n) if x0 is None else x0
+            err = np.abs(z - ref.prolong_add(xx, c, np.longdouble)).astype(np.float64)
+            scale = ref.prolong_scale(xx, c)
+            print(f"P2OP prolong {name} {tag} x0 {'0' if x0 is None else 'given'}: max error / sum |terms| = "
+                  f"{(err / np.maximum(scale, np.finfo(np.float64).tiny)).max():.2e}")
+            assert np.all(err <= 1e-15 * scale)
+
+
+@pytest.mark.parametrize("name", ["12x12", "16x10"])
+def test_hierarchy_d_under_the_p2_handle(require_gpu, name):
+    """k_fill_rows_p1_Dp2: level 0 of the P1 hierarchy stores D = T^T D_P2 T (1e-12 of its largest entry), the coarser levels its
+    Galerkin products as on a P1 handle; the masks are the frames."""
+    h = _handle(name, {})
+    for state in STATES:
+        case, info = h.fill(state)
+        assert info["hierarchy"]
+        vc = case["ref"].vcycle_reference()
+        nlev = h.problem.mg_levels()
+        assert nlev == len(vc.levels) >= 2
+        for l in range(nlev):
+            got = h.problem.mg_level_export(l)
+            L = vc.levels[l]
+            assert (got["nx"], got["ny"]) == (L["nx"], L["ny"]) and not got["f32"]  # fp64 levels: setup_f32 needs degree 1
+            want = VR.half_stencil(L["D"], L["nx"], L["ny"])
+            err = np.abs(got["Dh"] - want).max() / np.abs(want).max()
+            print(f"P2OP hierarchy {name} {state} level {l}: |Dh - Galerkin| / max |D| = {err:.2e}")
+            assert err <= 1e-12
+            assert np.array_equal(got["mask"], VR.frame_mask(L["nx"], L["ny"])) and np.array_equal(got["mask"], L["mask"])
+        from proximalgalerkin_amd._lib import PgxError
+
+        with pytest.raises(PgxError) as e:  # the V-cycle hook keeps its P1 precondition
+            h.problem.vcycle_apply(0, np.zeros(2 * case["ref"].nv))
+        assert e.value.code == PGX_ESTATE
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. the whole cycle
+# ---------------------------------------------------------------------------------------------------------------------
+def _cycle_rhs(h, case):
+    ref = case["ref"]
+    n, nv = ref.n, ref.nv
+    nx, ny = h.grid
+    rng = np.random.default_rng(31)
+    bedge = next(e for e in range(n - nv) if ref.isbc[nv + e])
+    iedge = next(e for e in range((n - nv) // 2, n - nv) if not ref.isbc[nv + e])
+
+    def impulse(dof):
+        b = np.zeros(2 * n)
+        b[dof], b[n + dof] = 1.0, -1.0
+        return b
+
+    return {"random": rng.standard_normal(2 * n), "corner": impulse(nx), "boundary-edge": impulse(nv + bedge),
+            "interior-edge": impulse(nv + iedge), "-F": -case["F"]}
+
+
+@pytest.mark.parametrize("rf32", [1, 0])
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("name", ["12x12", "16x10"])
+def test_whole_cycle(require_gpu, name, form, rf32):
+    """Stage 0 at nu = 6, omega = 0.75, entered as FGMRES enters the preconditioner, against the reference cycle on the exported
+    inverses with the float stash and the D the handle's residual reads."""
+    h = _handle(name, dict(FORMS[form], PGX_P2_RESID_F32=rf32))
+    for state in STATES:
+        case, info = h.fill(state)
+        assert info["hierarchy"] and info["resid_f32"] == bool(rf32)
+        ref = case["ref"]
+        n = ref.n
+        Ainv = h.problem.p2_patch_export()[1]
+        assert info["resid_kernel"] == "structured"
+        rows = _float_d_rows(h, info)
+        for bname, b in _cycle_rhs(h, case).items():
+            z = _stage(h, 0, b)
+            z32 = ref.cycle(b, Ainv, nu=NU, omega=OMEGA, stash_f32=True, d_f32=rows)
+            z64 = ref.cycle(b, Ainv, nu=NU, omega=OMEGA, stash_f32=False, d_f32=False)
+            for blk, s in (("u", slice(0, n)), ("psi", slice(n, 2 * n))):
+                E = np.abs(z32[s] - z64[s]).max()
+                dev = np.abs(z[s] - z32[s]).max()
+                bound = MARGIN * E + 1e-12 * np.abs(z32[s]).max()
+                print(f"P2OP cycle {name} {form} float-D {info['resid_f32']} {state} {bname} {blk}: E {E:.2e} device {dev:.2e} "
+                      f"max |z| {np.abs(z32[s]).max():.2e} device / bound {dev / bound:.3f}")
+                assert E > 0.0 and dev <= bound, (name, form, state, bname, blk, dev, E)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 9. the fallback counter, refusals
+# ---------------------------------------------------------------------------------------------------------------------
+def test_full_run_never_falls_back_to_the_sparse_lu(require_gpu):
+    """The settings-B run at 32 x 32: no Newton solve reaches p2_fallback_its = 60 Krylov iterations (oracle/p2_patch_proto.py
+    measured 7 to 15 per system there), so the counter of switches to the sparse LU stays at 0."""
+    from proximalgalerkin_amd import fem
+    from proximalgalerkin_amd.obstacle import run_outer_loop, setup_problem
+
+    _drop()
+    problem, sol, sol_k, alpha = setup_problem(fem.create_rectangle(DOMAIN, (32, 32)), 2)
+    counts, solve = [], problem.solve
+
+    def counted():
+        out = solve()
+        counts.append((problem.solver.getIterationNumber(), problem.solver.getLinearSolveIterations()))
+        return out
+
+    problem.solve = counted
+    try:
+        hist = run_outer_loop(problem, sol, sol_k, alpha, 100, "double_exponential", 1e2, 1e-4)
+        info = problem.p2_cycle_info()
+    finally:
+        problem.close()
+    print(f"P2OP fallback 32x32: (Newton steps, Krylov iterations) per solve {counts}; fallbacks {info['fallbacks']}")
+    assert hist["outer_iterations"] == len(counts) and all(n > 0 and k > 0 for n, k in counts)
+    assert info["fallbacks"] == 0
+
+
+def test_refusals(require_gpu):
+    """PGX_ESTATE and nothing launched: a P1 handle, a P2 handle without a Jacobian, the whole cycle without a hierarchy, the patch
+    smoother switched off; PGX_EINVAL for stages that do not exist or lack their x0."""
+    from proximalgalerkin_amd import _lib, fem
+    from proximalgalerkin_amd._lib import PgxError
+    from proximalgalerkin_amd.obstacle import setup_problem
+
+    _drop()
+
+    def code(fn, *a):
+        with pytest.raises(PgxError) as e:
+            fn(*a)
+        return e.value.code
+
+    grid = fem.create_rectangle(DOMAIN, (16, 16))
+    problem, sol, sol_k, alpha = setup_problem(grid, 1)
+    problem.assemble_jacobian(np.zeros(problem.ndofs))
+    assert code(problem.p2_cycle_info) == PGX_ESTATE
+    assert code(problem.p2_cycle_apply, 2, np.zeros(problem.ndofs), np.zeros(problem.ndofs)) == PGX_ESTATE
+    problem.close()
+    problem, sol, sol_k, alpha = setup_problem(grid, 2)
+    n2 = problem.ndofs
+    assert code(problem.p2_cycle_info) == PGX_ESTATE  # no Jacobian yet
+    assert problem._lib.pgx_p2_patch_export(problem._h, None, None) == PGX_ESTATE
+    problem.assemble_jacobian(_random_state(n2, 2))
+    assert problem.p2_cycle_info()["hierarchy"]
+    for stage, x0 in ((5, None), (-1, None), (2, None), (0, np.zeros(n2))):
+        assert code(problem.p2_cycle_apply, stage, np.zeros(n2), x0) == PGX_EINVAL
+    problem.close()
+    msh, _ = _mesh("perm8")
+    problem, sol, sol_k, alpha = setup_problem(msh, 2)
+    problem.assemble_jacobian(_random_state(problem.ndofs, 2))
+    assert not problem.p2_cycle_info()["hierarchy"]
+    assert code(problem.p2_cycle_apply, 0, np.zeros(problem.ndofs)) == PGX_ESTATE
+    problem.close()
+    _lib.tuning_set("PGX_P2_PATCH", 0)
+    try:
+        problem, sol, sol_k, alpha = setup_problem(grid, 2)
+        problem.assemble_jacobian(_random_state(problem.ndofs, 2))
+        assert code(problem.p2_cycle_info) == PGX_ESTATE
+        problem.close()
+    finally:
+        _lib.tuning_set("PGX_P2_PATCH", None)

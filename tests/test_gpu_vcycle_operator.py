@@ -497,11 +497,15 @@ def test_refusals_leave_the_handle_usable(require_gpu):
         return lib.pgx_vcycle_apply(problem._h, level, kw.get("nu", 6), OMEGA, kw.get("in_form", 0), kw.get("out_form", 0), kw.get("scale", 1.0),
                                     _lib.dptr(b), _lib.dptr(z))
 
-    # a P2 handle
+    # a P2 handle: the export serves the P1 hierarchy below its P2 level (tests/test_gpu_p2_cycle_operator.py compares it), the
+    # V-cycle hook keeps its P1 precondition
     problem, sol, sol_k, alpha = setup_problem(fem.create_rectangle(DOMAIN, (16, 16)), 2)
     n2, _ = state(problem, sol, sol_k, alpha)
-    _refused(problem, PGX_ESTATE)
-    assert raw_apply(problem, 0, n2) == PGX_ESTATE
+    assert problem.mg_levels() == 3 and problem.mg_level_export(0)["Dh"].shape == (4, 17 * 17)  # (16, 16), (8, 8), (4, 4)
+    with pytest.raises(PgxError) as e:
+        problem.vcycle_apply(0, np.ones(2 * 17 * 17))
+    assert e.value.code == PGX_ESTATE
+    assert raw_apply(problem, 0, n2) == PGX_ESTATE and raw_apply(problem, 0, 2 * 17 * 17) == PGX_ESTATE
     _spmv_works(problem, n2)
     problem.close()
     # an unstructured mesh (the same triangles without the grid structure: single-level smoother, no hierarchy)
