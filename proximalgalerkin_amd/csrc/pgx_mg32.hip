@@ -246,9 +246,14 @@ __device__ __forceinline__ float2 f_load_rhs(const FSmoothArgs& A, unsigned v) {
   return A.bf[v];
 }
 
-template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR>
+// HF = 1 ("halo rings saved"; FIRST launches only): the first sweep of a launch that starts from x = 0 reads no neighbour - it is
+// the pointwise solve x_1 = omega B^-1 b - so x_1 is exact on the WHOLE image, sweep s is exact s - 1 rings in, and K sweeps
+// need a halo of K - 1: sweep 1 runs on every image row and lane, sweep s >= 2 on rows / lanes [s - 1, . - (s - 1)).  The same
+// image of 64 x 32 then owns 54 x 22 vertices instead of 52 x 20 (K = 6).  HF = 0 is every launch's code as it was.
+template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR, int HF = 0>
 __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float2* img0, float2* img1, float2* exch) {
-  constexpr int W = 64, HALO = K + (RR ? 2 : 0), TX = W - 2 * HALO, H0 = TY + 2 * HALO, NW = F32_BLOCK / 64, R = (H0 + NW - 1) / NW;
+  constexpr int W = 64, HALO = K + (RR ? 2 : 0) - HF, TX = W - 2 * HALO, H0 = TY + 2 * HALO, NW = F32_BLOCK / 64, R = (H0 + NW - 1) / NW;
+  static_assert(HF == 0 || (HF == 1 && FIRST && !RR && H0 % NW == 0), "a saved halo ring needs a launch that starts from x = 0");
   const int sx = A.nx + 1;
   const int tx = 1 + b % A.g.nfx, ty = 1 + b / A.g.nfx;
   const int i0 = tx * TX - HALO, j0 = ty * TY - HALO;  // origin of the image
@@ -266,10 +271,10 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
 #pragma unroll
   for (int k = 0; k < R; ++k) {
     const int lj = wave + NW * k;
-    if (lj < H0 - 1) {  // rows 1 .. H0-2 are updated; row 0 only hands its upward links to row 1
+    if (HF || lj < H0 - 1) {  // rows 1 .. H0-2 are updated; row 0 only hands its upward links to row 1 (HF: sweep 1 updates every row)
       const unsigned v = (unsigned)((j0 + lj) * sx + gi);
       dw[k] = Dq[v];
-      if (lj >= 1) rb[k] = f_load_rhs<IO>(A, v);
+      if (HF || lj >= 1) rb[k] = f_load_rhs<IO>(A, v);
     }
   }
   if (!FIRST) {
@@ -291,7 +296,7 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
 #pragma unroll
   for (int k = 0; k < R; ++k) {
     const int lj = wave + NW * k;
-    if (lj < H0 - 1) {
+    if (HF || lj < H0 - 1) {
       dq[k] = f_unpack_d(dw[k]);  // once per launch, after the batch of loads
       exch[lj * W + lane] = make_float2(dq[k].z, dq[k].w);
     }
@@ -306,10 +311,13 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
 #pragma unroll
   for (int k = 0; k < R; ++k) {
     const int lj = wave + NW * k;
-    if (lj >= 1 && lj < H0 - 1) {
-      d2[k] = lane_shr1f(dq[k].y);                   // D(+1,0) of the left neighbour
-      d4[k] = exch[(lj - 1) * W + lane].x;           // D(0,+1) of the vertex below
-      d6[k] = exch[(lj - 1) * W + lane - 1].y;       // D(+1,+1) of the vertex below left; lane 0 (halo, never updated) reads the guard band
+    if (HF) d2[k] = d4[k] = d6[k] = 0.f;  // rows 0 and H0-1 take sweep 1 only, which reads no link
+    if (HF || (lj >= 1 && lj < H0 - 1)) {
+      if (!HF || (lj >= 1 && lj < H0 - 1)) {
+        d2[k] = lane_shr1f(dq[k].y);                   // D(+1,0) of the left neighbour
+        d4[k] = exch[(lj - 1) * W + lane].x;           // D(0,+1) of the vertex below
+        d6[k] = exch[(lj - 1) * W + lane - 1].y;       // D(+1,+1) of the vertex below left; lane 0 (halo, never updated) reads the guard band
+      }
       if (!LEAN) {
         const float rc = __builtin_amdgcn_rcpf(fmaf(-k0, dq[k].x, nm2));
         g0[k] = -dq[k].x * A.omega * rc;
@@ -331,11 +339,11 @@ __device__ __forceinline__ void f_smooth_fast(int b, const FSmoothArgs& A, float
   for (int s = 1; s <= K; ++s) {
     const float2* const src = ((s - 1) & 1) ? img1 : img0;
     float2* const dst = (s & 1) ? img1 : img0;
-    const bool act = lane >= s && lane < W - s;
+    const bool act = lane >= s - HF && lane < W - (s - HF);
 #pragma unroll
     for (int k = 0; k < R; ++k) {
       const int lj = wave + NW * k;
-      if (lj < s || lj >= H0 - s) continue;  // wave-uniform
+      if (lj < s - HF || lj >= H0 - (s - HF)) continue;  // wave-uniform
       float au = 0.f, ap = 0.f, xur = 0.f, xpr = 0.f;
       if (!FIRST || s > 1) {
         F_ROWS(src, lj * W + lane, k, au, ap, x0)
@@ -596,13 +604,14 @@ __device__ __forceinline__ void f_smooth_bnd(int b, const FSmoothArgs& A, float2
 // free until the first sweep writes it.  A frame vertex's row is then redone from LDS by the seven-slot formula of f_smooth_bnd:
 // a frame row in a wave-uniform branch, a frame column in the one lane that holds it.  Out-of-grid entries and their D links are
 // exact zeros, Dirichlet u reads as 0 and is solved exactly, as in f_smooth_bnd.
-template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR>
+template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR, int HF = 0>
 __device__ __forceinline__ void f_smooth_bnd_full(int b, const FSmoothArgs& A, float2* img0, float2* img1, float2* exch) {
-  constexpr int W = 64, HALO = K + (RR ? 2 : 0), TX = W - 2 * HALO, H0 = TY + 2 * HALO, NW = F32_BLOCK / 64, R = (H0 + NW - 1) / NW;
+  constexpr int W = 64, HALO = K + (RR ? 2 : 0) - HF, TX = W - 2 * HALO, H0 = TY + 2 * HALO, NW = F32_BLOCK / 64, R = (H0 + NW - 1) / NW;
   // staged rows: slot s holds (aK[0..6], M[0..6]) as seven float2; slots [0, 2W): the frame rows gj = 0 and gj = ny by lane,
   // [2W, 2W + 2 H0): the frame columns gi = 0 and gi = nx by image row
   static_assert(7 * (2 * W + 2 * H0) <= H0 * W, "the frame rows' coefficients must fit into the third image");
   static_assert(14 * H0 <= F32_BLOCK && 14 <= 2 * NW, "one value of a frame column, two of a frame row per thread");
+  static_assert(HF == 0 || (HF == 1 && FIRST && !RR && H0 % NW == 0), "a saved halo ring needs a launch that starts from x = 0");
   const int nx = A.nx, ny = A.ny, sx = nx + 1;
   const RowmapGrid& g = A.g;
   int tx, ty;
@@ -643,7 +652,7 @@ __device__ __forceinline__ void f_smooth_bnd_full(int b, const FSmoothArgs& A, f
       const int v = gj * sx + gi;
       dw[k] = Dq[v];
       bc[k] = A.mask[v] != 0;
-      if (lj >= 1 && lj < H0 - 1) rb[k] = f_load_rhs<IO>(A, (unsigned)v);
+      if (HF || (lj >= 1 && lj < H0 - 1)) rb[k] = f_load_rhs<IO>(A, (unsigned)v);
       if (!FIRST) xa[k] = f_add_coarse<CADD>(A.xf[v], gi, gj, A.nxc, A.cf, A.cdu, A.cdp);
     }
   }
@@ -696,10 +705,12 @@ __device__ __forceinline__ void f_smooth_bnd_full(int b, const FSmoothArgs& A, f
   for (int k = 0; k < R; ++k) {
     const int lj = wave + NW * k;
     d2[k] = d4[k] = d6[k] = g0[k] = g1[k] = g3[k] = 0.f;
-    if (lj >= 1 && lj < H0 - 1) {
-      d2[k] = lane_shr1f(dq[k].y);
-      d4[k] = img1[(lj - 1) * W + lane].x;
-      d6[k] = img1[(lj - 1) * W + lane - 1].y;
+    if (HF || (lj >= 1 && lj < H0 - 1)) {  // (HF: rows 0 and H0-1 take sweep 1 only, which reads no link)
+      if (!HF || (lj >= 1 && lj < H0 - 1)) {
+        d2[k] = lane_shr1f(dq[k].y);
+        d4[k] = img1[(lj - 1) * W + lane].x;
+        d6[k] = img1[(lj - 1) * W + lane - 1].y;
+      }
       // damped inverse of the vertex block, once per launch (f_jacobi: a Dirichlet row of u is solved exactly).  The psi row's
       // factor of su is g1 in either case: omega (-M0 / det) on a free row, 0 on a Dirichlet one
       float a = A.sc.kc[0], bm = A.sc.mc[0], om_u = A.omega;
@@ -763,11 +774,11 @@ __device__ __forceinline__ void f_smooth_bnd_full(int b, const FSmoothArgs& A, f
   for (int s = 1; s <= K; ++s) {
     const float2* const src = ((s - 1) & 1) ? img1 : img0;
     float2* const dst = (s & 1) ? img1 : img0;
-    const bool act = lane >= s && lane < W - s;
+    const bool act = lane >= s - HF && lane < W - (s - HF);
 #pragma unroll
     for (int k = 0; k < R; ++k) {
       const int lj = wave + NW * k;
-      if (lj < s || lj >= H0 - s) continue;  // wave-uniform
+      if (lj < s - HF || lj >= H0 - (s - HF)) continue;  // wave-uniform
       float au = 0.f, ap = 0.f, xur = 0.f, xpr = 0.f;
       if (!FIRST || s > 1) {
         const float2 x0 = rows(src, lj, k, au, ap);
@@ -832,24 +843,33 @@ __device__ __forceinline__ void f_smooth_bnd_full(int b, const FSmoothArgs& A, f
 // dependent-load chains overlap with the interior tiles that follow - blocks [nbnd, nbnd + nfast) the interior tiles.  PART = 1 /
 // 2: the interior tiles / the boundary sub-tiles alone (F32_K6_SPLIT); both read the old iterate and write disjoint vertices of
 // the new one, so the order of the two launches is free.
-template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR, int PART = 0>
+// HF = 1 (f_smooth_fast): a first launch with a halo of K - 1; its boundary blocks are always whole tiles.
+template <class DT, int TY, int K, bool FIRST, int IO, int CADD, int RR, int PART = 0, int HF = 0>
 __global__ void __launch_bounds__(F32_BLOCK, RR ? 2 : F32_WAVES_EU) k_f_smooth(const FSmoothArgs A) {
-  constexpr int W = 64, H0 = (PART == 2 ? f32_tb(K, RR) : TY) + 2 * (K + (RR ? 2 : 0)), PAD = W + 1;
+  constexpr int W = 64, H0 = (PART == 2 ? f32_tb(K, RR) : TY) + 2 * (K + (RR ? 2 : 0) - HF), PAD = W + 1;
   __shared__ float2 img_[3][H0 * W + 2 * PAD];  // guard bands: inactive edge lanes read (and discard) one entry outside a row;
                                                  // [2]: the (D(0,+1), D(+1,+1)) links every image row hands to the row above it
   const int blk = blockIdx.x;
-  if constexpr (PART == 0 && K == 6) {
-    if (A.bfull && blk < A.nbnd) {
-      f_smooth_bnd_full<DT, TY, K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
-      return;
+  if constexpr (HF != 0) {
+    static_assert(PART == 0 && K == 6, "the halo-saving form is a merged six-sweep launch");
+    if (blk < A.nbnd)
+      f_smooth_bnd_full<DT, TY, K, FIRST, IO, CADD, RR, HF>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+    else
+      f_smooth_fast<DT, TY, K, FIRST, IO, CADD, RR, HF>(xcd_block(blk - A.nbnd, gridDim.x - A.nbnd, A.remap), A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+  } else {
+    if constexpr (PART == 0 && K == 6) {
+      if (A.bfull && blk < A.nbnd) {
+        f_smooth_bnd_full<DT, TY, K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+        return;
+      }
     }
+    if (PART == 2 || (PART == 0 && blk < A.nbnd))
+      f_smooth_bnd<DT, TY, f32_tb(K, RR), K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+    else if (PART == 1)
+      f_smooth_fast<DT, TY, K, FIRST, IO, CADD, RR>(xcd_block(blk, gridDim.x, A.remap), A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
+    else
+      f_smooth_fast<DT, TY, K, FIRST, IO, CADD, RR>(xcd_block(blk - A.nbnd, gridDim.x - A.nbnd, A.remap), A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
   }
-  if (PART == 2 || (PART == 0 && blk < A.nbnd))
-    f_smooth_bnd<DT, TY, f32_tb(K, RR), K, FIRST, IO, CADD, RR>(blk, A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
-  else if (PART == 1)
-    f_smooth_fast<DT, TY, K, FIRST, IO, CADD, RR>(xcd_block(blk, gridDim.x, A.remap), A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
-  else
-    f_smooth_fast<DT, TY, K, FIRST, IO, CADD, RR>(xcd_block(blk - A.nbnd, gridDim.x - A.nbnd, A.remap), A, img_[0] + PAD, img_[1] + PAD, img_[2] + PAD);
 }
 
 // last pre-smoothing launch + residual + restriction (no coarse correction, float2 result); TY >= 8: the first interior tile's
@@ -916,6 +936,32 @@ static bool f32_bnd_full(int n) {
   return t_full.get() != 0 && n >= t_min.get();
 }
 
+// The first launch of a leg with a halo of five instead of six (k_f_smooth<..., HF = 1>)?  It starts from x = 0, so its first
+// sweep is exact on the whole image and the 64 x 32 image of the 20-row tiles owns 54 x 22 vertices: 14 % fewer workgroups on
+// 2049^2 and 1025^2, and a six-sweep launch is as long as the number of images it sweeps.
+// PGX_F32_FIRST_HALO (A/B switch: 0 = the 52 x 20 tiles in every launch) and PGX_F32_FIRST_HALO_MIN: from 1025^2 up - below, the
+// launches are one round of workgroups.  pgxk_f_smooth adds the conditions of the launch.
+static bool f32_first_halo(int n) {
+  static PgxTuneInt t_on("PGX_F32_FIRST_HALO", 1), t_min("PGX_F32_FIRST_HALO_MIN", 1000000);
+  return t_on.get() != 0 && n >= t_min.get();
+}
+
+// ... as 54 x 22 tiles in the image of the 20-row ones; whole boundary tiles only, the caller has checked their conditions
+template <class DT>
+static void launch_f_smooth_first5(hipStream_t st, FSmoothArgs& A) {
+  A.g = rowmap_grid<22, 5>(A.nx, A.ny, 1);
+  const int nfast = A.g.nfx * A.g.nfy;
+  A.bfull = 1;
+  A.nbnd = A.g.ntx * A.g.nty - nfast;
+  const dim3 grid(A.nbnd + nfast), block(F32_BLOCK);
+  if (A.b32u)
+    hipLaunchKernelGGL((k_f_smooth<DT, 22, 6, true, 3, 0, 0, 0, 1>), grid, block, 0, st, A);
+  else if (A.b64u)
+    hipLaunchKernelGGL((k_f_smooth<DT, 22, 6, true, 1, 0, 0, 0, 1>), grid, block, 0, st, A);
+  else
+    hipLaunchKernelGGL((k_f_smooth<DT, 22, 6, true, 0, 0, 0, 0, 1>), grid, block, 0, st, A);
+}
+
 template <class DT, int TY, int K>
 static void launch_f_smooth_t(hipStream_t st, int first, FSmoothArgs& A, int fast_ok) {
   A.g = rowmap_grid<TY, K>(A.nx, A.ny, fast_ok);
@@ -961,9 +1007,12 @@ static void launch_f_smooth(hipStream_t st, int first, FSmoothArgs& A, int fast_
 
 // Tile rows of a launch of K sweeps.  PGX_F32_TY: 4, 8, 16 for every K; 12 and 20 exist for the six-sweep launches only (images of
 // 24 and 32 rows: three and four per wave) - other launches take the next height below, and a six-sweep image needs TY >= 8.
-static int f32_tile_rows(const GridLevel& L, int K) {
+static int f32_ty_key() {
   static PgxTuneInt t_ty("PGX_F32_TY", 0);
-  const int ty = t_ty.get();
+  return t_ty.get();
+}
+static int f32_tile_rows(const GridLevel& L, int K) {
+  const int ty = f32_ty_key();
   if (K == 6) {
     if (ty == 8 || ty == 12 || ty == 16 || ty == 20) return ty;
     if (ty == 4) return 8;
@@ -1017,7 +1066,13 @@ void pgxk_f_smooth(hipStream_t st, int K, int first, const GridLevel& L, double 
   if (K == 6) {  // a whole leg of six sweeps in ONE launch
     if (cbf || cb64u)
       launch_f_smooth_rr<16, 6>(st, first, A, L.interior_free && (!C || C->interior_free));
-    else if (ty == 8)
+    else if (first && !F32_K6_SPLIT && L.interior_free && A.sc.uniform && f32_bnd_full(L.n) && (f32_ty_key() == 0 || f32_ty_key() == 20) &&
+             f32_first_halo(L.n)) {  // the 54 x 22 tiles of a launch that starts from x = 0, in the image of the 20-row tiles
+      if (A.dbf16)
+        launch_f_smooth_first5<uint2>(st, A);
+      else
+        launch_f_smooth_first5<float4>(st, A);
+    } else if (ty == 8)
       launch_f_smooth<8, 6>(st, first, A, L.interior_free);
     else if (ty == 12)
       launch_f_smooth<12, 6>(st, first, A, L.interior_free);
