@@ -1,5 +1,6 @@
 // Host side of libpgx.so: plan building (CSR pattern, inverted vertex->cell lists), multigrid
-// hierarchy, FGMRES, SNES-mirroring Newton driver, and the extern "C" ABI of include/pgx.h.
+// hierarchy, SNES-mirroring Newton driver, and the extern "C" ABI of include/pgx.h.  The handle is defined in pgx_handle.h;
+// FGMRES and the reductions' read-back are in pgx_krylov.hip.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -16,250 +17,10 @@
 #include "../../include/pgx.h"
 #include "../../include/pgx_nd.h"
 #include "pgx_comm.h"
+#include "pgx_handle.h"
 #include "pgx_internal.h"
 
 static thread_local std::string g_create_error;
-
-// Sharded path (include/pgx.h): geometry of this rank's strip on each distributed multigrid level.  Local vertex rows
-// of level l are [ghost-low: glo | owned: H | ghost-high: ghi]; g = 2^(ldist-l) is the ghost depth: glo = g (0 on rank 0),
-// ghi = g+1 (0 on the last rank, whose H includes the top row of the mesh).  Local row 0 is an even global row on every
-// level, so vertex coarsening of the local grid IS the local part of the global coarsening.
-struct DistLevel {
-  int g, glo, H, ghi;
-};
-struct Dist {
-  bool on = false;
-  pgx_comm* comm = nullptr;
-  int rank = 0, size = 1, ldist = 0, global_ny = 0;
-  std::vector<DistLevel> L;
-  GridLevel view{};  // this rank's rows of the first replicated level (pointers into that level's global arrays)
-  int view_row0 = 0, view_glo = 0, view_H = 0, view_own0 = 0;
-  long long n_halo = 0, n_allreduce = 0, n_vcycle = 0, n_krylov = 0;  // collective counts (pgx_comm_counts)
-  double* view_S = nullptr;  // [7 * view.n] strip-shaped coarse stencils before they are merged into the global level
-  size_t own_off = 0, own_cnt = 0;  // owned entries per field on level 0: [own_off, own_off + own_cnt)
-  // P2 on strips: the edge dofs follow the vertex dofs of a field, ordered by their LOWER vertex (row-major), so the edges whose
-  // lower vertex lies in one vertex row form one contiguous block of eb = 3 nx + 1 dofs (nx in the last local row).  An edge is
-  // owned by the rank that owns its lower vertex: owned edges = [eown_off, eown_off + eown_cnt) of the edge part.
-  size_t eb = 0, eown_off = 0, eown_cnt = 0;
-  size_t nk_field() const { return own_cnt + eown_cnt; }  // owned dofs per field (Krylov vectors are owned-compact)
-  int cell0 = 0, ncell_own = 0;     // owned cells (row-major cell order)
-  double *sb = nullptr, *wc = nullptr;  // local scatter buffer (2n), owned-compact scratch (2*own_cnt)
-};
-
-struct pgx_handle {
-  int device = 0;
-  Dist dist;
-  hipStream_t st = nullptr;
-  std::string err;
-  int n = 0, nc = 0, nx = 0, ny = 0, nnz = 0;  // n = mesh vertices = dofs per field of the P1 space
-  int degree = 1;
-  int nd = 0;  // dofs per field of the SOLUTION space: n (P1) or n + n_edges (P2)
-  bool structured = false;
-  QuadTab q{};
-  double f = 0.0, alpha = 1.0;
-  // mesh + problem data
-  double* coords = nullptr;
-  int32_t* cells = nullptr;
-  uint8_t* mask = nullptr;
-  double *gbc = nullptr, *bphi = nullptr;
-  // CSR pattern + inverted lists
-  int32_t *rowptr = nullptr, *colm = nullptr, *v2c_ptr = nullptr, *v2c_ent = nullptr, *v2c_pos = nullptr;
-  std::vector<int32_t> h_rowptr, h_col;
-  size_t fill_lds = 0;
-  double *Kv = nullptr, *Mv = nullptr, *Dv = nullptr;
-  bool jac_valid = false;
-  double* geoq = nullptr;  // order-2 geometry (pgx_create_curved): [cell][quadrature point][5] = |det J|, J^-1; nullptr = affine cells
-  float2* zf_out = nullptr;  // FGMRES: the level-0 single-precision cycle leaves its result HERE as float2 (no fp64 copy); see fgmres
-  int z_f32 = 1;             // PGX_Z_F32=0: the Z_j of the Krylov method in fp64 (A/B)
-  int f32_dbf16 = 1;         // PGX_F32_DBF16=0: the single-precision cycle's D(psi) stencil as float4 (A/B); default: packed bf16, 8 B
-  bool dv_lean = false;  // the interior rows of the CSR D values are stale (residual_dev(with_d = 2)); a full fill clears it
-  // operator of the solution space (aliases the P1 arrays above for degree 1)
-  int32_t *s_rowptr = nullptr, *s_colm = nullptr;
-  double *s_K = nullptr, *s_M = nullptr, *s_D = nullptr;
-  int s_nnz = 0;
-  size_t s_fill_lds = 0;
-  int32_t* s_blk = nullptr;  // P2: row blocks of the nnz-balanced stream kernel (k_bspmv_bal): s_nblk + 1 pairs (first row, its rowptr)
-  int s_nblk = 0, spmv_bal = 1;
-  uint8_t* s_code = nullptr;  // P2 on a uniform mesh: per entry the index of its (K, M) pair in s_tab (k_bspmv_bal<true>)
-  double* s_tab = nullptr;    // 256 (K, M) pairs
-  int s_ntab = 0, spmv_dict = 1;
-  std::vector<int32_t> s_h_rowptr, s_h_col;
-  // P2 extras: cell dofs, inverted lists of the P2 plan, P1<->P2 transfers, two-level cycle scratch
-  QuadTab2 q2{};
-  int32_t *cdofs = nullptr, *p2_v2c_ptr = nullptr, *p2_v2c_ent = nullptr, *p2_v2c_pos = nullptr;
-  int32_t *v2e_ptr = nullptr, *v2e = nullptr, *edge_ends = nullptr;
-  double *p2_xu = nullptr, *p2_xp = nullptr, *p2_ru = nullptr, *p2_rp = nullptr;
-  double* p2_stash = nullptr;  // [16 * nc] element residual vectors of the P2 assembly (deterministic scatter, pgx_p2.hip)
-  double *c1_bu = nullptr, *c1_bp = nullptr, *c1_xu = nullptr, *c1_xp = nullptr;
-  // vertex-star patch smoother of the P2 level (pgx_patch.hip): NN = slots per patch (0: vertex degree > 7, smoother unavailable)
-  int patch_nn = 0, p2_patch = 1, patch_nu = 2;
-  int p2_fallback_its = 60, p2_fallbacks = 0;  // patch cycle -> sparse LU after this many Krylov iterations without convergence
-  double patch_omega = 0.8;
-  bool patch_fresh = false;  // pinv holds the inverses of the current Jacobian
-  std::vector<int32_t> patch_dof_host;
-  int32_t *pdof = nullptr, *ppos = nullptr;
-  void* pinv = nullptr;  // patch inverses: float by default (a smoother inside FGMRES: same Krylov counts as double at 512^2 ... 2048^2,
-                         // half the bytes of the stream that bounds the sweep), double with the tuning key PGX_P2_PATCH_F32=0
-  int patch_f32 = 1;
-  // structured P2 operator apply (pgx_p2st.hip): interior groups [i0, i0 + ni) x [j0, j0 + nj) through the table-driven kernel,
-  // the frame rows through the CSR form.  state: 0 off, 1 pattern verified (K / M constants not yet fetched), 2 ready
-  struct P2St {
-    int state = 0, enable = 1, dist_enable = 1, select = 1, i0 = 0, ni = 0, j0 = 0, nj = 0, nframe = 0, ref_rows[4] = {0, 0, 0, 0};
-    P2StTab tab;
-    double K[46];
-    double* Dst = nullptr;
-    float* Dstf = nullptr;
-    int32_t* frame = nullptr;
-    bool fresh = false;
-  } p2st;
-  float* s_Df = nullptr;  // float copy of D(psi) for the residuals inside the P2 cycle (k_bspmv_bal<., true>); PGX_P2_RESID_F32=0: fp64
-  int p2_resid_f32 = 1;
-  int patch_sym = 1;     // float inverses in symmetric packing (pgx_patch.hip: 512 instead of 896 B per patch); PGX_P2_PATCH_SYM=0: full rows
-  double *p2_su = nullptr, *p2_sp = nullptr;
-  // state
-  double *x = nullptr, *xk = nullptr, *F = nullptr, *dx = nullptr, *xw = nullptr, *rhs = nullptr;
-  // Krylov workspace
-  int restart = 0;
-  double *V = nullptr, *Z = nullptr, *w = nullptr, *d_small = nullptr, *partials = nullptr, *partials2 = nullptr;
-  double* h_small = nullptr;  // pinned, mapped: the device publishes small results into it (fetch_small), the host polls
-  double* h_small_dev = nullptr;              // device view of h_small
-  unsigned long long* h_seq = nullptr;        // sequence word behind the payload (host view / device view)
-  unsigned long long* h_seq_dev = nullptr;
-  unsigned long long seq = 0;
-  int lean_d = 1;           // PGX_LEAN_D=0: the Newton loop always writes the CSR form of D(psi) as well
-  int spmv_d4 = 1;          // PGX_SPMV_D4=0: the matrix-free operator apply reads the four D arrays instead of its double4 copy
-  int lazy_norm = 1;        // PGX_LAZY_NORM=0: every new Krylov vector is normalised in place (one more pass over it per iteration)
-  double rhs_scale = 1.0;   // factor the next level-0 V-cycle applies to its fp64 right-hand side as it reads it (lazy normalisation)
-  const float* rhs_f32 = nullptr;  // != nullptr: the next level-0 single-precision cycle reads its right-hand side HERE, as the float pair
-                                   // (rhs_f32, rhs_f32 + n) - a vector of FGMRES's float basis - instead of the fp64 pair it is called with
-  int v_f32 = 1;            // PGX_V_F32=0: the Krylov basis of the lean P1 path in fp64 (see fgmres)
-  double v_f32_gain = 1e-4; // PGX_V_F32_GAIN: a cycle on the float basis ends once its estimate is below this factor times its starting residual
-  double v_f32_max = 1e30;  // PGX_V_F32_MAX: a new basis vector with a norm above this (or not finite) does not fit a float: guard in fgmres
-  int v_f32_min = 1000000;  // PGX_V_F32_MIN: the float basis from this many vertices up, where the Gram-Schmidt passes are bound by HBM
-                            // bandwidth; below, its few extra iterations and cycles are not paid back by the halved streams
-  bool v_f32_off = false;   // the guard fired: fp64 basis for the rest of this Newton solve (reset by pgx_newton_solve, like omega_now)
-  int host_poll = 1;  // PGX_HOST_POLL=0: hipMemcpyAsync + hipStreamSynchronize for every small read-back (round 3)
-  // Krylov / Newton driver passes (single handles with host_poll; the last three only with the matrix-free P1 operator: krylov_lean())
-  int gs_wide = 16;       // PGX_GS_WIDE=8: Gram-Schmidt launches of at most 8 basis vectors (k_multidot / k_multiaxpy_norm; 16: one pass over w up to 16)
-  int fused_publish = 1;  // PGX_FUSED_PUBLISH=0: second reduction stage (k_reduce_rows / k_reduce_partials) and k_publish as two launches
-  int ticket_reduce = 1;  // PGX_TICKET_REDUCE=0: the second stage (and the publish) as a launch of its own behind k_multidot, k_multiaxpy_norm
-                          // and k_axpy_norms; 1: their last block to arrive runs it (PgxTicket).  Only with fused_publish, see ticketed()
-  unsigned long long* d_ticket = nullptr;  // the ticket counters (PGX_TK_WORDS): zeroed when the handle is created, set back to zero by the
-                                           // last block of every ticketed launch, freed with the handle
-  int fused_resid = 1;    // PGX_FUSED_RESID=0: true residual of a restart cycle as operator apply + k_scale_copy(-1) + k_axpy(+b)
-  int lean_rhs = 1;       // PGX_LEAN_RHS=0: the Newton loop forms rhs = -F as a vector, fgmres zero-fills x and accumulates into it
-  int fused_step = 1;     // PGX_FUSED_STEP=0: xw += dx as k_axpy, |dx| and |xw| as two dev_norm calls with a read-back each
-  // multigrid
-  std::vector<GridLevel> lev;
-  double *tmp_u = nullptr, *tmp_p = nullptr, *res_u = nullptr, *res_p = nullptr;  // level-0 scratch (each n)
-  double omega_now = 0.0;  // smoother damping in force for the current Newton solve (fgmres lowers it on stagnation)
-  int coarse_sweeps = 4;  // prototype (oracle/krylov_proto.py): 2..60 sweeps give identical Krylov counts
-  int tail_start = -1;  // first level handled by the fused k_mg_tail launch (-1: none)
-  int xcd_remap = 2;    // bit 1 of the `first` kernel argument; PGX_XCD_REMAP=0 disables (A/B: +1..3 %)
-  int tail_verts = 1100;
-  int spmv_stream = 1;  // PGX_SPMV_STREAM=0: 8-lanes-per-row kernel instead of the CSR-stream kernel
-  int nu_coarse = 0;    // PGX_NU_COARSE: cap on the sweeps of unfused (small) levels; 0 = same as the fine levels
-  int fused_k3 = 1;     // PGX_FUSED_K3=0: two sweeps per launch even when nu is a multiple of 3
-  int fused_legs = 1;   // PGX_FUSED_LEGS=0: one launch per sweep / residual / restriction / prolongation
-  int fused_min = 4000;  // fused legs from 65^2 vertices up (measured with the row-mapped kernels: 2048^2 460 -> 451 ms, 1024^2
-                         // 113.5 -> 106.4, 512^2 68.5 -> 61.5 against 60000; the first, tile-mapped kernels needed >= 60000)
-  int cgs_selective = 1;  // second Gram-Schmidt projection only when the first one cancelled (PGX_CGS_SELECTIVE=0: always)
-  long cgs_skipped = 0, cgs_total = 0;
-  // second projection iff |w'|^2 < eta^2 |w|^2.  The textbook eta = 1/sqrt(2) re-orthogonalises 249 of 266 iterations at 2048^2 (a
-  // good preconditioner makes w = J M^-1 v_j ~ v_j: the first projection always cancels most of w); eta = 0.01 bounds the loss of
-  // orthogonality per step by 100 eps, re-orthogonalises 11 of 266 and leaves every Krylov count unchanged: 448 -> 416 ms per solve
-  double cgs_eta2 = 1e-4;
-  TailArgs tail{};
-  // sparse direct preconditioner (pc_type lu): nested-dissection multifrontal LU of the mixed Newton matrix (pgx_nd.hip)
-  pgx_nd* lu = nullptr;
-  // pgx_create_lu_dist: this handle is one of `size` REPLICAS (whole mesh, whole iterate on every rank) whose sparse LU is
-  // distributed over the ranks (pgx_nd_create_dist).  Residuals and observables are broadcast from rank 0 so that the
-  // replicas stay bitwise identical (the P2 assembly uses atomics) and issue the same collectives.
-  pgx_comm* lu_comm = nullptr;
-  double* Jmix = nullptr;  // [4 * s_nnz] values of the mixed CSR matrix in the layout lu was created with
-  bool dh_interior = false;
-  // PGX_D_DIRECT (default 1; 0: the launches before it, for A/B): on a single handle of degree 1 with a uniform finest level the
-  // kernels that compute D(psi) store every copy the solver reads - k_resid_fill_grid / k_resid_fill_frame write Dh, Dd4 and Dq of
-  // level 0 (no k_csr_to_stencil_h, k_pack_d4, k_f_pack_d there), k_rap7h writes Dq of the coarse level it produces, and the
-  // coarsenings onto levels of at least rap_lds_min vertices (PGX_RAP_LDS_MIN) stage their fine stencils in LDS.  Same bits.
-  int d_direct = 1;
-  int rap_lds_min = 60000;  // 257^2 and above: staged 7.2 against 9.7 us there, 13.4 / 22 at 513^2, 44 / 101 at 1025^2
-  bool d0_direct = false;  // with dh_interior: the frame rows of lev[0].Dh and lev[0].Dd4 / Dq are in place as well (residual_dev)
-  int stag_its = 12;       // PGX_STAG_ITS / PGX_STAG_GAIN: stagnation test of the smoother damping (fgmres)
-  double stag_gain = 1e-4;
-  int smooth_d32 = 0;      // PGX_SMOOTH_D32=1: the finest-level smoother reads a single-precision copy of the D stencils.  OFF by
-                           // default: its launches get 10 % shorter, but the operator apply that follows the V-cycle no longer finds
-                           // the double stencils in the Infinity Cache (k_st_spmv_r 0.74 -> 0.55 of the HBM peak) - net +0.9 %
-  int k6_max = 0;          // levels with at most this many vertices run 6 sweeps per smoother launch (PGX_K6_MAX)
-  int mg_f32 = 1;          // PGX_MG_F32=0: the round-3 fp64 V-cycle.  Default: single-precision V-cycle legs (pgx_mg32.hip) on every
-                           // uniform level with at least f32_min vertices above the fused tail - half the bytes per launch
-  int f32_min = 4000;      // PGX_F32_MIN
-  int f32_k6_max = 4300000;  // PGX_F32_K6_MAX: levels with at most this many vertices (2049^2) run a whole leg of six sweeps as ONE launch,
-                             // whether or not they fuse the restriction (f32_rr_max).  us per V-cycle at 2048^2 (round 4): off 459.7, up to
-                             // 129^2 453.5, up to 257^2 448.5, up to 513^2 444.3; ms per solve: up to 513^2 162.6, up to 2049^2 150.2
-  int f32_rr_max = 300000;   // PGX_F32_RR_MAX (measured, us per V-cycle from that level: 257^2 and below -2 each, 513^2 +3, 1025^2 +5, 2049^2 +12): levels with at most this many vertices fuse the residual + restriction into the last
-                             // pre-smoothing launch (pgx_mg32.hip, RR mode)
-  int resid_grid = 1;      // uniform structured P1: residual + D(psi) through k_resid_fill_grid (PGX_RESID_GRID=0: general kernel)
-  int spmv_stencil = 1;    // structured P1: the outer-Krylov operator apply through the level-0 stencil kernels (matrix-free)
-  bool lu_active = false;  // the current Newton solve preconditions with the factorisation
-  bool check_replicas = false;  // PGX_CHECK_REPLICAS=1: assert that the replicas' residuals are bitwise identical
-  // observables
-  double *obs_partials = nullptr, *d_out6 = nullptr;
-  int obs_blocks = 0;
-  // profiling
-  bool prof = false;
-  double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  std::vector<void*> allocs;
-};
-
-#define HIPCHK(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess) {                                                                     \
-      h->err = std::string(#call) + ": " + hipGetErrorString(e_);                               \
-      return PGX_EHIP;                                                                          \
-    }                                                                                           \
-  } while (0)
-
-template <typename T>
-static int dalloc(pgx_handle* h, T** p, size_t count) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-  if (e != hipSuccess) {
-    h->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-    return PGX_ENOMEM;
-  }
-  h->allocs.push_back(q);
-  *p = (T*)q;
-  return PGX_OK;
-}
-#define DALLOC(p, count)                         \
-  do {                                           \
-    int rc_ = dalloc(h, &(p), (size_t)(count));  \
-    if (rc_) return rc_;                         \
-  } while (0)
-
-struct PhaseTimer {
-  pgx_handle* h;
-  int slot;
-  PhaseTimer(pgx_handle* h_, int s) : h(h_), slot(s) {
-    static const char* const names[8] = {"pgx:residual", "pgx:jacobian", "pgx:mg_setup/lu_factor", "pgx:spmv", "pgx:precond",
-                                         "pgx:orthogonalise", "pgx:observables", "pgx:newton_solve"};
-    pgx_roctx(names[s & 7]);
-    if (h->prof) hipEventRecord(h->e0, h->st);
-  }
-  ~PhaseTimer() {
-    pgx_roctx(nullptr);
-    if (h->prof) {
-      hipEventRecord(h->e1, h->st);
-      hipEventSynchronize(h->e1);
-      float ms = 0;
-      hipEventElapsedTime(&ms, h->e0, h->e1);
-      h->ms[slot] += ms;
-    }
-  }
-};
 
 // ---- tuning table (pgx_scope.h: pgx_tune) ----
 namespace {
@@ -687,7 +448,6 @@ static int build_plan_p2(pgx_handle* h, const pgx_mesh* m, const std::vector<uin
 // (K, M) dictionary of the P2 level for k_bspmv_bal<true>: distinct pairs after rounding to a grid of 2^-40 of the largest entry
 // (finer than the tolerance of detect_uniform below; a function of each entry alone: deterministic).  Seeded with nothing; every round lists up to 4096 unmatched entries, the host adds their distinct values.
 // More than 256 pairs (a non-uniform mesh) => no dictionary, the kernel streams K and M as before.
-static int allreduce_dev(pgx_handle* h, double* dev, size_t n);
 // max |x_i| through atomicMax on the bit pattern (non-negative doubles order like their 64-bit patterns)
 __global__ void __launch_bounds__(256) k_maxabs(int64_t n, const double* __restrict__ x, unsigned long long* out) {
   double m = 0.0;
@@ -925,7 +685,7 @@ static int halo_solution(pgx_handle* h, double* fu, double* fp) {
   if (rc) h->err = h->dist.comm->err;
   return rc;
 }
-static int allreduce_dev(pgx_handle* h, double* dev, size_t n) {
+int allreduce_dev(pgx_handle* h, double* dev, size_t n) {
   const int rc = h->dist.comm->allreduce(h->st, dev, n);
   ++h->dist.n_allreduce;
   if (rc) h->err = h->dist.comm->err;
@@ -1285,7 +1045,6 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_STAG_ITS")) h->stag_its = std::max(2, atoi(e));
   if (const char* e = pgx_tune("PGX_STAG_GAIN")) h->stag_gain = atof(e);
   if (const char* e = pgx_tune("PGX_FUSED_MIN")) h->fused_min = atoi(e);
-  if (const char* e = pgx_tune("PGX_CGS_SELECTIVE")) h->cgs_selective = atoi(e);
   if (const char* e = pgx_tune("PGX_CGS_ETA2")) h->cgs_eta2 = atof(e);
   if (const char* e = pgx_tune("PGX_COARSE_SWEEPS")) h->coarse_sweeps = atoi(e);
   auto fail = [&](int rc) {
@@ -1548,7 +1307,7 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
     DALLOC(h->w, n2);
     DALLOC(h->d_small, 4 * (h->restart + 2));
     DALLOC(h->partials, (size_t)PGX_RED_BLOCKS * (h->restart + 2));
-    DALLOC(h->partials2, ((n2 + PGX_BLOCK - 1) / PGX_BLOCK) * (size_t)62);
+    DALLOC(h->partials2, 2 * (size_t)pgxk_multidot_blocks(n2));  // pgxk_axpy_norms: two rows of its grid
     DALLOC(h->d_ticket, PGX_TK_WORDS);
     HIPCHK(hipMemsetAsync(h->d_ticket, 0, sizeof(unsigned long long) * PGX_TK_WORDS, h->st));
     {  // small read-backs (norms, the Hessenberg column, observables): pinned + mapped + coherent, one sequence word at the end
@@ -1618,7 +1377,7 @@ extern "C" void pgx_destroy(pgx_handle* h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->st) hipStreamSynchronize(h->st);
-  if (h->cgs_selective && pgx_tune("PGX_CGS_REPORT"))
+  if (pgx_tune("PGX_CGS_REPORT"))
     fprintf(stderr, "pgx: selective CGS2 skipped the second projection in %ld of %ld Krylov iterations\n", h->cgs_skipped, h->cgs_total);
   if (h->lu) pgx_nd_destroy(h->lu);
   for (void* p : h->allocs) hipFree(p);
@@ -1632,10 +1391,6 @@ extern "C" void pgx_destroy(pgx_handle* h) {
 // ------------------------------------------------------------------------------------------------
 // state access
 // ------------------------------------------------------------------------------------------------
-#define NEED(hh)          \
-  if (!(hh)) return PGX_EINVAL; \
-  hipSetDevice((hh)->device)
-
 extern "C" int pgx_num_dofs(const pgx_handle* h, int64_t* nd) {
   if (!h || !nd) return PGX_EINVAL;
   *nd = 2 * (int64_t)h->nd;
@@ -1714,151 +1469,6 @@ extern "C" int pgx_set_alpha(pgx_handle* h, double a) {
 // ------------------------------------------------------------------------------------------------
 // building blocks
 // ------------------------------------------------------------------------------------------------
-// 2-norm of a device vector.  Sharded handles pass OWNED-COMPACT vectors (len = 2 * own_cnt): the squared norms of
-// the ranks are summed by one all-reduce before the square root.
-// Replicas of a distributed-LU handle (pgx_create_lu_dist) compute every steering scalar redundantly - norms, Gram-Schmidt
-// coefficients, observables.  The kernels are deterministic, so the copies agree bitwise today; but a rank that ever took a
-// different branch would issue different collectives and RCCL has no timeout.  So the few doubles that DECIDE control flow are
-// always taken from rank 0 (one tiny all-reduce of "mine if rank 0 else zero"); only the O(n) residual comparison stays behind
-// PGX_CHECK_REPLICAS.  No-op on ordinary and on sharded handles.
-static int replica_agree(pgx_handle* h, double* dev, size_t n) {
-  if (!h->lu_comm || h->lu_comm->size == 1) return PGX_OK;
-  if (h->lu_comm->rank != 0) HIPCHK(hipMemsetAsync(dev, 0, n * sizeof(double), h->st));
-  const int rc = h->lu_comm->allreduce(h->st, dev, n);
-  if (rc) h->err = "replica agreement: " + h->lu_comm->err;
-  return rc;
-}
-
-// Small device results -> host WITHOUT a stream synchronisation (round 4; VERDICT r03: "no hipStreamSynchronize between Krylov
-// iterations").  A one-workgroup kernel at the end of the enqueued work stores the n doubles into pinned, mapped host memory with
-// system-scope stores, fences, and publishes a sequence number; the host polls that word.  What used to cost a D2H copy command, a
-// stream synchronisation and the driver's wake-up (15-25 us in which the GPU idles) costs the PCIe write and a cache miss.
-__global__ void __launch_bounds__(64) k_publish(int n, const double* __restrict__ src, double* dst, int n2, const double* __restrict__ src2,
-                                                double* dst2, unsigned long long seq, unsigned long long* seqp) {
-  for (int i = threadIdx.x; i < n; i += 64) __hip_atomic_store(dst + i, src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  for (int i = threadIdx.x; i < n2; i += 64) __hip_atomic_store(dst2 + i, src2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __threadfence_system();  // one wave: every lane's stores are ordered before lane 0's flag store below
-  if (threadIdx.x == 0) __hip_atomic_store(seqp, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-static int wait_published(pgx_handle* h, unsigned long long seq);  // the bounded host poll on the sequence word
-// h_small[hoff .. hoff + n) <- dsrc[0 .. n) (and optionally a second range), blocking until the values have arrived
-static int fetch_small(pgx_handle* h, const double* dsrc, size_t n, size_t hoff = 0, const double* dsrc2 = nullptr, size_t n2 = 0,
-                       size_t hoff2 = 0) {
-  if (!h->host_poll) {
-    HIPCHK(hipMemcpyAsync(h->h_small + hoff, dsrc, sizeof(double) * n, hipMemcpyDeviceToHost, h->st));
-    if (n2) HIPCHK(hipMemcpyAsync(h->h_small + hoff2, dsrc2, sizeof(double) * n2, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
-    return PGX_OK;
-  }
-  const unsigned long long seq = ++h->seq;
-  hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->st, (int)n, dsrc, h->h_small_dev + hoff, (int)n2, dsrc2, h->h_small_dev + hoff2,
-                     seq, h->h_seq_dev);
-  return wait_published(h, seq);
-}
-// the second stage of a reduction and its read-back in one launch (pgxk_reduce_publish): rows of nb partials -> dout[0 .. nrows) on
-// the device and h_small[hoff_r ..), and dsrc1[0 .. n1) -> h_small[hoff1 ..); blocks like fetch_small.  Callers: fused_readback(h)
-static bool fused_readback(const pgx_handle* h) { return h->fused_publish && h->host_poll && !h->dist.on && !h->lu_comm; }
-static int reduce_fetch(pgx_handle* h, int nb, const double* partials, int nrows, double* dout, size_t hoff_r, const double* dsrc1 = nullptr,
-                        size_t n1 = 0, size_t hoff1 = 0) {
-  const unsigned long long seq = ++h->seq;
-  pgxk_reduce_publish(h->st, nb, partials, nrows, dout, h->h_small_dev + hoff_r, (int)n1, dsrc1, h->h_small_dev + hoff1, seq, h->h_seq_dev);
-  return wait_published(h, seq);
-}
-// The second stage inside the producer launch (PgxTicket, pgx_internal.h): where reduce_fetch would follow the launch.  Sharded handles,
-// replicas and the copy read-back keep the launches: an all-reduce or a copy sits between the stages there.
-static bool ticketed(const pgx_handle* h) { return h->ticket_reduce && fused_readback(h); }
-// a ticket whose reducer publishes what reduce_fetch(h, ., ., ., ., hoff_r, dsrc1, n1, hoff1) would; the caller waits for *seq
-static PgxTicket ticket_publish(pgx_handle* h, unsigned long long* seq, size_t hoff_r, const double* dsrc1 = nullptr, size_t n1 = 0,
-                                size_t hoff1 = 0) {
-  PgxTicket t;
-  t.ctr = h->d_ticket;
-  t.hout = h->h_small_dev + hoff_r;
-  t.n1 = (int)n1;
-  t.src1 = dsrc1;
-  t.dst1 = h->h_small_dev + hoff1;
-  t.seq = *seq = ++h->seq;
-  t.seqp = h->h_seq_dev;
-  return t;
-}
-// a ticket whose reducer leaves its results on the device only
-static PgxTicket ticket_device(pgx_handle* h) {
-  PgxTicket t;
-  t.ctr = h->d_ticket;
-  return t;
-}
-static int wait_published(pgx_handle* h, unsigned long long seq) {
-  // Bounded wait: a collective or a kernel ahead of k_publish that never completes leaves hipStreamQuery at NotReady
-  // for ever - after PGX_COMM_TIMEOUT seconds (default 120; the transports' own limit) the call fails with PGX_ECOMM / PGX_EHIP and
-  // a message instead of spinning.  The poll backs off: a pause per probe, and after ~50 us without an answer a yield per batch of
-  // probes, so that eight ranks plus the BLAS threads of an oversubscribed host do not starve each other.
-  static const double limit_s = [] {
-    const char* t = getenv("PGX_COMM_TIMEOUT");
-    return t ? std::max(1.0, atof(t)) : 120.0;
-  }();
-  std::chrono::steady_clock::time_point t0;
-  bool timed = false;
-  for (unsigned long spins = 1;; ++spins) {
-    if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == seq) return PGX_OK;
-    __builtin_ia32_pause();
-    if (spins > 0x2000 && (spins & 0xff) == 0) std::this_thread::yield();
-    if ((spins & 0x3fff) == 0) {  // a failed launch or a faulted kernel must not leave the host spinning
-      if (!timed) {
-        t0 = std::chrono::steady_clock::now();
-        timed = true;
-      } else if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s) {
-        h->err = "fetch_small: the device did not publish within PGX_COMM_TIMEOUT (" + std::to_string((int)limit_s) +
-                 " s): a kernel or a collective ahead of it on the stream does not complete" + (h->dist.on || h->lu_comm ? " (a peer rank is missing?)" : "");
-        return (h->dist.on || h->lu_comm) ? PGX_ECOMM : PGX_EHIP;
-      }
-      const hipError_t e = hipStreamQuery(h->st);
-      if (e == hipSuccess) {
-        if (__atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == seq) return PGX_OK;
-        h->err = "fetch_small: the stream drained without publishing (launch failure)";
-        return PGX_EHIP;
-      }
-      if (e != hipErrorNotReady) {
-        h->err = std::string("fetch_small: ") + hipGetErrorString(e);
-        return PGX_EHIP;
-      }
-    }
-  }
-}
-
-static int dev_norm(pgx_handle* h, const double* v, double* out, size_t len = 0) {
-  if (fused_readback(h)) {  // k_reduce_partials (nv = 1) + k_publish as one launch, or inside k_multidot's
-    const size_t l = len ? len : 2 * (size_t)h->nd;
-    int rc;
-    if (ticketed(h)) {
-      unsigned long long seq;
-      PgxTicket tk = ticket_publish(h, &seq, 0);
-      const bool done = pgxk_multidot(h->st, l, 1, v, 0, v, h->partials, h->d_small, nullptr, 8, &tk);
-      if (!done) h->err = "dev_norm: k_multidot<1> without its second stage";  // (one vector: every instantiation carries it)
-      rc = done ? wait_published(h, seq) : PGX_EHIP;
-    } else {
-      pgxk_multidot(h->st, l, 1, v, 0, v, h->partials, nullptr);
-      rc = reduce_fetch(h, pgxk_multidot_blocks(l), h->partials, 1, h->d_small, 0);
-    }
-    if (rc) return rc;
-    *out = std::sqrt(h->h_small[0]);
-    return PGX_OK;
-  }
-  pgxk_multidot(h->st, len ? len : 2 * (size_t)h->nd, 1, v, 0, v, h->partials, h->d_small);
-  if (h->dist.on) {
-    const int rc = allreduce_dev(h, h->d_small, 1);
-    if (rc) return rc;
-  }
-  {
-    const int rc = replica_agree(h, h->d_small, 1);
-    if (rc) return rc;
-  }
-  {
-    const int rc = fetch_small(h, h->d_small, 1);
-    if (rc) return rc;
-  }
-  *out = std::sqrt(h->h_small[0]);
-  return PGX_OK;
-}
-
 // PGX_D_DIRECT applies: single handle, degree 1, uniform finest level through the grid kernels, fp64 stencils without the float copy
 static bool d_direct_on(const pgx_handle* h) {
   return h->d_direct && !h->dist.on && h->degree == 1 && h->structured && h->resid_grid && !h->lev.empty() && h->lev[0].uniform &&
@@ -2022,7 +1632,7 @@ static void p2st_apply(pgx_handle* h, const double* xu, const double* xp, const 
 // y = J x on device vectors of length 2*nd
 static void level_apply(pgx_handle* h, int l, int mode, const double* xu, const double* xp, const double* bu,
                         const double* bp, double omega, int first, double* yu, double* yp);
-static void spmv_dev(pgx_handle* h, const double* x, double* y) {
+void spmv_dev(pgx_handle* h, const double* x, double* y) {
   if (h->degree == 2 && h->spmv_stream && h->spmv_bal && p2st_ready(h)) {
     static PgxTuneInt bench_inner("PGX_P2ST_BENCH_INNER", 0);  // measurement hook (tools/p2_spmv_bench.py): time the float-D form
     p2st_apply(h, x, x + h->nd, nullptr, nullptr, y, y + h->nd, bench_inner.get() != 0);
@@ -2113,7 +1723,7 @@ static const float2* vcycle_f(pgx_handle* h, int l, const double* bu, const doub
   }
   return cu;
 }
-static inline bool f32_cycle_ok(const pgx_handle* h, int l, int nu) {
+bool f32_cycle_ok(const pgx_handle* h, int l, int nu) {
   return h->lev[l].f32 && h->fused_legs && l + 1 < (int)h->lev.size() && nu >= 2 && (nu % 2 == 0 || (nu % 3 == 0 && h->fused_k3));
 }
 
@@ -2375,7 +1985,7 @@ static int vcycle_dist_f(pgx_handle* h, int l, double* bu, double* bp, double* o
 }
 
 // owned entries of a local (u | psi) vector <-> owned-compact vector [u_owned | psi_owned]
-static void gather_owned(pgx_handle* h, const double* loc, double* cmp) {
+void gather_owned(pgx_handle* h, const double* loc, double* cmp) {
   const Dist& D = h->dist;
   const size_t nf = D.nk_field(), nd = (size_t)h->nd, nv = (size_t)h->n;
   for (int f = 0; f < 2; ++f) {
@@ -2693,14 +2303,7 @@ static int lu_factor(pgx_handle* h) {
   return rc;
 }
 
-// FGMRES keeps its Z_j as float2 fields (round 5) where they leave the single-precision cycle and the operator apply is the
-// matrix-free stencil kernel: one predicate for the solver and for pgx_spmv_bench, which replays the solver's sequence
-static inline bool z_f32_active(const pgx_handle* h, int nu) {
-  return h->z_f32 && !h->dist.on && !h->lu_active && h->degree == 1 && h->structured && !h->lev.empty() && h->lev[0].uniform &&
-         h->spmv_stencil == 1 && f32_cycle_ok(h, 0, nu);
-}
-
-static int precond(pgx_handle* h, const double* b, double* z, int nu, double omega) {
+int precond(pgx_handle* h, const double* b, double* z, int nu, double omega) {
   if (h->lu_active) {
     int rc = pgx_nd_solve(h->lu, b, z, 1);
     if (rc) h->err = std::string("pc_type lu: ") + pgx_nd_last_error(h->lu);
@@ -2731,372 +2334,6 @@ static int precond(pgx_handle* h, const double* b, double* z, int nu, double ome
   return PGX_OK;
 }
 
-// Single handle on the matrix-free structured P1 operator (uniform level 0): where the lean driver passes apply - the operator kernel's
-// residual mode (PGX_FUSED_RESID), the signed right-hand side without a -F copy or a zero fill (PGX_LEAN_RHS), the fused Newton update
-// (PGX_FUSED_STEP).  Sharded, replicated-LU, P2 and general-mesh handles keep the plain sequence.
-static inline bool krylov_lean(const pgx_handle* h) {
-  return !h->dist.on && !h->lu_comm && !h->lu_active && h->degree == 1 && h->structured && h->spmv_stencil == 1 && !h->lev.empty() &&
-         h->lev[0].uniform;
-}
-
-// FGMRES(restart) on J dx = b, right-preconditioned by one V-cycle; CGS2 orthogonalisation with
-// batched device dot products; Givens rotations on the host (one small D2H copy + sync per iteration).
-// bnorm_known >= 0: the 2-norm of b, already on the host (the Newton driver's |F|: b = -F) - saves a reduction and its read-back
-// bsign = +-1: the system solved is J dx = bsign * b (the Newton driver hands in F itself with bsign = -1 instead of a copy -F)
-static int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts* o, int* its_out, double* relres,
-                  double bnorm_known = -1.0, double bsign = 1.0) {
-  const size_t n2 = 2 * (size_t)h->nd;
-  // Sharded: the Krylov space lives on OWNED dofs (basis vectors V_j, b, residuals are owned-compact, length nk, so the
-  // tuned vector kernels run unchanged and every dot product is "local partial + one all-reduce"); the operators work
-  // on local vectors with ghost rows (Z_j, x), with a gather after every SpMV.
-  const bool dist = h->dist.on;
-  const size_t nk = dist ? 2 * h->dist.nk_field() : n2;
-  double* const wk = dist ? h->dist.wc : h->w;
-  // P2: the two-level preconditioner is weaker on the late large-alpha systems (30-60 its): use the full basis
-  const int m = (h->degree == 2) ? h->restart : std::min(std::max(o->ksp_restart, 1), h->restart);
-  std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), y(m);
-  double bnorm = bnorm_known;
-  int rc = PGX_OK;
-  if (!(bnorm_known >= 0.0) && (rc = dev_norm(h, b, &bnorm, nk))) return rc;
-  // lean: no zero fill - the first solution update starts its sums from 0.0 instead of reading zeros back (x_unset), and x = 0 is
-  // written only on the ways out that leave no update behind
-  const bool lean = krylov_lean(h);
-  bool x_unset = lean && h->lean_rhs;
-  if (!x_unset) pgxk_set(h->st, n2, 0.0, x);
-  *its_out = 0;
-  *relres = 0.0;
-  if (bnorm == 0.0 || !std::isfinite(bnorm)) {
-    if (x_unset) pgxk_set(h->st, n2, 0.0, x);
-    if (bnorm != 0.0) *relres = bnorm;
-    return PGX_OK;
-  }
-  const double target = o->ksp_rtol * bnorm;
-  int its = 0;
-  double res = bnorm;
-  double prev_cycle_res = bnorm;
-  bool first_cycle = true;
-  bool redo = false;  // the cycle about to start repeats one that the float-basis guard abandoned (below)
-  // Smoother damping.  The default 0.8 is the fast choice while psi is smooth on the mesh scale (lambda_max of the
-  // Jacobi-scaled element matrices is 2); an overshot Newton iterate makes exp(psi) jump by orders of magnitude
-  // inside single elements, lambda_max approaches its bound 3 (dofs per triangle) and only omega < 2/3 is a
-  // convergent smoother.  FGMRES tolerates a changing preconditioner, so on stagnation (30 iterations that gain
-  // < 10x) the rest of this Newton solve runs at the unconditionally stable value.
-  const double omega_safe = 0.6;
-  double omega = (h->omega_now > 0.0) ? std::min(h->omega_now, o->mg_omega) : o->mg_omega;
-  // Lazy normalisation (round 4): a new basis vector stays as the Gram-Schmidt pass left it, W_{j+1} = w', and only its scale
-  // s_{j+1} = 1 / |w'| is kept (v_i = s_i W_i): the V-cycle multiplies its right-hand side by s_j as its first launch reads it, the
-  // batched dot products come back as s_i^2 (W_i . w) - the coefficients the projection w' = w - sum_i (v_i . w) v_i applies to the
-  // stored W_i - and the pass over w that only divided it by its norm (67 MB read + written per iteration) is gone.  Only where
-  // the preconditioner is the single-precision cycle entered on level 0 (it is the one that takes the factor).
-  const bool lazy = h->lazy_norm && h->cgs_selective && !h->lu_active && h->degree == 1 && m + 2 <= PGX_DOT_SCALE_MAX && !h->lev.empty() &&
-                    f32_cycle_ok(h, 0, o->mg_nu);  // (the non-selective CGS2 kernels carry no scale factors: that mode runs un-lazy)
-  // Z_j in single precision (round 5): on this path z_j leaves a float cycle, so storing it as one float2 field loses nothing - the
-  // cycle's last launch writes it in place, the operator apply reads it (k_st_spmv_r<true>), the solution update sums it
-  // (k_lincomb_f2): 100 MB less per Krylov iteration at 2048^2 than the fp64 pair.  w = J z_j and H stay fp64.
-  const bool zf32 = z_f32_active(h, o->mg_nu);
-  // The basis V in single precision (PGX_V_F32, the lean P1 path only, from PGX_V_F32_MIN vertices up): the vectors are stored as float in the same [u | psi] layout, at
-  // a stride padded to 16 bytes, inside the storage of the fp64 basis; w = J z_j is fp64 in h->w, dot products and projections are
-  // fp64 on the widened basis, and the last chunk of the second pass stores (float) w' as V_{j+1} and returns the norm of the ROUNDED
-  // vector.  The Gram-Schmidt passes move j + 3.5 instead of 2 j + 5 fp64 vectors.  The Arnoldi estimate of such a cycle stalls near
-  // 1e-7 of the residual the cycle started from (the basis spans r / beta to float accuracy only), so a cycle ends once the estimate has
-  // gained v_f32_gain; the loop head then takes the TRUE residual in fp64 and the next cycle starts from it.
-  const bool vf32_ok = h->v_f32 && lean && lazy && zf32 && h->nd >= h->v_f32_min;
-  float* const Vf = reinterpret_cast<float*>(h->V);
-  const size_t ldvf = (nk + 3) & ~(size_t)3;  // (m + 1) ldvf floats fit in the (restart + 1) nk doubles of h->V
-  while (true) {
-    double beta;
-    const bool vf32 = vf32_ok && !h->v_f32_off;
-    if (first_cycle && its >= o->ksp_max_it) break;
-    if (first_cycle) {
-      beta = bnorm;
-      if (vf32)
-        pgxk_scale_copy_f32(h->st, nk, bsign * (1.0 / beta), b, Vf);
-      else
-        pgxk_scale_copy(h->st, nk, bsign * (1.0 / beta), b, h->V);  // (bsign = -1: bitwise (-b) / beta)
-    } else {
-      // r = bsign b - J x
-      PhaseTimer t(h, 3);
-      if (lean && h->fused_resid) {  // one pass: the operator kernel stores bsign b - J x
-        pgxk_st_spmv(h->st, h->lev[0], h->alpha, x, x + h->nd, h->xcd_remap ? 1 : 0, h->w, h->w + h->nd, nullptr, b, b + h->nd, bsign);
-      } else {
-        spmv_dev(h, x, h->w);
-        if (dist) gather_owned(h, h->w, wk);
-        pgxk_scale_copy(h->st, nk, -1.0, wk, wk);
-        pgxk_axpy(h->st, nk, bsign, b, wk);
-      }
-      rc = dev_norm(h, wk, &beta, nk);
-      if (rc) return rc;
-      res = beta;
-      if (o->monitor > 1) printf("      ksp true residual after cycle: %.6e (rel %.3e)\n", beta, beta / bnorm);
-      // (redo: the same residual as at the head of the abandoned cycle - x was not touched - which passed both tests then)
-      if (!redo && beta <= target) break;
-      // attainable-accuracy exit: a full restart cycle that gains < 10x once we are at LU-level residuals
-      if (!redo && beta > 0.1 * prev_cycle_res && beta <= 1e-7 * bnorm) break;
-      if (its >= o->ksp_max_it) break;
-      prev_cycle_res = beta;
-      if (vf32)
-        pgxk_scale_copy_f32(h->st, nk, 1.0 / beta, wk, Vf);
-      else
-        pgxk_scale_copy(h->st, nk, 1.0 / beta, wk, h->V);
-    }
-    const bool was_first = first_cycle;
-    first_cycle = false;
-    redo = false;
-    bool abandoned = false;
-    double hn_bad = 0.0;
-    // float basis: the estimate is only trusted down to v_f32_gain times the residual this cycle started from
-    const double cycle_target = vf32 ? std::max(target, h->v_f32_gain * beta) : target;
-    std::fill(g.begin(), g.end(), 0.0);
-    g[0] = beta;
-    float2* const Zf = reinterpret_cast<float2*>(h->Z);
-    PgxDotScale sc2;  // s_i^2
-    std::vector<double> sv((size_t)m + 2, 1.0);  // s_i
-    for (int i = 0; i < PGX_DOT_SCALE_MAX; ++i) sc2.s[i] = 1.0;
-    int j = 0;
-    for (; j < m && its < o->ksp_max_it; ++j) {
-      double* vj = h->V + (size_t)j * nk;
-      double* zj = h->Z + (size_t)j * n2;
-      {
-        PhaseTimer t(h, 4);
-        h->rhs_scale = lazy ? sv[j] : 1.0;
-        h->zf_out = zf32 ? Zf + (size_t)j * h->nd : nullptr;
-        h->rhs_f32 = vf32 ? Vf + (size_t)j * ldvf : nullptr;  // (vj is then not read: the cycle's first launch takes the float pair)
-        rc = precond(h, vj, zj, o->mg_nu, omega);
-        h->rhs_f32 = nullptr;
-        h->zf_out = nullptr;
-        h->rhs_scale = 1.0;
-        if (rc) return rc;
-      }
-      {
-        PhaseTimer t(h, 3);
-        if (dist) {
-          spmv_dev(h, zj, h->w);
-          gather_owned(h, h->w, h->V + (size_t)(j + 1) * nk);
-        } else if (zf32) {
-          double* const wn = vf32 ? h->w : h->V + (size_t)(j + 1) * n2;  // float basis: w stays fp64, in the scratch
-          pgxk_st_spmv(h->st, h->lev[0], h->alpha, nullptr, nullptr, h->xcd_remap ? 1 : 0, wn, wn + h->nd, Zf + (size_t)j * h->nd);
-        } else {
-          spmv_dev(h, zj, h->V + (size_t)(j + 1) * n2);
-        }
-      }
-      // w = J z_j was written straight into the V_{j+1} slot (float basis: into h->w).  CGS2 (classical Gram-Schmidt, always two
-      // passes: one pass loses orthogonality on these ill-conditioned systems and the true residual stalls).
-      // Each pass is ONE batched dot kernel [h; ww] = [V_0..V_j, w]^T w plus one batched axpy; the norm of the
-      // result comes from Pythagoras on the second pass (|w''|^2 = ww' - |h2|^2, cancellation-free because
-      // the second pass removes almost nothing), so no separate norm kernel.
-      double* wj = h->V + (size_t)(j + 1) * nk;
-      float* const vnext = Vf + (size_t)(j + 1) * ldvf;  // float basis: where (float) w' goes
-      double hn = 0.0;
-      {
-        PhaseTimer t(h, 5);
-        double* d_h1 = h->d_small;
-        double* d_h2 = h->d_small + (m + 2);
-        const PgxDotScale* const dsc = lazy ? &sc2 : nullptr;
-        // pass 1: h1 = V^T w.  passes 2+3 fused: w' = w - V h1 and [h2; |w'|^2] in one sweep over the basis.
-        // Sharded: each batch of partial dot products is completed by ONE packed all-reduce, enqueued on the stream.
-        PgxTicket tkd = ticket_device(h);
-        PgxTicket* const tk1 = ticketed(h) ? &tkd : nullptr;  // h1's second stage in the last block of the dot-product launch
-        if (vf32)
-          pgxk_multidot_f32(h->st, nk, j + 1, Vf, ldvf, h->w, nullptr, h->partials, d_h1, dsc, h->gs_wide, tk1);
-        else
-          pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h1, dsc, h->gs_wide, tk1);
-        if (dist && (rc = allreduce_dev(h, d_h1, j + 1))) return rc;
-        double wp2, h1h1 = 0.0, hh = 0.0;
-        bool second;
-        if (h->cgs_selective) {
-          // lean second pass: w' = w - V h1 and |w'|^2; V^T w' (for the second projection) only if the test below asks for it
-          if (ticketed(h)) {  // ... in the last block of the projection launch
-            unsigned long long seq;
-            const unsigned long long seq0 = h->seq;
-            PgxTicket tk = ticket_publish(h, &seq, (size_t)(m + 2) + j + 1, d_h1, (size_t)(j + 1), 0);
-            const bool done = vf32 ? pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h1, 0, h->w, vnext, h->partials, d_h2 + j + 1, h->gs_wide, &tk)
-                                   : pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, d_h2 + j + 1, h->gs_wide, &tk);
-            if (done) {
-              rc = wait_published(h, seq);
-            } else {  // an instantiation without the second stage: the launch of its own
-              h->seq = seq0;
-              rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_h2 + j + 1, (size_t)(m + 2) + j + 1, d_h1, (size_t)(j + 1), 0);
-            }
-            if (rc) return rc;
-          } else if (fused_readback(h)) {  // the norm's second stage and the read-back of [h1; |w'|^2] in one launch
-            if (vf32)
-              pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h1, 0, h->w, vnext, h->partials, nullptr, h->gs_wide);
-            else
-              pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, nullptr, h->gs_wide);
-            if ((rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_h2 + j + 1, (size_t)(m + 2) + j + 1, d_h1, (size_t)(j + 1), 0)))
-              return rc;
-          } else {
-            if (vf32)
-              pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h1, 0, h->w, vnext, h->partials, d_h2 + j + 1, h->gs_wide);
-            else
-              pgxk_multiaxpy_norm(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials, d_h2 + j + 1, h->gs_wide);
-            if (dist && (rc = allreduce_dev(h, d_h2 + j + 1, 1))) return rc;
-            if ((rc = replica_agree(h, h->d_small, 2 * (size_t)(m + 2)))) return rc;
-            if ((rc = fetch_small(h, d_h1, (size_t)(j + 1), 0, d_h2 + j + 1, 1, (size_t)(m + 2) + j + 1))) return rc;
-          }
-          for (int i = 0; i <= j; ++i) {
-            h->h_small[i] /= sv[i];  // lazy: the device holds s_i^2 (W_i . w); the Hessenberg entry is s_i (W_i . w)
-            h1h1 += h->h_small[i] * h->h_small[i];
-          }
-          wp2 = h->h_small[(m + 2) + j + 1];
-          // "twice is enough" (Kahan / Parlett; Daniel-Gragg-Kaufman-Stewart): the second projection is only needed when the
-          // first one cancelled most of w, |w'| < eta |w| with |w|^2 = |w'|^2 + |h1|^2
-          second = wp2 < h->cgs_eta2 * (wp2 + h1h1);
-          if (second) {
-            PgxTicket tkd2 = ticket_device(h);
-            PgxTicket* const tk2 = ticketed(h) ? &tkd2 : nullptr;
-            if (vf32)  // against the vector as stored: (float) w', widened
-              pgxk_multidot_f32(h->st, nk, j + 1, Vf, ldvf, nullptr, vnext, h->partials, d_h2, dsc, h->gs_wide, tk2);
-            else
-              pgxk_multidot(h->st, nk, j + 1, h->V, nk, wj, h->partials, d_h2, dsc, h->gs_wide, tk2);
-            if (dist && (rc = allreduce_dev(h, d_h2, j + 1))) return rc;
-            if ((rc = replica_agree(h, d_h2, (size_t)(j + 1)))) return rc;
-            if ((rc = fetch_small(h, d_h2, (size_t)(j + 1), (size_t)(m + 2)))) return rc;
-            for (int i = 0; i <= j; ++i) h->h_small[(m + 2) + i] /= sv[i];
-          }
-        } else {
-          if (j + 1 <= 60) {
-            pgxk_axpy_dot(h->st, nk, j + 1, h->V, nk, d_h1, wj, h->partials2, d_h2);
-          } else {  // beyond the fused kernel's LDS capacity (61 slices of 2 KB): two separate passes
-            pgxk_multiaxpy(h->st, nk, j + 1, h->V, nk, d_h1, wj);
-            pgxk_multidot(h->st, nk, j + 2, h->V, nk, wj, h->partials, d_h2);
-          }
-          if (dist && (rc = allreduce_dev(h, d_h2, j + 2))) return rc;
-          if ((rc = replica_agree(h, h->d_small, 2 * (size_t)(m + 2)))) return rc;
-          if ((rc = fetch_small(h, h->d_small, 2 * (size_t)(m + 2)))) return rc;
-          wp2 = h->h_small[(m + 2) + j + 1];
-          second = true;
-        }
-        for (int i = 0; i <= j; ++i) {
-          const double h2 = second ? h->h_small[(m + 2) + i] : 0.0;
-          H[(size_t)i * m + j] = h->h_small[i] + h2;
-          hh += h2 * h2;
-        }
-        if (second && vf32) {
-          // float basis: the stored vector, widened, is projected again and re-rounded in the same launch, which also sums the squares of
-          // what it stores: hn is the norm of the vector kept (Pythagoras would describe the unrounded one).  One more small read-back,
-          // on the rare path only.
-          double* const d_n2 = d_h2 + j + 1;
-          if (ticketed(h)) {
-            unsigned long long seq;
-            const unsigned long long seq0 = h->seq;
-            PgxTicket tk = ticket_publish(h, &seq, (size_t)(m + 2) + j + 1);
-            if (pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h2, 1, h->w, vnext, h->partials, d_n2, h->gs_wide, &tk)) {
-              rc = wait_published(h, seq);
-            } else {
-              h->seq = seq0;
-              rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_n2, (size_t)(m + 2) + j + 1);
-            }
-            if (rc) return rc;
-          } else if (fused_readback(h)) {
-            pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h2, 1, h->w, vnext, h->partials, nullptr, h->gs_wide);
-            if ((rc = reduce_fetch(h, pgxk_stream_blocks(nk), h->partials, 1, d_n2, (size_t)(m + 2) + j + 1))) return rc;
-          } else {
-            pgxk_multiaxpy_norm_f32(h->st, nk, j + 1, Vf, ldvf, d_h2, 1, h->w, vnext, h->partials, d_n2, h->gs_wide);
-            if ((rc = fetch_small(h, d_n2, 1, (size_t)(m + 2) + j + 1))) return rc;
-          }
-          hn = std::sqrt(std::max(h->h_small[(m + 2) + j + 1], 0.0));
-        } else if (second) {
-          hn = std::sqrt(std::max(wp2 - hh, 0.0));
-          // last pass fused with the normalisation: v_{j+1} = (w' - V h2) / hn   (|w''|^2 = |w'|^2 - |h2|^2, Pythagoras)
-          if (hn > 0.0) {
-            if (lazy)
-              pgxk_multiaxpy(h->st, nk, j + 1, h->V, nk, d_h2, wj);
-            else
-              pgxk_multiaxpy_scale(h->st, nk, j + 1, h->V, nk, d_h2, 1.0 / hn, wj);
-          }
-        } else {
-          hn = std::sqrt(std::max(wp2, 0.0));
-          if (hn > 0.0 && !lazy) pgxk_scale_copy(h->st, nk, 1.0 / hn, wj, wj);
-          ++h->cgs_skipped;
-        }
-        // Guard of the float basis: an overshot Newton iterate puts 1e300 into D(psi), and w = J z_j can then leave the float range.  A
-        // new vector whose norm is not finite (or above v_f32_max) ends the float basis for the rest of this Newton solve: this cycle is
-        // abandoned - its columns are dropped, x is not updated, its iterations stay counted - and redone in fp64 from the same residual.
-        if (vf32 && (!std::isfinite(hn) || hn > h->v_f32_max)) {
-          ++its;
-          ++h->cgs_total;
-          hn_bad = hn;
-          abandoned = true;
-          break;
-        }
-        if (lazy && hn > 0.0) {
-          sv[j + 1] = 1.0 / hn;
-          sc2.s[j + 1] = sv[j + 1] * sv[j + 1];
-        }
-        ++h->cgs_total;
-      }
-      H[(size_t)(j + 1) * m + j] = hn;
-      for (int i = 0; i < j; ++i) {
-        const double t1 = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
-        H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
-        H[(size_t)i * m + j] = t1;
-      }
-      const double a = H[(size_t)j * m + j], bb = H[(size_t)(j + 1) * m + j];
-      const double rr = std::hypot(a, bb);
-      cs[j] = rr == 0.0 ? 1.0 : a / rr;
-      sn[j] = rr == 0.0 ? 0.0 : bb / rr;
-      H[(size_t)j * m + j] = rr;
-      H[(size_t)(j + 1) * m + j] = 0.0;
-      g[j + 1] = -sn[j] * g[j];
-      g[j] = cs[j] * g[j];
-      res = std::fabs(g[j + 1]);
-      ++its;
-      if (dist) ++h->dist.n_krylov;
-      if (o->monitor > 1) printf("      ksp %3d  rnorm %.6e  rel %.3e\n", its, res, res / bnorm);
-      if (!std::isfinite(res)) {
-        if (x_unset) pgxk_set(h->st, n2, 0.0, x);
-        *its_out = its;
-        *relres = res / bnorm;
-        return PGX_OK;
-      }
-      if (res <= cycle_target || hn == 0.0) {
-        ++j;
-        break;
-      }
-      // Stagnation test.  A healthy solve gains a factor 5-8 per iteration; a smoother that diverges on the rough late iterates
-      // shows within a dozen iterations.  FGMRES tolerates a changing preconditioner, so the damping is switched IN PLACE (no
-      // restart: the basis built so far stays useful) as soon as `stag_its` iterations have gained less than 1e-4 (round 1
-      // waited for a full cycle of 30 that gained < 10x and restarted).
-      if (omega > omega_safe && j + 1 == std::min(m, h->stag_its) && res > h->stag_gain * beta) {
-        h->omega_now = omega = omega_safe;  // sticky until pgx_newton_solve returns: later iterates are rough too
-        if (o->monitor > 1) printf("      ksp stagnates: smoother damping -> %.2f for the rest of this Newton solve\n", omega);
-      }
-    }
-    if (abandoned) {
-      h->v_f32_off = true;
-      if (o->monitor > 1) printf("      ksp: basis vector outside the float range (norm %.3e): this cycle again, with the fp64 basis\n", hn_bad);
-      res = beta;
-      first_cycle = was_first;  // the first cycle starts again from b (x is still unset with PGX_LEAN_RHS), a later one from b - J x
-      redo = !was_first;
-      continue;
-    }
-    // y = H^-1 g (upper triangular), x += Z y
-    for (int i = j - 1; i >= 0; --i) {
-      double s = g[i];
-      for (int k = i + 1; k < j; ++k) s -= H[(size_t)i * m + k] * y[k];
-      y[i] = s / H[(size_t)i * m + i];
-    }
-    // y travels with the launch as an argument (at most PGX_DOT_SCALE_MAX coefficients; a longer basis - P2 - uploads it as before, and
-    // h_small is then not touched again before that copy is done: the next read-back is ordered behind it on the stream)
-    const double* const y_arg = j <= PGX_DOT_SCALE_MAX ? y.data() : nullptr;
-    if (!y_arg) {
-      for (int i = 0; i < j; ++i) h->h_small[i] = y[i];
-      HIPCHK(hipMemcpyAsync(h->d_small, h->h_small, sizeof(double) * j, hipMemcpyHostToDevice, h->st));
-    }
-    if (zf32)
-      pgxk_lincomb_f2(h->st, (size_t)h->nd, j, Zf, (size_t)h->nd, h->d_small, x, x + h->nd, x_unset ? 0 : 1, y_arg);
-    else
-      pgxk_lincomb(h->st, n2, j, h->Z, n2, h->d_small, x, x_unset ? 0 : 1, y_arg);
-    x_unset = false;
-    // (no synchronisation: the loop head recomputes the TRUE residual b - Jx - it decides convergence, not the Arnoldi estimate)
-  }
-  if (x_unset) pgxk_set(h->st, n2, 0.0, x);  // ksp_max_it == 0: no cycle ran
-  *its_out = its;
-  *relres = res / bnorm;
-  return PGX_OK;
-}
-
 // ------------------------------------------------------------------------------------------------
 // C ABI: fine-grained calls
 // ------------------------------------------------------------------------------------------------
@@ -3121,111 +2358,6 @@ extern "C" int pgx_residual(pgx_handle* h, const double* x, double* F, double* f
   }
   if (F) return copy_out(h, F, h->F);
   HIPCHK(hipStreamSynchronize(h->st));
-  return PGX_OK;
-}
-
-// Test hook (include/pgx.h): the two-launch route against the ticket route of the Gram-Schmidt reductions, on data of its own in the
-// handle's Krylov storage.  Reads no state of a solve and leaves none behind but scratch contents, and the sequence number.
-extern "C" int pgx_reduce_selfcheck(pgx_handle* h, int nv, int64_t len, int basis_f32, int reps, uint64_t seed, int64_t* mismatches) {
-  NEED(h);
-  if (!mismatches) return PGX_EINVAL;
-  const size_t n2 = 2 * (size_t)h->nd;
-  if (h->dist.on || h->lu_comm || !h->host_poll) {
-    h->err = "pgx_reduce_selfcheck: single handles with the polled read-back only";
-    return PGX_EINVAL;
-  }
-  if (nv < 1 || nv > std::min(h->restart - 1, PGX_DOT_SCALE_MAX) || len < 2 || (len & 1) || (size_t)len > n2 || reps < 1) {
-    h->err = "pgx_reduce_selfcheck: 1 <= nv <= min(restart - 1, " + std::to_string(PGX_DOT_SCALE_MAX) + "), len even, 2 <= len <= 2 nd, reps >= 1";
-    return PGX_EINVAL;
-  }
-  const size_t l = (size_t)len;
-  const size_t ldvf = (l + 3) & ~(size_t)3, ldv = basis_f32 ? ldvf : l;
-  float* const Vf = reinterpret_cast<float*>(h->V);
-  float* const vnext = Vf + (size_t)nv * ldvf;       // float basis: where (float) w' goes
-  double* const wsave = h->Z;                         // the vector as filled
-  double* const wkeep = h->Z + n2;                    // w' of the two-launch route (float basis: vnext, len / 2 words)
-  const size_t wwords = basis_f32 ? l / 2 : l;        // 8-byte words of the stored w'
-  const int m2 = h->restart + 2;
-  double* const d_a = h->d_small;                     // two-launch route: [h (nv); |w'|^2]
-  double* const d_b = h->d_small + m2;                // ticket route
-  std::vector<double> ha(nv + 1), hb(nv + 1), pa(nv + 1), pb(nv + 1), wa(wwords), wb(wwords);
-  int64_t bad = 0;
-  auto differ = [](const double* a, const double* b, size_t n) {
-    int64_t d = 0;
-    for (size_t i = 0; i < n; ++i) {
-      uint64_t x, y;
-      memcpy(&x, a + i, 8);
-      memcpy(&y, b + i, 8);
-      d += x != y;
-    }
-    return d;
-  };
-  auto project = [&](double* out, PgxTicket* tk) {  // w' = w - V h (h: the two-launch route's dot products) and |w'|^2
-    return basis_f32 ? pgxk_multiaxpy_norm_f32(h->st, l, nv, Vf, ldvf, d_a, 0, h->w, vnext, h->partials, out, h->gs_wide, tk)
-                     : pgxk_multiaxpy_norm(h->st, l, nv, h->V, ldv, d_a, h->w, h->partials, out, h->gs_wide, tk);
-  };
-  double* const wres = basis_f32 ? reinterpret_cast<double*>(vnext) : h->w;
-  for (int rep = 0; rep < reps; ++rep) {
-    const unsigned long long sd = (unsigned long long)seed * 1000003ull + (unsigned long long)rep * 65ull;
-    for (int i = 0; i < nv; ++i) {
-      if (basis_f32)
-        pgxk_fill_hash(h->st, l, sd + 1 + i, nullptr, Vf + (size_t)i * ldvf);
-      else
-        pgxk_fill_hash(h->st, l, sd + 1 + i, h->V + (size_t)i * ldv, nullptr);
-    }
-    pgxk_fill_hash(h->st, l, sd, h->w, nullptr);
-    pgxk_scale_copy(h->st, l, 1.0, h->w, wsave);
-    PgxDotScale sc;
-    for (int i = 0; i < PGX_DOT_SCALE_MAX; ++i) sc.s[i] = 1.0 + (double)((i * 7 + rep) % 13) / 16.0;
-    const PgxDotScale* const scp = (rep & 1) ? &sc : nullptr;  // both second-stage kernels, k_reduce_partials and its scaled form
-    // dot products: two launches, then the ticket
-    HIPCHK(hipMemsetAsync(h->d_small, 0xff, sizeof(double) * 2 * (size_t)m2, h->st));
-    if (basis_f32)
-      pgxk_multidot_f32(h->st, l, nv, Vf, ldvf, h->w, nullptr, h->partials, d_a, scp, h->gs_wide);
-    else
-      pgxk_multidot(h->st, l, nv, h->V, ldv, h->w, h->partials, d_a, scp, h->gs_wide);
-    PgxTicket tkd = ticket_device(h);
-    const bool dot_tk = basis_f32 ? pgxk_multidot_f32(h->st, l, nv, Vf, ldvf, h->w, nullptr, h->partials, d_b, scp, h->gs_wide, &tkd)
-                                  : pgxk_multidot(h->st, l, nv, h->V, ldv, h->w, h->partials, d_b, scp, h->gs_wide, &tkd);
-    (void)dot_tk;  // false: this instantiation keeps the second-stage launch and the two routes are one
-    // projection and norm, two launches: the partials, then k_reduce_publish
-    project(nullptr, nullptr);
-    int rc = reduce_fetch(h, pgxk_stream_blocks(l), h->partials, 1, d_a + nv, (size_t)m2 + nv, d_a, (size_t)nv, 0);
-    if (rc) return rc;
-    for (int i = 0; i < nv; ++i) pa[i] = h->h_small[i];
-    pa[nv] = h->h_small[(size_t)m2 + nv];
-    HIPCHK(hipMemcpyAsync(wa.data(), wres, sizeof(double) * wwords, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipMemcpyAsync(ha.data(), d_a, sizeof(double) * (nv + 1), hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
-    for (int i = 0; i <= nv; ++i) h->h_small[i] = h->h_small[(size_t)m2 + i] = 0.0;
-    // the same inputs again, with the ticket
-    pgxk_scale_copy(h->st, l, 1.0, wsave, h->w);
-    HIPCHK(hipMemsetAsync(wkeep, 0, sizeof(double) * wwords, h->st));
-    if (basis_f32) HIPCHK(hipMemsetAsync(vnext, 0, sizeof(float) * ldvf, h->st));
-    {
-      unsigned long long seq;
-      const unsigned long long seq0 = h->seq;
-      PgxTicket tk = ticket_publish(h, &seq, (size_t)m2 + nv, d_a, (size_t)nv, 0);
-      if (project(d_b + nv, &tk)) {
-        rc = wait_published(h, seq);
-      } else {
-        h->seq = seq0;
-        rc = reduce_fetch(h, pgxk_stream_blocks(l), h->partials, 1, d_b + nv, (size_t)m2 + nv, d_a, (size_t)nv, 0);
-      }
-      if (rc) return rc;
-    }
-    for (int i = 0; i < nv; ++i) pb[i] = h->h_small[i];
-    pb[nv] = h->h_small[(size_t)m2 + nv];
-    HIPCHK(hipMemcpyAsync(wb.data(), wres, sizeof(double) * wwords, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipMemcpyAsync(hb.data(), d_b, sizeof(double) * (nv + 1), hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
-    bad += differ(ha.data(), hb.data(), (size_t)nv + 1);  // device results: the dot products and the norm
-    bad += differ(pa.data(), pb.data(), (size_t)nv + 1);  // what the host was sent
-    bad += differ(pa.data(), ha.data(), (size_t)nv + 1);  // ... is what the device holds
-    bad += differ(wa.data(), wb.data(), wwords);          // the stored w'
-  }
-  HIPCHK(hipGetLastError());
-  *mismatches = bad;
   return PGX_OK;
 }
 
@@ -3984,18 +3116,20 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
       break;
     }
     // xw += dx; fused: the same pass leaves the block sums of |dx|^2 and |xw|^2 (partials2: nothing else in the Newton loop uses
-    // it) for the step test below, which then needs one read-back and no further pass
-    const bool fstep = h->fused_step && fused_readback(h) && !use_lu && !mg_first && krylov_lean(h);
-    int step_nb = 0;
-    // ticketed: the last block of the step's launch sums |dx|^2 and |xw|^2 and publishes them to h_small[2], [3] (the residual norm
-    // read back in between takes h_small[0]); the host reads them below, behind the wait for that norm, without a launch or a wait more
-    const bool fstep_tk = fstep && ticketed(h);
-    if (fstep_tk) {
-      unsigned long long seq;
-      PgxTicket tk = ticket_publish(h, &seq, 2);
-      step_nb = pgxk_axpy_norms(h->st, n2, h->dx, h->xw, h->partials2, h->d_small + 2, &tk);
-    } else if (fstep)
-      step_nb = pgxk_axpy_norms(h->st, n2, h->dx, h->xw, h->partials2);
+    // it) for the step test below, which then needs one read-back and no further pass.  On the ticket route the last block of the
+    // step's launch publishes the two sums to h_small[2], [3] (the residual norm read back in between takes h_small[0]) and the host
+    // reads them below, behind the wait for that norm, without a launch or a wait more; the launch of its own comes after that norm
+    // and takes h_small[0], [1]
+    const PgxRoute step_route = read_back_route(h);
+    const bool fstep = h->fused_step && step_route != PGX_RB_PLAIN && !use_lu && !mg_first && krylov_lean(h);
+    const size_t step_off = step_route == PGX_RB_TICKET ? 2 : 0;
+    const PgxReadBack step_rb{pgxk_multidot_blocks(n2), h->partials2, 2, h->d_small + step_off, step_off};
+    PgxPending step_pending{};
+    if (fstep)
+      step_pending = read_back_start(h, step_rb, step_route, [&](PgxTicket* tk, double* out) {
+        pgxk_axpy_norms(h->st, n2, h->dx, h->xw, h->partials2, out, tk);
+        return true;
+      });
     else
       pgxk_axpy(h->st, n2, 1.0, h->dx, h->xw);
     if (dist && (rc = halo_solution(h, h->xw, h->xw + h->nd))) return rc;
@@ -4017,13 +3151,10 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
       rsn = PGX_SNES_CONVERGED_FNORM_RELATIVE;
     } else {
       double snorm, xnorm;
-      if (fstep_tk) {  // published by the step's launch, which completed before the residual norm's did
-        snorm = std::sqrt(h->h_small[2]);
-        xnorm = std::sqrt(h->h_small[3]);
-      } else if (fstep) {
-        if ((rc = reduce_fetch(h, step_nb, h->partials2, 2, h->d_small, 0))) return rc;
-        snorm = std::sqrt(h->h_small[0]);
-        xnorm = std::sqrt(h->h_small[1]);
+      if (fstep) {
+        if ((rc = read_back_finish(h, step_rb, step_pending))) return rc;
+        snorm = std::sqrt(h->h_small[step_off]);
+        xnorm = std::sqrt(h->h_small[step_off + 1]);
       } else {
         rc = owned_norm(h->dx, &snorm);
         if (rc) return rc;

@@ -1,5 +1,5 @@
-// Internal declarations shared by pgx_kernels.hip (device code + launch wrappers) and pgx_api.hip
-// (host-side plan building, Newton / FGMRES / multigrid drivers, C ABI).  gfx950 only.
+// Internal declarations shared by pgx_kernels.hip (device code + launch wrappers), pgx_api.hip (host-side plan building,
+// Newton / multigrid drivers, C ABI) and pgx_krylov.hip (FGMRES and the reductions' read-back).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -324,9 +324,7 @@ void pgxk_resid_fill_grid(hipStream_t st, int write_d, const GridLevel& L, size_
 // direct != 0 (PGX_D_DIRECT): the frame goes through the compact k_resid_fill_frame (one thread per frame vertex), and with write_d
 // and write_sh both kernels also store L.Dh of the frame and the copies L.Dd4 / L.Dq (where allocated) of every vertex: nothing of
 // level 0 is left for pgxk_csr_to_stencil_h, pgxk_f_pack_d and pgxk_pack_d4.  colm: the CSR columns (the frame's Dh slots).
-// CGS2 with fused passes: (w' = w - V h1; [h2; |w'|^2] = [V,w']^T w') in one pass, then v = (w' - V h2)*scale
-void pgxk_axpy_dot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h1, double* w,
-                   double* partials, double* out);
+// CGS2, second projection fused with the normalisation: v = (w' - V h2) * scale
 void pgxk_multiaxpy_scale(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h,
                           double scale, double* w);
 // w -= V h and out[0] = |w'|^2 in one pass over the basis (selective CGS2: the lean second pass)

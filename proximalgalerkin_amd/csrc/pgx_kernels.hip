@@ -10,7 +10,7 @@
 //   k_st_resid_restrict_t          b_c = P^T(b - Jx) in one launch;  k_st_apply<MODE> plain sweeps on mid levels
 //   k_mg_tail_lds / k_mg_tail      whole V-cycle of all small levels in one launch
 //   k_rap7 / k_rap7h, k_csr_to_stencil(_h), k_restrict, k_prolong_add   hierarchy set-up and transfers
-//   k_multidot<NV>, k_axpy_dot, k_multiaxpy_scale<NV>, ...                3-pass CGS2 and Krylov vector kernels
+//   k_multidot<NV>, k_multiaxpy_norm, k_multiaxpy_scale<NV>, ...              3-pass CGS2 and Krylov vector kernels
 //   k_observables (+ P2 twins in pgx_p2.hip)
 #include "pgx_internal.h"
 #include "pgx_stencil.h"
@@ -1576,7 +1576,7 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_reduce_partials(int nblocks, int 
   const double r = block_sum(s, sm);
   if (threadIdx.x == 0) out[v] = r;
 }
-// the same with a factor per dot product (lazy normalisation of the Krylov basis: pgx_api.hip, fgmres)
+// the same with a factor per dot product (lazy normalisation of the Krylov basis: pgx_krylov.hip, fgmres)
 __global__ void __launch_bounds__(PGX_BLOCK) k_reduce_partials_scaled(int nblocks, int nv, const double* __restrict__ p, PgxDotScale sc,
                                                                       double* __restrict__ out) {
   __shared__ double sm[PGX_BLOCK / WAVE];
@@ -1666,7 +1666,7 @@ bool pgxk_multidot_f32(hipStream_t st, size_t len, int nv, const float* V, size_
 
 // The second stage of a two-stage reduction and the read-back of its result in ONE one-block launch: rows of nb partials are
 // summed in the fixed shape of k_reduce_rows / k_reduce_partials (nv = 1) - thread t adds p[t], p[t + 256], ..., then block_sum -
-// so out[r] is bitwise what those kernels leave; then wave 0 does what k_publish (pgx_api.hip) does: the sums and up to n1 more
+// so out[r] is bitwise what those kernels leave; then wave 0 does what k_publish (pgx_krylov.hip) does: the sums and up to n1 more
 // device doubles go to mapped host memory with system-scope stores, a fence, and the sequence word the host polls.  Ordered
 // behind its producers by the stream; nothing waits on the device.
 __global__ void __launch_bounds__(PGX_BLOCK) k_reduce_publish(int nb, const double* __restrict__ p, int nrows, double* out, double* hout,
@@ -1753,62 +1753,6 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_multiaxpy(size_t len2, const doub
   }
 }
 
-// CGS2, passes 2+3 fused:  w' = w - V h1  and then  [h2; |w'|^2] = [V, w']^T w'  in ONE pass over the basis.
-// A block owns a 256-element slice of every basis vector: while it forms w' it parks the slices in LDS
-// (nv x 2 KB), then dots them against w' from LDS - the basis is read from HBM once instead of twice.
-// Two-stage fixed-shape reduction (per-block partials, then k_reduce_partials) -> bitwise reproducible.
-__global__ void __launch_bounds__(PGX_BLOCK) k_axpy_dot(size_t len, int nv, const double* __restrict__ V, size_t ldv,
-                                                        const double* __restrict__ h1, double* __restrict__ w,
-                                                        double* __restrict__ partials) {
-  extern __shared__ double sh[];  // [nv+1][256] slices (+ w'), then hs[nv]
-  double* hs = sh + (size_t)(nv + 1) * PGX_BLOCK;
-  const int t = threadIdx.x;
-  const int lane = t & (WAVE - 1), wid = t / WAVE;
-  if (t < nv) hs[t] = h1[t];
-  constexpr int NW = PGX_BLOCK / WAVE;
-  constexpr int MAXA = 16;  // ceil(62 / 4): vectors handled by one wave
-  double acc[MAXA];
-#pragma unroll
-  for (int k = 0; k < MAXA; ++k) acc[k] = 0.0;
-  const size_t nchunks = (len + PGX_BLOCK - 1) / PGX_BLOCK;
-  for (size_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-    __syncthreads();  // previous chunk's LDS image fully consumed (also orders the hs[] fill the first time)
-    const size_t i = chunk * PGX_BLOCK + t;
-    const bool live = i < len;
-    double wv = live ? w[i] : 0.0;
-#pragma unroll 8
-    for (int v = 0; v < nv; ++v) {
-      const double a = live ? __builtin_nontemporal_load(V + (size_t)v * ldv + i) : 0.0;
-      sh[v * PGX_BLOCK + t] = a;
-      wv -= hs[v] * a;
-    }
-    if (live) w[i] = wv;
-    sh[nv * PGX_BLOCK + t] = wv;
-    __syncthreads();
-    const double* wl = sh + (size_t)nv * PGX_BLOCK;
-    double wr[NW];
-#pragma unroll
-    for (int r = 0; r < NW; ++r) wr[r] = wl[lane + WAVE * r];
-#pragma unroll
-    for (int k = 0; k < MAXA; ++k) {
-      const int v = wid + NW * k;
-      if (v <= nv) {
-        const double* sv = sh + (size_t)v * PGX_BLOCK;
-#pragma unroll
-        for (int r = 0; r < NW; ++r) acc[k] += sv[lane + WAVE * r] * wr[r];
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < MAXA; ++k) {
-    const int v = wid + NW * k;
-    if (v <= nv) {
-      const double r = wave_sum(acc[k]);
-      if (lane == 0) partials[(size_t)v * gridDim.x + blockIdx.x] = r;  // [v][block]: coalesced second stage
-    }
-  }
-}
-
 // out[v] = sum_b p[v][b]  (row-contiguous partials)
 __global__ void __launch_bounds__(PGX_BLOCK) k_reduce_rows(int nb, const double* __restrict__ p,
                                                            double* __restrict__ out) {
@@ -1818,18 +1762,6 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_reduce_rows(int nb, const double*
   for (int b = threadIdx.x; b < nb; b += blockDim.x) s += row[b];
   const double r = block_sum(s, sm);
   if (threadIdx.x == 0) out[blockIdx.x] = r;
-}
-
-// out[0..nv-1] = h2, out[nv] = |w'|^2.  partials must hold ceil(len/256) * (nv+1) doubles.
-void pgxk_axpy_dot(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h1, double* w,
-                   double* partials, double* out) {
-  size_t nchunks = (len + PGX_BLOCK - 1) / PGX_BLOCK;
-  const unsigned nb = (unsigned)std::min<size_t>(nchunks, 4096);  // blocks loop over chunks: 8x fewer partials at 2048^2
-  const size_t lds = ((size_t)(nv + 1) * PGX_BLOCK + nv) * sizeof(double);
-  if (first_use_on_device(1))
-    hipFuncSetAttribute((const void*)k_axpy_dot, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-  hipLaunchKernelGGL(k_axpy_dot, dim3(nb), dim3(PGX_BLOCK), lds, st, len, nv, V, ldv, h1, w, partials);
-  hipLaunchKernelGGL(k_reduce_rows, dim3(nv + 1), dim3(PGX_BLOCK), 0, st, (int)nb, partials, out);
 }
 
 // CGS2 pass 4 fused with the normalisation:  v_next = (w - V h2) * scale
@@ -1880,8 +1812,8 @@ void pgxk_multiaxpy_scale(hipStream_t st, size_t len, int nv, const double* V, s
 
 // w -= sum_v h[v] V_v in chunks of <= 8 (16: `wide`) vectors; the LAST chunk also leaves the block's share of |w'|^2 in partials[block]
 // (fixed-shape two-stage reduction: reproducible).  The lean second pass of selective CGS2: one read of the basis, one
-// read-modify-write of w, no LDS parking of basis slices (k_axpy_dot does that to get V^T w' in the same pass, which is only
-// needed when the second projection is - 11 of 266 iterations at 2048^2).
+// read-modify-write of w; V^T w' is not formed in the same pass, because it is only needed when the second projection is - 11 of
+// 266 iterations at 2048^2.
 // VT: element type of the basis, WT: that of the vector read (see k_multidot); the projection is fp64.  With an fp64 basis w is
 // updated in place.  With a float basis the vector is read as WT from win and leaves as OT: the LAST chunk (NORM) stores (float) w' -
 // the next basis vector - and sums the squares of the ROUNDED values, so the norm is that of the vector stored; a chunk before it

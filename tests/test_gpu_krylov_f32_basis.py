@@ -1,4 +1,4 @@
-"""The single-precision Krylov basis of the lean P1 path (csrc/pgx_api.hip: fgmres; PGX_V_F32, PGX_V_F32_GAIN, PGX_V_F32_MAX).
+"""The single-precision Krylov basis of the lean P1 path (csrc/pgx_krylov.hip: fgmres; PGX_V_F32, PGX_V_F32_GAIN, PGX_V_F32_MAX).
 
 The basis vectors are stored as float, w = J z_j stays fp64, dot products and projections are fp64 on the widened basis, and a cycle
 ends once its Arnoldi estimate has gained PGX_V_F32_GAIN over the true residual it started from (the loop head then takes the true

@@ -1,4 +1,4 @@
-"""The lean passes of the Krylov / Newton driver (csrc/pgx_api.hip: fgmres, pgx_newton_solve): Gram-Schmidt launches of up to 16 basis
+"""The lean passes of the Krylov / Newton driver (csrc/pgx_krylov.hip: fgmres; csrc/pgx_api.hip: pgx_newton_solve): Gram-Schmidt launches of up to 16 basis
 vectors (PGX_GS_WIDE), the second reduction stage and the read-back in one launch (PGX_FUSED_PUBLISH), the true residual of a restart
 cycle out of the operator kernel (PGX_FUSED_RESID), the signed right-hand side without a -F copy or a zero fill (PGX_LEAN_RHS), the
 Newton update with its two norms (PGX_FUSED_STEP).  Every one of them is an exact transformation: with a key off and on the Newton

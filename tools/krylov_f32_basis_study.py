@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Does a SINGLE-PRECISION Krylov basis cost Krylov iterations, and how many bytes does it save?  CPU twin of fgmres (csrc/pgx_api.hip)
+"""Does a SINGLE-PRECISION Krylov basis cost Krylov iterations, and how many bytes does it save?  CPU twin of fgmres (csrc/pgx_krylov.hip)
 on the lean P1 path: one full settings-B LVPP run per row, the Newton systems solved by the FGMRES of oracle/krylov_proto.py extended
 by what the library's loop has - restart 30, lazy normalisation, the selective second projection (eta = 0.01), the true residual
 b - J x in fp64 after every cycle, the attainable-accuracy exit - and preconditioned by the single-precision V(nu,nu) cycle with D as
