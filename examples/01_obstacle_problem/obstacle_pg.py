@@ -24,6 +24,10 @@ if __name__ == "__main__":
     parser.add_argument("--disk", dest="disk_h", type=float, default=0.0,
                         help="mesh size of a unit-DISK mesh (the reference's own domain, generate_mesh_gmsh.py:23) instead of "
                              "the square; general mesh -> sparse-LU preconditioner")
+    parser.add_argument("--refinements", dest="refinements", type=int, default=0,
+                        help="with --disk RES: refine that mesh this many times, new boundary vertices on the circle "
+                             "(generate_mesh_gmsh.py:26-36: disk_L); the refined mesh carries its hierarchy, and from PGX_UMG_MIN "
+                             "vertices up the degree-1 solve preconditions with the multilevel cycle instead of the sparse LU")
     parser.add_argument("--polynomial_order", "-p", dest="polynomial_order", type=int, default=1, choices=[1, 2],
                         help="Polynomial order of primal space")
     parser.add_argument("--alpha-scheme", dest="alpha_scheme", type=str, default="constant",
@@ -39,7 +43,9 @@ if __name__ == "__main__":
 
         msh = read_mesh(args.filename)  # .xdmf / gmsh .msh; order-2 triangles keep their mid-side nodes (curved cells)
     else:
-        msh = (fem.create_disk(args.disk_h) if args.disk_h > 0.0 else
+        if args.refinements and not args.disk_h > 0.0:
+            parser.error("--refinements goes with --disk RES")
+        msh = (fem.create_disk(args.disk_h, refinements=args.refinements) if args.disk_h > 0.0 else
                fem.create_rectangle(((-1.0, -1.0), (1.0, 1.0)), (args.N, args.N)))
     sol, newton_steps = solve_problem(msh, args.polynomial_order, args.maximum_number_of_outer_loop_iterations,
                                       args.alpha_scheme, args.alpha_max, args.tol_exit,

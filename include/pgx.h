@@ -70,7 +70,8 @@ typedef struct {
   const int32_t* cells;   /* [n_cells][3], vertex ids */
   /* >0 only for the right-diagonal structured triangulation with vertex v = j*(nx+1)+i and cells
    * (2q, 2q+1) = [v0,v1,v3],[v0,v2,v3] of square q = j*nx+i (dolfinx create_rectangle default).
-   * Enables the geometric multigrid preconditioner; 0 = general mesh (single-level smoother). */
+   * Enables the geometric multigrid preconditioner; 0 = general mesh: sparse LU or single-level smoother, and the
+   * multilevel cycle once pgx_set_hierarchy has attached the hierarchy of a refined mesh. */
   int32_t structured_nx;
   int32_t structured_ny;
   /* degree 2 only (NULL / 0 for degree 1): dofs per field are [vertices | one per edge]; row c lists the 3
@@ -239,6 +240,36 @@ int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, int in_form
 
 /* (pgx_mg_level_export also serves structured P2 handles: their levels are the P1 hierarchy below the P2 level, level 0 holding
  * D = T^T D_P2 T, the coarse space of the two-level cycle.  pgx_vcycle_apply keeps its P1 precondition.) */
+
+/* ---- Refined general meshes: a multigrid hierarchy given by topology alone (csrc/pgx_umg.hip) ----
+ * A mesh that came out of uniform (red) refinement has the nested P1 hierarchy; this call hands it to a degree-1 handle, which then
+ * preconditions FGMRES with the collective-smoother V-cycle on block-CSR levels, as the structured handles do on stencils.
+ *   n_transfers       number of refinements to undo (>= 1); level 0 is the handle's mesh, level t + 1 has n_coarse[t] vertices
+ *   n_coarse[t]       strictly decreasing, n_coarse[0] < n_vertices
+ *   parents[t]        [n_fine_t][2] with n_fine_0 = n_vertices, n_fine_t = n_coarse[t - 1]: (v, v) for the first n_coarse[t] rows (a
+ *                     vertex keeps its number on the coarser level), the two ends of the bisected edge for every other row
+ * The prolongation has two entries of 1/2 per row; level t + 1 stores P^T K P, P^T M P and - after every Jacobian fill - P^T D P of
+ * the unconstrained level-t values; the Dirichlet set of a level is the fine one on the inherited vertices.  Order-2 geometry needs
+ * nothing extra: the products start from whatever values level 0 holds.
+ * Call it after pgx_create / pgx_create_curved and before the first Jacobian fill (PGX_ESTATE afterwards, and on a second call).
+ * PGX_EINVAL, with a message and nothing launched or changed: a structured, sharded, LU-distributed or degree-2 handle; a parent
+ * index outside the coarse level; a transfer whose first n_coarse[t] rows are not (v, v) (or a later row that is); n_coarse not
+ * strictly decreasing.
+ * Solver selection with a hierarchy attached: pc_type 1 runs the cycle (tuning key PGX_UMG=0: the single-level smoother, for A/B),
+ * 2 the sparse LU, 0 the cycle from PGX_UMG_MIN vertices up and the LU below.  The coarsest level runs PGX_UMG_COARSE_SWEEPS (60)
+ * smoother sweeps, in one launch where it fits the LDS of one workgroup (PGX_UMG_COARSE_LDS=0: as separate launches). */
+int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32_t* n_coarse, const int32_t* const* parents);
+/* Test hooks of that hierarchy, in the style of pgx_mg_level_export / pgx_vcycle_apply (whose preconditions and behaviour they leave
+ * alone; numpy twin: tests/umg_reference.py).  Both need an attached hierarchy (PGX_UMG on), a filled Jacobian and the sparse LU not
+ * active: PGX_ESTATE otherwise, nothing launched.
+ * Level `level` (0 = the handle's own block CSR): *n vertices, *nnz entries, the CSR pattern, the stored unconstrained K, M, D values
+ * and the Dirichlet mask; every array may be NULL.  Copies only.  PGX_EINVAL: no such level. */
+int pgx_umg_level_export(pgx_handle* h, int level, int32_t* n, int32_t* nnz, int32_t* rowptr, int32_t* col, double* K, double* M, double* D,
+                         uint8_t* mask);
+/* z = ONE V(nu, nu) cycle for b, entered on `level` from a zero guess; host vectors [u | psi] of 2 n_level entries.  Level 0 runs
+ * through the preconditioner entry of FGMRES.  On a level > 0 the u part of b must be 0 on that level's Dirichlet rows, as every
+ * restricted residual is; PGX_EINVAL otherwise. */
+int pgx_umg_cycle_apply(pgx_handle* h, int level, int nu, double omega, const double* b, double* z);
 
 /* ---- Test hooks of the P2 two-level preconditioner (pgx_api.hip: pcycle_p2_patch; pgx_patch.hip): patch_nu additive vertex-star
  * sweeps | restriction to the P1 hierarchy | one P1 V-cycle | prolongation | patch_nu sweeps.  They replace nothing in the reference

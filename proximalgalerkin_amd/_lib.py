@@ -370,6 +370,10 @@ SYMBOLS = [
     ("pgx_mg_level_export", C.c_int,
      [_H, C.c_int, c_int32_p, c_int32_p, c_double_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), c_int32_p, c_int32_p]),
     ("pgx_vcycle_apply", C.c_int, [_H, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p]),
+    ("pgx_set_hierarchy", C.c_int, [_H, C.c_int32, c_int32_p, C.POINTER(c_int32_p)]),
+    ("pgx_umg_level_export", C.c_int,
+     [_H, C.c_int, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_uint8)]),
+    ("pgx_umg_cycle_apply", C.c_int, [_H, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p]),
     ("pgx_p2_cycle_info", C.c_int, [_H, c_int32_p, c_double_p]),
     ("pgx_p2_patch_export", C.c_int, [_H, c_int32_p, c_double_p]),
     ("pgx_p2_cycle_apply", C.c_int, [_H, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p]),

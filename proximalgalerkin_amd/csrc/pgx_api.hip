@@ -1047,6 +1047,10 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_FUSED_MIN")) h->fused_min = atoi(e);
   if (const char* e = pgx_tune("PGX_CGS_ETA2")) h->cgs_eta2 = atof(e);
   if (const char* e = pgx_tune("PGX_COARSE_SWEEPS")) h->coarse_sweeps = atoi(e);
+  if (const char* e = pgx_tune("PGX_UMG")) h->umg_enable = atoi(e);
+  if (const char* e = pgx_tune("PGX_UMG_MIN")) h->umg_min = atoi(e);
+  if (const char* e = pgx_tune("PGX_UMG_COARSE_SWEEPS")) h->umg_coarse_sweeps = std::max(1, atoi(e));
+  if (const char* e = pgx_tune("PGX_UMG_COARSE_LDS")) h->umg_coarse_lds = atoi(e);
   auto fail = [&](int rc) {
     g_create_error = h->err;
     pgx_destroy(h);
@@ -1559,7 +1563,15 @@ static int jacobian_dev(pgx_handle* h, const double* x, bool have_d = false) {
       if (h->lev[l].f32) pgxk_f_pack_d(h->st, h->lev[l]);
     }
   }
+  // refined general mesh: D(psi) of every coarse level from the full level-0 CSR values (K and M were coarsened by pgx_set_hierarchy);
+  // not where nothing reads it: under PGX_UMG=0, and in a Newton solve that preconditions with the sparse LU
+  for (size_t l = 1; umg_on(h) && !h->umg_idle && l < h->umg.size(); ++l) {
+    PhaseTimer t(h, 2);
+    const UmgLevel& C = h->umg[l];
+    pgxk_umg_rap(h->st, C.nnz, C.plan_lpe, C.plan_ptr, C.plan_src, h->umg[l - 1].D, C.D);
+  }
   h->jac_valid = true;
+  h->jac_ever = true;
   h->patch_fresh = false;
   h->p2st.fresh = false;
   return PGX_OK;
@@ -1727,9 +1739,49 @@ bool f32_cycle_ok(const pgx_handle* h, int l, int nu) {
   return h->lev[l].f32 && h->fused_legs && l + 1 < (int)h->lev.size() && nu >= 2 && (nu % 2 == 0 || (nu % 3 == 0 && h->fused_k3));
 }
 
+// Refined general mesh (pgx_set_hierarchy; kernels: pgx_umg.hip): the same V(nu, nu) cycle on block-CSR levels.  Per level: nu sweeps
+// of k_bspmv<2> (the first from zero) | k_bspmv<1> writes b - J x, k_umg_resid_restrict gathers P^T of it | the level below |
+// k_umg_prolong_add | nu sweeps.  The coarsest level runs umg_coarse_sweeps sweeps from zero: in one launch of one workgroup where its
+// operator and vectors fit the LDS (pgxk_umg_coarse_lds <= PGX_UMG_COARSE_LDS_MAX: about 600 vertices) and the handle's device took
+// that limit (umg_coarse_fits, settled by pgx_set_hierarchy), as k_bspmv<2> launches otherwise.
+static void vcycle_umg(pgx_handle* h, int l, const double* bu, const double* bp, double* outu, double* outp, int nu, double omega) {
+  const UmgLevel& L = h->umg[l];
+  const bool last = l + 1 == (int)h->umg.size();
+  if (last && h->umg_coarse_lds && h->umg_coarse_fits) {
+    pgxk_umg_coarse(h->st, L.n, L.nnz, L.rowptr, L.colm, L.K, L.M, L.D, h->alpha, omega, h->umg_coarse_sweeps, bu, bp, outu, outp);
+    return;
+  }
+  const int total = last ? h->umg_coarse_sweeps : 2 * nu;
+  bool toA = (total % 2) == 1;  // alternate targets so that the final sweep lands in (outu, outp)
+  const double *cu = nullptr, *cp = nullptr;
+  auto sweep = [&](int first) {
+    double* tu = toA ? outu : L.xu2;
+    double* tp = toA ? outp : L.xp2;
+    pgxk_bspmv(h->st, 2, L.n, L.rowptr, L.colm, L.K, L.M, L.D, h->alpha, cu, cp, bu, bp, omega, first | h->xcd_remap, tu, tp);
+    cu = tu;
+    cp = tp;
+    toA = !toA;
+  };
+  if (last) {
+    for (int s = 0; s < total; ++s) sweep(s == 0);
+    return;
+  }
+  for (int s = 0; s < nu; ++s) sweep(s == 0);
+  pgxk_bspmv(h->st, 1, L.n, L.rowptr, L.colm, L.K, L.M, L.D, h->alpha, cu, cp, bu, bp, 0.0, h->xcd_remap, L.ru, L.rp);
+  const UmgLevel& C = h->umg[l + 1];
+  pgxk_umg_resid_restrict(h->st, C.n, C.ch_ptr, C.ch_idx, C.mask, L.ru, L.rp, C.bu, C.bp);
+  vcycle_umg(h, l + 1, C.bu, C.bp, C.xu, C.xp, nu, omega);
+  pgxk_umg_prolong_add(h->st, L.n, C.parents, C.xu, C.xp, (double*)cu, (double*)cp);
+  for (int s = 0; s < nu; ++s) sweep(0);
+}
+
 // one V(nu,nu) cycle for J_l x = b, zero initial guess, result in (outu,outp)
 static void vcycle(pgx_handle* h, int l, const double* bu, const double* bp, double* outu, double* outp, int nu,
                    double omega) {
+  if (umg_on(h)) {
+    vcycle_umg(h, l, bu, bp, outu, outp, nu, omega);
+    return;
+  }
   GridLevel& L = h->lev[l];
   if (f32_cycle_ok(h, l, nu)) {
     vcycle_f(h, l, bu, bp, outu, outp, nu, omega);
@@ -2699,6 +2751,256 @@ extern "C" int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Hierarchy of a refined general mesh (include/pgx.h: pgx_set_hierarchy).  Host symbolic pass per transfer: the coarse pattern
+// P^T (pattern) P, per coarse entry the list of fine entries that sum into it (the Galerkin plan of k_umg_rap, items sorted by fine
+// entry index), and per coarse vertex its child list (P^T as CSR, children in ascending order: the vertex itself first).  Then K and
+// M of every coarse level, once; D follows on every Jacobian fill (jacobian_dev).
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+static int umg_upload(pgx_handle* h, T** dst, const std::vector<T>& src) {
+  DALLOC(*dst, src.size());
+  if (!src.empty()) HIPCHK(hipMemcpyAsync(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, h->st));
+  return PGX_OK;
+}
+
+extern "C" int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32_t* n_coarse, const int32_t* const* parents) {
+  NEED(h);
+  if (!h->umg.empty()) {
+    h->err = "pgx_set_hierarchy: this handle already has a hierarchy";
+    return PGX_ESTATE;
+  }
+  if (h->jac_ever) {
+    h->err = "pgx_set_hierarchy comes before the first Jacobian fill";
+    return PGX_ESTATE;
+  }
+  if (h->structured || h->dist.on || h->lu_comm || h->degree != 1) {
+    h->err = "pgx_set_hierarchy: for single degree-1 handles on general meshes (structured meshes have their grid hierarchy; sharded, "
+             "LU-distributed and degree-2 handles have none of this kind)";
+    return PGX_EINVAL;
+  }
+  if (n_transfers < 1 || !n_coarse || !parents) {
+    h->err = "pgx_set_hierarchy: at least one transfer, with its coarse size and its parents array";
+    return PGX_EINVAL;
+  }
+  if (h->nnz >= (1 << 30)) {
+    h->err = "pgx_set_hierarchy: the Galerkin plan addresses fewer than 2^30 fine entries";
+    return PGX_EINVAL;
+  }
+  {  // everything is checked before anything is built
+    int nf = h->n;
+    for (int t = 0; t < n_transfers; ++t) {
+      const int nc = n_coarse[t];
+      if (nc < 1 || nc >= nf) {
+        h->err = "pgx_set_hierarchy: n_coarse must be strictly decreasing, below n_vertices (transfer " + std::to_string(t) + ")";
+        return PGX_EINVAL;
+      }
+      const int32_t* P = parents[t];
+      if (!P) {
+        h->err = "pgx_set_hierarchy: null parents array (transfer " + std::to_string(t) + ")";
+        return PGX_EINVAL;
+      }
+      for (int v = 0; v < nf; ++v) {
+        const int p0 = P[2 * v], p1 = P[2 * v + 1];
+        if (p0 < 0 || p1 < 0 || p0 >= nc || p1 >= nc) {
+          h->err = "pgx_set_hierarchy: parent index outside the coarse level (transfer " + std::to_string(t) + ", vertex " + std::to_string(v) + ")";
+          return PGX_EINVAL;
+        }
+        if (v < nc ? (p0 != v || p1 != v) : (p0 == p1)) {
+          h->err = "pgx_set_hierarchy: the first n_coarse rows of a transfer are (v, v), the others the two ends of an edge (transfer " +
+                   std::to_string(t) + ", vertex " + std::to_string(v) + ")";
+          return PGX_EINVAL;
+        }
+      }
+      nf = nc;
+    }
+  }
+  std::vector<UmgLevel> lv(n_transfers + 1);
+  {
+    UmgLevel& L0 = lv[0];
+    L0.n = h->n;
+    L0.nnz = h->nnz;
+    L0.rowptr = h->rowptr;
+    L0.colm = h->colm;
+    L0.K = h->Kv;
+    L0.M = h->Mv;
+    L0.D = h->Dv;
+    L0.mask = h->mask;
+    L0.xu2 = h->tmp_u;
+    L0.xp2 = h->tmp_p;
+    L0.ru = h->res_u;
+    L0.rp = h->res_p;
+    L0.h_rowptr = h->h_rowptr;
+    L0.h_col = h->h_col;
+    L0.h_mask.resize(h->n);
+    HIPCHK(hipMemcpy(L0.h_mask.data(), h->mask, h->n, hipMemcpyDeviceToHost));
+  }
+  for (int t = 0; t < n_transfers; ++t) {
+    const UmgLevel& F = lv[t];
+    UmgLevel& C = lv[t + 1];
+    const int nf = F.n, nc = n_coarse[t];
+    const int32_t* P = parents[t];
+    C.n = nc;
+    // items of coarse row I: (coarse column, fine entry | s << 30), from every fine entry (i, j) with I a parent of i
+    std::vector<int64_t> rcount(nc + 1, 0);
+    auto np_of = [&](int v) { return v < nc ? 1 : 2; };
+    for (int i = 0; i < nf; ++i) {
+      int64_t items = 0;
+      for (int e = F.h_rowptr[i]; e < F.h_rowptr[i + 1]; ++e) items += np_of(F.h_col[e]);
+      for (int a = 0; a < np_of(i); ++a) rcount[P[2 * i + a] + 1] += items;
+    }
+    for (int I = 0; I < nc; ++I) rcount[I + 1] += rcount[I];
+    struct Item {
+      int32_t col, src;
+    };
+    std::vector<Item> items((size_t)rcount[nc]);
+    {
+      std::vector<int64_t> pos(rcount.begin(), rcount.end() - 1);
+      for (int i = 0; i < nf; ++i)
+        for (int a = 0; a < np_of(i); ++a) {
+          const int I = P[2 * i + a];
+          for (int e = F.h_rowptr[i]; e < F.h_rowptr[i + 1]; ++e) {
+            const int j = F.h_col[e];
+            const int32_t s = (i >= nc ? 1 : 0) + (j >= nc ? 1 : 0);
+            for (int b = 0; b < np_of(j); ++b) items[(size_t)pos[I]++] = Item{P[2 * j + b], (int32_t)((uint32_t)e | ((uint32_t)s << 30))};
+          }
+        }
+    }
+    C.h_rowptr.assign(nc + 1, 0);
+    std::vector<int32_t> plan_ptr(1, 0), plan_src;
+    plan_src.reserve(items.size());
+    for (int I = 0; I < nc; ++I) {
+      Item* const b = items.data() + rcount[I];
+      Item* const e = items.data() + rcount[I + 1];
+      std::sort(b, e, [](const Item& x, const Item& y) {
+        return x.col != y.col ? x.col < y.col : (x.src & 0x3fffffff) < (y.src & 0x3fffffff);
+      });
+      for (Item* q = b; q < e; ++q) {
+        if (q == b || q->col != (q - 1)->col) {
+          if (q != b) plan_ptr.push_back((int32_t)plan_src.size());
+          C.h_col.push_back(q->col);
+        }
+        plan_src.push_back(q->src);
+      }
+      if (b != e) plan_ptr.push_back((int32_t)plan_src.size());
+      C.h_rowptr[I + 1] = (int32_t)C.h_col.size();
+    }
+    if (plan_src.size() >= ((size_t)1 << 31)) {
+      h->err = "pgx_set_hierarchy: Galerkin plan exceeds int32";
+      return PGX_EINVAL;
+    }
+    C.nnz = (int)C.h_col.size();
+    const double plan_mean = C.nnz ? (double)plan_src.size() / C.nnz : 0.0;
+    // red refinement gives plan rows of 10.6 ... 12.1 items on average (at most 41): three items per lane, or two where rows run longer
+    C.plan_lpe = plan_mean <= 11.5 ? 4 : 8;
+    C.h_mask.assign(F.h_mask.begin(), F.h_mask.begin() + nc);  // the fine mask on the inherited vertices
+    std::vector<int32_t> colm(C.nnz), ch_ptr(nc + 1, 0), ch_idx;
+    for (int e = 0; e < C.nnz; ++e) colm[e] = (int32_t)((uint32_t)C.h_col[e] | (C.h_mask[C.h_col[e]] ? 0x80000000u : 0u));
+    for (int v = 0; v < nf; ++v)
+      for (int a = 0; a < np_of(v); ++a) ++ch_ptr[P[2 * v + a] + 1];
+    for (int I = 0; I < nc; ++I) ch_ptr[I + 1] += ch_ptr[I];
+    ch_idx.resize(ch_ptr[nc]);
+    {
+      std::vector<int32_t> pos(ch_ptr.begin(), ch_ptr.end() - 1);
+      for (int v = 0; v < nf; ++v)
+        for (int a = 0; a < np_of(v); ++a) ch_idx[pos[P[2 * v + a]]++] = v;
+    }
+    std::vector<int32_t> par(P, P + 2 * (size_t)nf);
+    int rc;
+    if ((rc = umg_upload(h, &C.rowptr, C.h_rowptr)) || (rc = umg_upload(h, &C.colm, colm)) || (rc = umg_upload(h, &C.mask, C.h_mask)) ||
+        (rc = umg_upload(h, &C.parents, par)) || (rc = umg_upload(h, &C.ch_ptr, ch_ptr)) || (rc = umg_upload(h, &C.ch_idx, ch_idx)) ||
+        (rc = umg_upload(h, &C.plan_ptr, plan_ptr)) || (rc = umg_upload(h, &C.plan_src, plan_src)))
+      return rc;
+    DALLOC(C.K, C.nnz);
+    DALLOC(C.M, C.nnz);
+    DALLOC(C.D, C.nnz);
+    double** const vecs[8] = {&C.bu, &C.bp, &C.xu, &C.xp, &C.xu2, &C.xp2, &C.ru, &C.rp};
+    for (double** v : vecs) DALLOC(*v, nc);
+    HIPCHK(hipStreamSynchronize(h->st));  // the uploads read host vectors that end with this iteration
+  }
+  for (int l = 1; l <= n_transfers; ++l) {
+    const UmgLevel& C = lv[l];
+    pgxk_umg_rap(h->st, C.nnz, C.plan_lpe, C.plan_ptr, C.plan_src, lv[l - 1].K, C.K);
+    pgxk_umg_rap(h->st, C.nnz, C.plan_lpe, C.plan_ptr, C.plan_src, lv[l - 1].M, C.M);
+  }
+  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(hipGetLastError());
+  // the coarsest level in one launch: only where this handle's device accepts the kernel's LDS limit (set per device, here)
+  h->umg_coarse_fits = pgxk_umg_coarse_prepare(lv.back().n, lv.back().nnz);
+  h->umg = std::move(lv);
+  h->jac_valid = false;
+  return PGX_OK;
+}
+
+// Test hooks of that hierarchy (include/pgx.h): copies of what a level stores, and one cycle through the functions the solver calls.
+static int umg_hook_ready(pgx_handle* h, const char* who) {
+  if (!h->jac_valid || !umg_on(h) || h->lu_active) {
+    h->err = std::string(who) + " needs a handle with an attached hierarchy (pgx_set_hierarchy, PGX_UMG on), a filled Jacobian and the sparse LU not active";
+    return PGX_ESTATE;
+  }
+  return PGX_OK;
+}
+
+extern "C" int pgx_umg_level_export(pgx_handle* h, int level, int32_t* n, int32_t* nnz, int32_t* rowptr, int32_t* col, double* K, double* M,
+                                    double* D, uint8_t* mask) {
+  NEED(h);
+  {
+    const int rc = umg_hook_ready(h, "pgx_umg_level_export");
+    if (rc) return rc;
+  }
+  if (level < 0 || level >= (int)h->umg.size()) {
+    h->err = "pgx_umg_level_export: no such level";
+    return PGX_EINVAL;
+  }
+  const UmgLevel& L = h->umg[level];
+  if (n) *n = L.n;
+  if (nnz) *nnz = L.nnz;
+  HIPCHK(hipStreamSynchronize(h->st));
+  if (rowptr) memcpy(rowptr, L.h_rowptr.data(), sizeof(int32_t) * (L.n + 1));
+  if (col) memcpy(col, L.h_col.data(), sizeof(int32_t) * L.nnz);
+  if (K) HIPCHK(hipMemcpy(K, L.K, sizeof(double) * L.nnz, hipMemcpyDeviceToHost));
+  if (M) HIPCHK(hipMemcpy(M, L.M, sizeof(double) * L.nnz, hipMemcpyDeviceToHost));
+  if (D) HIPCHK(hipMemcpy(D, L.D, sizeof(double) * L.nnz, hipMemcpyDeviceToHost));
+  if (mask) memcpy(mask, L.h_mask.data(), L.n);
+  return PGX_OK;
+}
+
+extern "C" int pgx_umg_cycle_apply(pgx_handle* h, int level, int nu, double omega, const double* b, double* z) {
+  NEED(h);
+  {
+    const int rc = umg_hook_ready(h, "pgx_umg_cycle_apply");
+    if (rc) return rc;
+  }
+  if (!b || !z || nu < 1 || level < 0 || level >= (int)h->umg.size()) {
+    h->err = "pgx_umg_cycle_apply: bad argument (an existing level, nu >= 1, b and z)";
+    return PGX_EINVAL;
+  }
+  if (level == 0) {  // as fgmres enters the preconditioner: right-hand side in h->rhs, result in h->w
+    int rc = copy_in(h, h->rhs, b);
+    if (rc) return rc;
+    if ((rc = precond(h, h->rhs, h->w, nu, omega))) return rc;
+    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipGetLastError());
+    return copy_out(h, z, h->w);
+  }
+  const UmgLevel& L = h->umg[level];
+  const size_t n = (size_t)L.n;
+  for (size_t i = 0; i < n; ++i)
+    if (L.h_mask[i] && b[i] != 0.0) {
+      h->err = "pgx_umg_cycle_apply: on a level below the finest the u part of b must be 0 on Dirichlet rows (what every restriction delivers)";
+      return PGX_EINVAL;
+    }
+  HIPCHK(hipMemcpyAsync(L.bu, b, sizeof(double) * n, hipMemcpyHostToDevice, h->st));
+  HIPCHK(hipMemcpyAsync(L.bp, b + n, sizeof(double) * n, hipMemcpyHostToDevice, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  vcycle_umg(h, level, L.bu, L.bp, L.xu, L.xp, nu, omega);
+  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(z, L.xu, sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(z + n, L.xp, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return PGX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Test hooks of the P2 two-level cycle (include/pgx.h): what the patch smoother stores, and the stages of pcycle_p2_patch one at a
 // time through the functions the cycle itself calls (p2_cycle_resid, p2_cycle_patch, pgxk_p2_restrict, pgxk_p2_prolong_add, precond).
 // ------------------------------------------------------------------------------------------------
@@ -3011,8 +3313,10 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
   // scale; the LU then stays in place for the rest of that pgx_newton_solve call.
   const bool mg_first = optv.pc_type == 0 && h->degree == 2 && h->structured && h->lev.size() > 1 && h->patch_nn && h->p2_patch &&
                         !h->dist.on && !h->lu_comm;
+  // a refined general mesh with its hierarchy attached (pgx_set_hierarchy): auto takes the multilevel cycle from umg_min vertices up
+  const bool umg_auto = umg_on(h) && h->n >= h->umg_min;
   bool use_lu = h->lu_comm || optv.pc_type == 2 ||
-                (optv.pc_type == 0 && (h->degree == 2 || !h->structured) && !h->dist.on && !mg_first);
+                (optv.pc_type == 0 && (h->degree == 2 || !h->structured) && !h->dist.on && !mg_first && !umg_auto);
   h->lu_active = false;
   if (use_lu) {
     int rcl = ensure_lu(h);
@@ -3033,9 +3337,11 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
   struct JacStale {
     pgx_handle* h;
     ~JacStale() {
-      if (h->dh_interior || h->dv_lean) h->jac_valid = false;
+      if (h->dh_interior || h->dv_lean || umg_on(h)) h->jac_valid = false;  // (the coarse D of a general-mesh hierarchy: stale too)
+      h->umg_idle = false;
     }
   } jac_stale{h};
+  h->umg_idle = use_lu;  // degree 1: use_lu does not change within the solve
   PgxRange range("pgx:newton_solve");
   int its = 0, lin = 0, rsn = 0;
   double fnorm = 0, fnorm0 = 0, ttol = 0;

@@ -37,6 +37,21 @@ struct Dist {
   double *sb = nullptr, *wc = nullptr;  // local scatter buffer (2n), owned-compact scratch (2*own_cnt)
 };
 
+// One level of the hierarchy of a refined general mesh (pgx_set_hierarchy; kernels: pgx_umg.hip).  Level 0 aliases the handle's own
+// block CSR and level-0 scratch; a level l > 0 owns its operator, its vectors and the transfer from level l - 1 onto it.
+struct UmgLevel {
+  int n = 0, nnz = 0;
+  int32_t *rowptr = nullptr, *colm = nullptr;  // colm as k_bspmv reads it: column | Dirichlet flag << 31
+  double *K = nullptr, *M = nullptr, *D = nullptr;  // unconstrained values; levels > 0: P^T (.) P of the level above
+  uint8_t* mask = nullptr;
+  // transfer from level l - 1 (n_f vertices): parents [n_f][2]; child lists = P^T as CSR; Galerkin plan per entry of this level
+  int32_t *parents = nullptr, *ch_ptr = nullptr, *ch_idx = nullptr, *plan_ptr = nullptr, *plan_src = nullptr;
+  int plan_lpe = 4;       // lanes per coarse entry in k_umg_rap, from the mean plan-row length
+  double *bu = nullptr, *bp = nullptr, *xu = nullptr, *xp = nullptr, *xu2 = nullptr, *xp2 = nullptr, *ru = nullptr, *rp = nullptr;
+  std::vector<int32_t> h_rowptr, h_col;
+  std::vector<uint8_t> h_mask;
+};
+
 struct pgx_handle {
   int device = 0;
   Dist dist;
@@ -160,6 +175,18 @@ struct pgx_handle {
   // orthogonality per step by 100 eps, re-orthogonalises 11 of 266 and leaves every Krylov count unchanged: 448 -> 416 ms per solve
   double cgs_eta2 = 1e-4;
   TailArgs tail{};
+  // hierarchy of a refined general mesh (pgx_set_hierarchy): empty = none, the handle runs as it did before that call existed
+  std::vector<UmgLevel> umg;
+  int umg_enable = 1;          // PGX_UMG=0: the single-level smoother although a hierarchy is attached (A/B)
+  int umg_min = 20000;         // PGX_UMG_MIN: pc_type auto takes the cycle from this many vertices up, the sparse LU below.  20 381 vertices
+                               // (disk_3) is the smallest size measured, and the cycle is already the faster of the two there; the crossover
+                               // lies below and is not located (with what the figures include)
+  int umg_coarse_sweeps = 60;  // PGX_UMG_COARSE_SWEEPS
+  int umg_coarse_lds = 1;      // PGX_UMG_COARSE_LDS=0: the coarsest level as repeated k_bspmv<2> launches although it fits one workgroup's LDS
+  bool umg_coarse_fits = false;  // the coarsest level fits k_umg_coarse and this handle's device took its LDS limit (pgx_set_hierarchy)
+  bool umg_idle = false;       // the current Newton solve preconditions with the sparse LU: nobody reads the coarse D, its fills skip it
+                               // (the solve ends with jac_valid dropped, so the hooks never see that state)
+  bool jac_ever = false;      // a Jacobian was filled at least once (pgx_set_hierarchy comes before that)
   // sparse direct preconditioner (pc_type lu): nested-dissection multifrontal LU of the mixed Newton matrix (pgx_nd.hip)
   pgx_nd* lu = nullptr;
   // pgx_create_lu_dist: this handle is one of `size` REPLICAS (whole mesh, whole iterate on every rank) whose sparse LU is
@@ -203,7 +230,10 @@ struct pgx_handle {
   std::vector<void*> allocs;
 };
 
-#define HIPCHK(call)                                                                            \
+// the multilevel cycle of a refined general mesh is what this handle's preconditioner entry runs
+static inline bool umg_on(const pgx_handle* h) { return h->umg.size() > 1 && h->umg_enable; }
+
+#define HIPCHK(call)                                                                           \
   do {                                                                                          \
     hipError_t e_ = (call);                                                                     \
     if (e_ != hipSuccess) {                                                                     \

@@ -136,6 +136,19 @@ void pgxk_fill_rows(hipStream_t st, int mode, int n, size_t lds_bytes, const int
 void pgxk_bspmv(hipStream_t st, int mode, int n, const int32_t* rowptr, const int32_t* colm, const double* K,
                 const double* M, const double* D, double alpha, const double* xu, const double* xp, const double* bu,
                 const double* bp, double omega, int first, double* yu, double* yp);
+// ---- pgx_umg.hip: transfers, Galerkin products and the coarsest level of the hierarchy of a refined general mesh ----
+// dst[e] = sum over the plan row of coarse entry e of 2^-s src[i] (one item = i | s << 30); lpe = lanes per coarse entry (4 or 8)
+void pgxk_umg_rap(hipStream_t st, int nnz_c, int lpe, const int32_t* plan_ptr, const int32_t* plan_src, const double* src, double* dst);
+// (bu, bp) = P^T (ru, rp) over the child list of every coarse vertex; the u part is 0 on the coarse level's Dirichlet rows
+void pgxk_umg_resid_restrict(hipStream_t st, int n_c, const int32_t* ch_ptr, const int32_t* ch_idx, const uint8_t* mask_c, const double* ru,
+                             const double* rp, double* bu, double* bp);
+void pgxk_umg_prolong_add(hipStream_t st, int n_f, const int32_t* parents, const double* cu, const double* cp, double* xu, double* xp);
+// `sweeps` collective-Jacobi sweeps from zero on a level whose block CSR and vectors fit into the LDS of one workgroup
+#define PGX_UMG_COARSE_LDS_MAX (156 * 1024)
+size_t pgxk_umg_coarse_lds(int n, int nnz);
+bool pgxk_umg_coarse_prepare(int n, int nnz);  // raises the kernel's LDS limit on the current device; false: sweep with k_bspmv instead
+void pgxk_umg_coarse(hipStream_t st, int n, int nnz, const int32_t* rowptr, const int32_t* colm, const double* K, const double* M,
+                     const double* D, double alpha, double omega, int sweeps, const double* bu, const double* bp, double* xu, double* xp);
 void pgxk_observables(hipStream_t st, int nc, int n, const int32_t* cells, const double* coords, const double* x,
                       const double* xk, double alpha, double f, QuadTab q, double* partials, int nblocks, double* out6,
                       int raw = 0, const double* geo = nullptr);

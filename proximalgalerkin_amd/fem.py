@@ -80,6 +80,9 @@ class Mesh:
             raise ValueError("expected coords (nv,2) and triangle cells (nc,3)")
         self.structured = tuple(int(s) for s in structured) if structured else None
         self.partition = partition  # StripPartition: this Mesh is one rank's strip (owned + ghost vertex rows)
+        # refine() leaves the nested P1 hierarchy here: `parents` arrays (nv_fine, 2) int32, ordered fine -> coarse, one per refinement
+        # ((v, v) for a vertex the coarser mesh has too, the two ends of the bisected edge for a midpoint).  None: no hierarchy
+        self.hierarchy = None
         # ORDER-2 GEOMETRY (round 5): `midside[e]` = the geometry's mid-side node on edge e (numbering of edges()), as a gmsh mesh of
         # element order 2 carries it (the reference's own meshes: generate_mesh_gmsh.py:30-33, lvpp/mesh_generation.py:88,158).  The
         # cell map is then x(xi) = sum_a X_a N2_a(xi) over the 3 vertices + 3 mid-side nodes (local edge i opposite local vertex i).
@@ -101,7 +104,11 @@ class Mesh:
 
     def flattened(self):
         """The same mesh with affine cells (mid-side nodes dropped): what a degree-1 run uses (include/pgx.h: pgx_create_curved)."""
-        return Mesh(self.geometry, self.cells, structured=self.structured, partition=self.partition) if self.curved else self
+        if not self.curved:
+            return self
+        flat = Mesh(self.geometry, self.cells, structured=self.structured, partition=self.partition)
+        flat.hierarchy = self.hierarchy
+        return flat
 
     def geometry_at(self, points):
         """Cell map at reference points (nq, 2): physical points xq (nc, nq, 2) and the per-point geometry the curved kernels read,
@@ -285,10 +292,51 @@ def _create_rectangle_crossed(points, n):
     return Mesh(coords, cells, structured=None)
 
 
-def create_disk(h: float, radius: float = 1.0):
+def refine(mesh: Mesh, snap_radius: float | None = None) -> Mesh:
+    """Red refinement of a general triangle mesh.  Old vertices keep their numbers; edge e of mesh.edges() gets the new vertex
+    nv + e at its midpoint; cell c becomes the cells 4 c + (0, 1, 2, 3): the corner triangles at its local vertices 0, 1, 2, then the
+    middle one, all with the parent's orientation.  snap_radius: the new vertices of exterior edges are scaled onto the circle of that
+    radius about the origin (what gmsh's refine() does on the OCC disk of generate_mesh_gmsh.py:23-29); only those move.
+
+    The result is a general mesh (`structured` is None) and carries `hierarchy`: the list, fine -> coarse, of one `parents` array
+    (nv_fine, 2) int32 per refinement - (v, v) for an inherited vertex, the two edge ends for a midpoint.  Refining a refined mesh
+    extends the list.  A curved (`midside`) mesh is refined as its flattened mesh."""
+    if mesh.partition is not None:
+        raise NotImplementedError("refine works on a whole mesh, not on one rank's strip")
+    mesh = mesh.flattened()
+    nv = mesh.num_vertices
+    edges, cell_edges = mesh.edges()
+    x = mesh.geometry
+    mid = 0.5 * (x[edges[:, 0]] + x[edges[:, 1]])
+    if snap_radius is not None:
+        ext = np.bincount(cell_edges.ravel(), minlength=len(edges)) == 1
+        mid[ext] *= (float(snap_radius) / np.hypot(mid[ext, 0], mid[ext, 1]))[:, None]
+    c = mesh.cells.astype(np.int64)
+    m = nv + cell_edges.astype(np.int64)  # m[:, i] = midpoint of the edge opposite local vertex i
+    cells = np.empty((4 * len(c), 3), dtype=np.int32)
+    cells[0::4] = np.stack([c[:, 0], m[:, 2], m[:, 1]], axis=1)
+    cells[1::4] = np.stack([m[:, 2], c[:, 1], m[:, 0]], axis=1)
+    cells[2::4] = np.stack([m[:, 1], m[:, 0], c[:, 2]], axis=1)
+    cells[3::4] = np.stack([m[:, 0], m[:, 1], m[:, 2]], axis=1)
+    fine = Mesh(np.concatenate([x, mid]), cells)
+    own = np.arange(nv, dtype=np.int32)
+    parents = np.ascontiguousarray(np.concatenate([np.stack([own, own], axis=1), edges.astype(np.int32)]))
+    fine.hierarchy = [parents] + list(mesh.hierarchy or [])
+    return fine
+
+
+def create_disk(h: float, radius: float = 1.0, refinements: int = 0):
     """Delaunay triangulation of a disk with mesh size ~h: concentric rings, staggered - the reference's example-01 domain is
     a gmsh disk of radius 1 (examples/01_obstacle_problem/generate_mesh_gmsh.py:23); gmsh itself is not available here.
-    A general (unstructured) mesh: the solver preconditions with the sparse LU."""
+    A general (unstructured) mesh.  refinements = 0: that mesh alone, without a hierarchy - the solver preconditions with the sparse
+    LU (or, asked for "pgx_mg", the single-level smoother).  refinements = k: the mesh at size h refined k times by refine() with its
+    new boundary vertices on the circle, as generate_mesh_gmsh.py:26-36 builds disk_k; it carries `hierarchy`, and a degree-1 solve on
+    it can precondition with the multilevel cycle (include/pgx.h: pgx_set_hierarchy)."""
+    if refinements:
+        msh = create_disk(h, radius)
+        for _ in range(int(refinements)):
+            msh = refine(msh, snap_radius=radius)
+        return msh
     from scipy.spatial import Delaunay
 
     pts = [(0.0, 0.0)]

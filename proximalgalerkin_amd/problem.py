@@ -224,6 +224,11 @@ class NonlinearProblem:
             _lib.check(lib, None, rc, "pgx_create_sharded")
         self._h = h
         self.ndofs = V.num_dofs
+        # a refined general mesh (fem.refine) hands its nested P1 hierarchy to a degree-1 handle: FGMRES can then precondition with the
+        # multilevel cycle (include/pgx.h: pgx_set_hierarchy).  Meshes without one - files, structured grids - are solved as before
+        hier = getattr(mesh, "hierarchy", None)
+        if hier and V.degree == 1 and part is None and lu_comm is None and not mesh.structured:
+            self.set_hierarchy(hier)
         F.sol.x._binding = (self, "state")
         F.sol_k.x._binding = (self, "prev")
         F.sol.x._dev_valid = F.sol_k.x._dev_valid = False
@@ -409,6 +414,54 @@ class NonlinearProblem:
             raise ValueError(f"b must hold [u | psi] of level {level}: {2 * (nx.value + 1) * (ny.value + 1)} entries")
         self._check_code(self._lib.pgx_vcycle_apply(self._h, int(level), int(nu), float(omega), int(in_form), int(out_form), float(scale),
                                                     _lib.dptr(b), _lib.dptr(z)), "pgx_vcycle_apply")
+        return z
+
+    def set_hierarchy(self, parents, n_coarse=None):
+        """Attach the hierarchy of a refined general mesh (include/pgx.h: pgx_set_hierarchy): `parents` as Mesh.hierarchy holds them,
+        fine -> coarse; n_coarse[t] defaults to the number of (v, v) rows of parents[t]."""
+        par = [np.ascontiguousarray(p, dtype=np.int32) for p in parents]
+        if n_coarse is None:
+            n_coarse = [int(np.count_nonzero(p[:, 0] == p[:, 1])) for p in par]
+        nc = np.ascontiguousarray(n_coarse, dtype=np.int32)
+        ptrs = (_lib.c_int32_p * max(len(par), 1))(*[_lib.iptr(p) for p in par])
+        self._check_code(self._lib.pgx_set_hierarchy(self._h, len(par), _lib.iptr(nc), ptrs), "pgx_set_hierarchy")
+        self._umg_levels = len(par) + 1
+
+    def umg_level_export(self, level):
+        """What level `level` of the general-mesh hierarchy stores after the last assemble_jacobian (include/pgx.h:
+        pgx_umg_level_export; a test hook): dict(n, rowptr, col, K, M, D, mask)."""
+        n, nnz = C.c_int32(0), C.c_int32(0)
+        lib = self._lib
+        self._check_code(lib.pgx_umg_level_export(self._h, int(level), C.byref(n), C.byref(nnz), None, None, None, None, None, None),
+                         "pgx_umg_level_export")
+        rowptr, col = np.empty(n.value + 1, dtype=np.int32), np.empty(nnz.value, dtype=np.int32)
+        K, M, D = np.empty(nnz.value), np.empty(nnz.value), np.empty(nnz.value)
+        mask = np.empty(n.value, dtype=np.uint8)
+        self._check_code(lib.pgx_umg_level_export(self._h, int(level), None, None, _lib.iptr(rowptr), _lib.iptr(col), _lib.dptr(K),
+                                                  _lib.dptr(M), _lib.dptr(D), mask.ctypes.data_as(C.POINTER(C.c_uint8))),
+                         "pgx_umg_level_export")
+        return dict(n=n.value, rowptr=rowptr, col=col, K=K, M=M, D=D, mask=mask.astype(bool))
+
+    def umg_levels(self):
+        """Number of levels pgx_umg_level_export serves: the transfers handed to set_hierarchy, plus one.  Raises as that hook does
+        where it would not serve level 0 (no hierarchy, no filled Jacobian)."""
+        n = C.c_int32(0)
+        self._check_code(self._lib.pgx_umg_level_export(self._h, 0, C.byref(n), None, None, None, None, None, None, None),
+                         "pgx_umg_level_export")
+        return self._umg_levels
+
+    def umg_cycle_apply(self, level, b, nu=6, omega=0.75):
+        """One V(nu, nu) cycle of the general-mesh hierarchy entered on `level` from a zero guess, b and the result [u | psi] of that
+        level (include/pgx.h: pgx_umg_cycle_apply; a test hook)."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        z = np.empty_like(b)
+        n = C.c_int32(0)
+        self._check_code(self._lib.pgx_umg_level_export(self._h, int(level), C.byref(n), None, None, None, None, None, None, None),
+                         "pgx_umg_cycle_apply")
+        if b.shape != (2 * n.value,):
+            raise ValueError(f"b must hold [u | psi] of level {level}: {2 * n.value} entries")
+        self._check_code(self._lib.pgx_umg_cycle_apply(self._h, int(level), int(nu), float(omega), _lib.dptr(b), _lib.dptr(z)),
+                         "pgx_umg_cycle_apply")
         return z
 
     P2_PATCH_FORMS = ("double", "float", "float-sym", "bf16-sym")

@@ -1,0 +1,226 @@
+#!/usr/bin/env python3
+"""Example 01 on the reference's disk family with the multilevel cycle of refined general meshes.
+
+    python3 tools/disk_mg_check.py [--levels 3 4 5 6] [--modes mg single lu] [--trace-level 5] [--out profiles/umg_disk_scaling.json]
+
+For every L: create_disk(0.1, refinements=L) - the construction of generate_mesh_gmsh.py's disk_L - solved with settings B
+(double_exponential, alpha_max 100, tol 1e-4) under "pgx_mg" (the cycle), "pgx_mg" with PGX_UMG=0 (the single-level smoother) and
+"pgx_lu".  Recorded: vertices per level, Newton counts, Krylov iterations per Newton step (read from the solver's monitor lines in a
+second, untimed run), and per LVPP solve the host clock around pgx_newton_solve (which ends in a synchronisation).  What the times
+include: the first solve of a handle carries its one-time work - under "pgx_lu" the symbolic analysis of the factorisation - so the
+mean over all solves, the first solve and the mean without it are recorded separately; the cycle's one-time host pass
+(pgx_set_hierarchy) runs when the handle is created and is recorded as set_hierarchy_seconds.  Each mode is run once untimed on
+the first mesh before anything is timed (code objects loaded); one timed run per entry, so no spread.  --trace-level L runs the "mg" solve of that L once more under rocprofv3 --kernel-trace
+and adds the per-launch times of the k_umg_* kernels per grid size, with the achieved bandwidth of k_umg_rap and
+k_umg_resid_restrict on the finest transfer against their algorithmic bytes.  A mode that fails (the single-level smoother runs into
+the Krylov iteration cap on the large meshes) is recorded with its message.  Needs an MI355X."""
+import argparse
+import contextlib
+import csv
+import ctypes
+import glob
+import json
+import os
+import pathlib
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+BASE = {"ksp_type": "preonly", "ksp_error_if_not_converged": True, "snes_error_if_not_converged": True, "snes_linesearch_type": "none",
+        "snes_rtol": 1e-6, "snes_max_it": 100}
+MODES = {"mg": ("pgx_mg", {}), "single": ("pgx_mg", {"PGX_UMG": 0}), "lu": ("pgx_lu", {})}
+
+
+@contextlib.contextmanager
+def c_stdout_to(path):
+    """The library prints its monitor lines with printf: redirect file descriptor 1."""
+    sys.stdout.flush()
+    libc = ctypes.CDLL(None)
+    saved = os.dup(1)
+    with open(path, "w") as f:
+        os.dup2(f.fileno(), 1)
+        try:
+            yield
+        finally:
+            libc.fflush(None)
+            os.dup2(saved, 1)
+            os.close(saved)
+
+
+def solve(msh, mode, monitor_file=None):
+    from proximalgalerkin_amd import _lib
+    from proximalgalerkin_amd.obstacle import run_outer_loop, setup_problem
+
+    from proximalgalerkin_amd.problem import NonlinearProblem
+
+    pc, keys = MODES[mode]
+    for k, v in keys.items():
+        _lib.tuning_set(k, v)
+    hier_s, set_hierarchy = [], NonlinearProblem.set_hierarchy
+
+    def timed_set_hierarchy(self, *args, **kw):  # pgx_set_hierarchy returns after a synchronisation
+        t0 = time.perf_counter()
+        r = set_hierarchy(self, *args, **kw)
+        hier_s.append(time.perf_counter() - t0)
+        return r
+
+    NonlinearProblem.set_hierarchy = timed_set_hierarchy
+    try:
+        opts = dict(BASE, pc_type=pc)
+        if monitor_file:
+            opts["snes_monitor"] = None
+        problem, sol, sol_k, alpha = setup_problem(msh, 1, petsc_options=opts)
+        try:
+            lin, ms, inner = [], [], problem.solve
+
+            def counted():
+                t0 = time.perf_counter()
+                r = inner()  # pgx_newton_solve returns after a synchronisation of its stream
+                ms.append(1e3 * (time.perf_counter() - t0))
+                lin.append(problem.solver.getLinearSolveIterations())
+                return r
+
+            problem.solve = counted
+            with (c_stdout_to(monitor_file) if monitor_file else contextlib.nullcontext()):
+                hist = run_outer_loop(problem, sol, sol_k, alpha, 500, "double_exponential", 1e2, 1e-4)
+            u = sol.x.array[: msh.num_vertices].copy()
+        finally:
+            problem.close()
+    finally:
+        NonlinearProblem.set_hierarchy = set_hierarchy
+        for k in keys:
+            _lib.tuning_set(k, None)
+    rec = dict(newton=[int(v) for v in hist["Newton steps"]], krylov_per_lvpp_solve=lin, ms_per_lvpp_solve=[round(v, 3) for v in ms],
+               ms_per_lvpp_solve_mean=round(float(np.mean(ms)), 3), ms_first_solve=round(ms[0], 3),
+               ms_per_lvpp_solve_mean_without_first=round(float(np.mean(ms[1:])), 3) if len(ms) > 1 else None,
+               ms_total=round(float(np.sum(ms)), 3), set_hierarchy_seconds=round(hier_s[0], 4) if hier_s else None)
+    if monitor_file:
+        steps = [int(m) for m in re.findall(r"KSP its (\d+)", pathlib.Path(monitor_file).read_text())]
+        rec = dict(krylov_per_newton_step=steps, krylov_per_newton_step_range=[min(steps), max(steps)] if steps else None)
+    return rec, u
+
+
+def transfer_bytes(parents, rowptr, col):
+    """Algorithmic bytes of one k_umg_rap launch and one k_umg_resid_restrict launch on the transfer `parents` from the level with
+    the pattern (rowptr, col): every operand once."""
+    nf = len(parents)
+    nc = int(np.count_nonzero(parents[:, 0] == parents[:, 1]))
+    npar = np.where(np.arange(nf) < nc, 1, 2)
+    rows = np.repeat(np.arange(nf), np.diff(rowptr))
+    plan = int(np.sum(npar[rows] * npar[col]))
+    import scipy.sparse as sp
+
+    P = sp.csr_matrix((np.ones(2 * nf), (np.repeat(np.arange(nf), 2), parents.ravel())), shape=(nf, nc))
+    A = sp.csr_matrix((np.ones(len(col)), col, rowptr), shape=(nf, nf))
+    nnz_c = int((P.T @ A @ P).nnz)
+    rap = 4 * plan + 4 * (nnz_c + 1) + 8 * len(col) + 8 * nnz_c
+    children = nc + 2 * (nf - nc)
+    restrict = 16 * nf + 4 * children + 4 * (nc + 1) + nc + 16 * nc
+    return dict(n_fine=nf, n_coarse=nc, nnz_fine=int(len(col)), nnz_coarse=nnz_c, plan_items=plan, plan_row_mean=round(plan / nnz_c, 2),
+                rap_bytes=rap, resid_restrict_bytes=restrict)
+
+
+def kernel_times(trace_dir):
+    acc = {}
+    for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+        for r in csv.DictReader(open(f, newline="")):
+            name = r["Kernel_Name"]
+            if "k_umg_" not in name and "k_bspmv" not in name:
+                continue
+            short = re.sub(r"^void ", "", name.split("(")[0])
+            acc.setdefault((short, int(r.get("Grid_Size", r.get("Grid_Size_X", 0)))), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    return [dict(kernel=k, grid=g, launches=len(v), us_mean=round(float(np.mean(v)), 2), us_min=round(float(np.min(v)), 2),
+                 us_max=round(float(np.max(v)), 2)) for (k, g), v in sorted(acc.items(), key=lambda kv: (kv[0][0], -kv[0][1]))]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--levels", type=int, nargs="+", default=[3, 4, 5, 6])
+    ap.add_argument("--modes", nargs="+", default=["mg", "single", "lu"], choices=sorted(MODES))
+    ap.add_argument("--h", type=float, default=0.1)
+    ap.add_argument("--lu-max-level", type=int, default=5, help="largest L solved under pgx_lu")
+    ap.add_argument("--single-max-level", type=int, default=5, help="largest L solved with the single-level smoother")
+    ap.add_argument("--trace-level", type=int, default=None)
+    ap.add_argument("--trace-timeout", type=float, default=300.0, help="seconds the traced child process may take")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "umg_disk_scaling.json"))
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    from proximalgalerkin_amd import fem
+
+    if a.child:  # under rocprofv3: one "mg" run of one mesh, nothing else
+        solve(fem.create_disk(a.h, refinements=a.levels[0]), "mg")
+        return
+    out = dict(h=a.h, settings="B: double_exponential, alpha_max 100, tol 1e-4; V(6,6), omega 0.75, 60 coarse sweeps", levels={})
+    warm = set()
+    for L in a.levels:
+        t0 = time.perf_counter()
+        msh = fem.create_disk(a.h, refinements=L)
+        sizes = [len(p) for p in msh.hierarchy] + [int(np.count_nonzero(msh.hierarchy[-1][:, 0] == msh.hierarchy[-1][:, 1]))]
+        rec = dict(vertices=sizes, mesh_seconds=round(time.perf_counter() - t0, 2))
+        print(f"L={L}: vertices {sizes}", flush=True)
+        u_ref = {}
+        for mode in a.modes:
+            if (mode == "lu" and L > a.lu_max_level) or (mode == "single" and L > a.single_max_level):
+                rec[mode] = "not run at this size"
+                continue
+            try:
+                if mode not in warm:  # once per process and mode: code objects, first-use allocations
+                    solve(msh, mode)
+                    warm.add(mode)
+                t0 = time.perf_counter()
+                r, u = solve(msh, mode)
+                r["setup_and_solve_seconds"] = round(time.perf_counter() - t0, 2)
+                u_ref[mode] = u
+                if mode != "lu":
+                    with tempfile.TemporaryDirectory() as tmp:
+                        r.update(solve(msh, mode, os.path.join(tmp, "monitor.txt"))[0])
+                rec[mode] = r
+                print(f"  {mode}: Newton {r['newton']}, Krylov per Newton step {r.get('krylov_per_newton_step_range')}, "
+                      f"ms per LVPP solve: mean {r['ms_per_lvpp_solve_mean']}, first {r['ms_first_solve']}, without the first "
+                      f"{r['ms_per_lvpp_solve_mean_without_first']}; set_hierarchy {r['set_hierarchy_seconds']} s", flush=True)
+            except Exception as e:  # e.g. the single-level smoother at the Krylov iteration cap
+                rec[mode] = f"failed: {type(e).__name__}: {e}"
+                print(f"  {mode}: {rec[mode]}", flush=True)
+        if "lu" in u_ref:
+            for mode in ("mg", "single"):
+                if mode in u_ref:
+                    rec[f"rel_l2_u_{mode}_vs_lu"] = float(np.linalg.norm(u_ref[mode] - u_ref["lu"]) / np.linalg.norm(u_ref["lu"]))
+        out["levels"][str(L)] = rec
+        pathlib.Path(a.out).write_text(json.dumps(out, indent=1) + "\n")  # after every size: a later failure keeps what was measured
+    if a.trace_level is not None:
+        L = a.trace_level
+        msh = fem.create_disk(a.h, refinements=L)
+        from proximalgalerkin_amd.obstacle import setup_problem
+
+        problem = setup_problem(msh, 1)[0]
+        rowptr, col = problem.export_blocks(with_D=False)[:2]
+        problem.close()
+        tb = transfer_bytes(msh.hierarchy[0], rowptr, col)
+        with tempfile.TemporaryDirectory() as tmp:
+            child = subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "t", "--", sys.executable, __file__,
+                                    "--child", "--levels", str(L), "--h", str(a.h)], timeout=a.trace_timeout, stdout=subprocess.DEVNULL,
+                                   stderr=subprocess.PIPE, text=True)  # a child that hangs ends here, and the script with it
+            if child.returncode:
+                sys.exit(f"the traced run ended with status {child.returncode}:\n{child.stderr[-2000:]}")
+            kt = kernel_times(tmp)
+        for k in kt:
+            # the launches of the finest transfer, by their grid (threads or blocks; k_umg_rap runs 1, 4 or 8 lanes per coarse entry)
+            blocks = {"k_umg_rap": [-(-tb["nnz_coarse"] * lanes // 256) for lanes in (1, 4, 8)], "k_umg_resid_restrict": [-(-tb["n_coarse"] // 256)]}
+            for name, by in (("k_umg_rap", tb["rap_bytes"]), ("k_umg_resid_restrict", tb["resid_restrict_bytes"])):
+                if k["kernel"].startswith(name) and any(k["grid"] in (b * 256, b) for b in blocks[name]):
+                    k["algorithmic_bytes"] = by
+                    k["gb_per_s_mean"] = round(by / k["us_mean"] / 1e3, 1)
+        out["kernel_trace"] = dict(level=L, finest_transfer=tb, kernels=kt)
+        pathlib.Path(a.out).write_text(json.dumps(out, indent=1) + "\n")
+        for k in kt:
+            print(k, flush=True)
+
+
+if __name__ == "__main__":
+    main()
