@@ -27,7 +27,8 @@ if __name__ == "__main__":
     parser.add_argument("--refinements", dest="refinements", type=int, default=0,
                         help="with --disk RES: refine that mesh this many times, new boundary vertices on the circle "
                              "(generate_mesh_gmsh.py:26-36: disk_L); the refined mesh carries its hierarchy, and from PGX_UMG_MIN "
-                             "vertices up the degree-1 solve preconditions with the multilevel cycle instead of the sparse LU")
+                             "vertices up the degree-1 solve preconditions with the multilevel cycle instead of the sparse LU; with -p 2 the "
+                             "patch cycle over that hierarchy comes first from PGX_UMG_MIN_P2 vertices up")
     parser.add_argument("--polynomial_order", "-p", dest="polynomial_order", type=int, default=1, choices=[1, 2],
                         help="Polynomial order of primal space")
     parser.add_argument("--alpha-scheme", dest="alpha_scheme", type=str, default="constant",

@@ -242,8 +242,11 @@ int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, int in_form
  * D = T^T D_P2 T, the coarse space of the two-level cycle.  pgx_vcycle_apply keeps its P1 precondition.) */
 
 /* ---- Refined general meshes: a multigrid hierarchy given by topology alone (csrc/pgx_umg.hip) ----
- * A mesh that came out of uniform (red) refinement has the nested P1 hierarchy; this call hands it to a degree-1 handle, which then
- * preconditions FGMRES with the collective-smoother V-cycle on block-CSR levels, as the structured handles do on stencils.
+ * A mesh that came out of uniform (red) refinement has the nested P1 hierarchy; this call hands it to a single handle of degree 1 or 2.  A
+ * degree-1 handle then preconditions FGMRES with the collective-smoother V-cycle on block-CSR levels, as the structured handles do on
+ * stencils.  Under a degree-2 handle the hierarchy is the coarse solve of the two-level patch cycle (below): `parents` still speak of
+ * vertices, level 0 is the handle's P1 block CSR with D = T^T D_P2 T (refreshed by every Jacobian fill), and level-l vectors have
+ * 2 n_l vertex entries.
  *   n_transfers       number of refinements to undo (>= 1); level 0 is the handle's mesh, level t + 1 has n_coarse[t] vertices
  *   n_coarse[t]       strictly decreasing, n_coarse[0] < n_vertices
  *   parents[t]        [n_fine_t][2] with n_fine_0 = n_vertices, n_fine_t = n_coarse[t - 1]: (v, v) for the first n_coarse[t] rows (a
@@ -252,11 +255,13 @@ int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, int in_form
  * the unconstrained level-t values; the Dirichlet set of a level is the fine one on the inherited vertices.  Order-2 geometry needs
  * nothing extra: the products start from whatever values level 0 holds.
  * Call it after pgx_create / pgx_create_curved and before the first Jacobian fill (PGX_ESTATE afterwards, and on a second call).
- * PGX_EINVAL, with a message and nothing launched or changed: a structured, sharded, LU-distributed or degree-2 handle; a parent
+ * PGX_EINVAL, with a message and nothing launched or changed: a structured, sharded or LU-distributed handle; a parent
  * index outside the coarse level; a transfer whose first n_coarse[t] rows are not (v, v) (or a later row that is); n_coarse not
  * strictly decreasing.
  * Solver selection with a hierarchy attached: pc_type 1 runs the cycle (tuning key PGX_UMG=0: the single-level smoother, for A/B),
- * 2 the sparse LU, 0 the cycle from PGX_UMG_MIN vertices up and the LU below.  The coarsest level runs PGX_UMG_COARSE_SWEEPS (60)
+ * 2 the sparse LU, 0 the cycle from PGX_UMG_MIN vertices up and the LU below.  Degree 2: 1 the two-level patch cycle over this hierarchy
+ * (it needs the patch smoother: largest vertex degree <= 15), 2 the LU, 0 the cycle first from PGX_UMG_MIN_P2 vertices up, with the
+ * sparse-LU rescue of structured P2 after PGX_P2_FALLBACK_ITS iterations, and the LU below.  The coarsest level runs PGX_UMG_COARSE_SWEEPS (60)
  * smoother sweeps, in one launch where it fits the LDS of one workgroup (PGX_UMG_COARSE_LDS=0: as separate launches). */
 int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32_t* n_coarse, const int32_t* const* parents);
 /* Test hooks of that hierarchy, in the style of pgx_mg_level_export / pgx_vcycle_apply (whose preconditions and behaviour they leave
@@ -267,7 +272,8 @@ int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32_t* n_coars
 int pgx_umg_level_export(pgx_handle* h, int level, int32_t* n, int32_t* nnz, int32_t* rowptr, int32_t* col, double* K, double* M, double* D,
                          uint8_t* mask);
 /* z = ONE V(nu, nu) cycle for b, entered on `level` from a zero guess; host vectors [u | psi] of 2 n_level entries.  Level 0 runs
- * through the preconditioner entry of FGMRES.  On a level > 0 the u part of b must be 0 on that level's Dirichlet rows, as every
+ * through the preconditioner entry of FGMRES (degree 2, whose entry is the two-level cycle: through the level-0 cycle that cycle calls;
+ * b and z have 2 n_vertices entries).  On a level > 0 the u part of b must be 0 on that level's Dirichlet rows, as every
  * restricted residual is; PGX_EINVAL otherwise. */
 int pgx_umg_cycle_apply(pgx_handle* h, int level, int nu, double omega, const double* b, double* z);
 
@@ -275,7 +281,7 @@ int pgx_umg_cycle_apply(pgx_handle* h, int level, int nu, double omega, const do
  * sweeps | restriction to the P1 hierarchy | one P1 V-cycle | prolongation | patch_nu sweeps.  They replace nothing in the reference
  * (which factorises the P2 Newton matrix as well, obstacle_pg.py:68-70,129-131): they let tests compare what the device stores and
  * computes, stage by stage, with a numpy statement of the same algebra (tests/p2_cycle_reference.py).  Preconditions of all three: a
- * single-GPU P2 handle with a patch smoother (vertex degree <= 7, PGX_P2_PATCH on), a filled Jacobian, not sharded, the sparse LU
+ * single-GPU P2 handle with a patch smoother (vertex degree <= 15; <= 7 under PGX_P2_PATCH_WIDE=0; PGX_P2_PATCH on), a filled Jacobian, not sharded, the sparse LU
  * not active; anything else is PGX_ESTATE with a message, and nothing is launched.  None changes how a solve runs: they make the
  * calls the cycle makes, on the cycle's own buffers. */
 /* out = { [0] slots per patch NN (7 or 8; a patch matrix has 2 NN rows),
@@ -286,7 +292,8 @@ int pgx_umg_cycle_apply(pgx_handle* h, int level, int nu, double omega, const do
  *         [5] Newton solves since create in which the patch cycle stagnated (p2_fallback_its Krylov iterations without convergence)
  *             and the sparse LU took over,
  *         [6] 1: kernel [4] = 1 reads K and M through its dictionary (values on a grid of 2^-40 of the largest entry),
- *         [7] 1: the handle has the P1 grid hierarchy the whole cycle needs (stage 0 below) };  *patch_omega (may be NULL): damping
+ *         [7] 1: the handle has the P1 hierarchy the whole cycle needs (stage 0 below): the grid hierarchy of a structured mesh, or an
+ *             attached one (pgx_set_hierarchy) };  *patch_omega (may be NULL): damping
  * of the sweeps.  Brings the patch data up to date for the current Jacobian, as the first cycle of a solve does. */
 int pgx_p2_cycle_info(pgx_handle* h, int32_t out[8], double* patch_omega);
 /* Host copies of the patch data of the current Jacobian (either may be NULL); nv patches, patch p = vertex p:
@@ -295,6 +302,16 @@ int pgx_p2_cycle_info(pgx_handle* h, int32_t out[8], double* patch_omega);
  *                         rows / columns = (u slots, psi slots).  Symmetric packing: the chunks at or left of a row's diagonal block
  *                         as stored, the rest as the kernel mirrors them; bf16 words shifted up; float and double cast. */
 int pgx_p2_patch_export(pgx_handle* h, int32_t* pdof, double* Ainv);
+/* Wide stars.  A star of vertex degree 8 ... 15 does not fit the 16 lanes of a narrow patch.  On a mesh whose largest degree lies in
+ * that range NN is 8, the vertices of degree >= 8 form the wide set - their rows of pdof above are all -1 and their narrow inverses the
+ * identity - and a second pair of kernels (32 lanes per star, 16 slots, inverses in full rows, float or, where the narrow form is
+ * double, double) serves them inside the same sweep.  Largest degree > 15, or PGX_P2_PATCH_WIDE=0 with degree > 7: no patch smoother.
+ *   *nw                  number of wide stars (0 on most meshes; then nothing else is written)
+ *   verts [nw]           their vertices, ascending
+ *   wdof  [nw][16]       slot 0 the vertex, then its edge dofs, -1 = unused slot
+ *   Ainv  [nw][32][32]   the stored inverses as k_patch_apply_wide reads them, rows / columns = (16 u slots, 16 psi slots)
+ * Every pointer may be NULL; preconditions as pgx_p2_patch_export. */
+int pgx_p2_wide_export(pgx_handle* h, int32_t* nw, int32_t* verts, int32_t* wdof, double* Ainv);
 /* One stage of the cycle on host vectors ([u | psi] of the P2 space, 2 nd entries, unless stated), through the launches of the cycle:
  *   stage 1  one sweep, z = x0 + sweep(b - J x0): the cycle's residual kernel, then the patch sweep; x0 == NULL: the first sweep of
  *            a cycle (x = 0, r = b, no residual launch)
@@ -302,7 +319,7 @@ int pgx_p2_patch_export(pgx_handle* h, int32_t* pdof, double* Ainv);
  *   stage 3  z [2 nv] = T^T b, the restriction to the P1 space (u rows of Dirichlet vertices 0)
  *   stage 4  z = x0 + T b with b [2 nv] (x0 == NULL: 0), the prolongation
  *   stage 0  the whole preconditioner, entered exactly as FGMRES enters it, with a V(nu, nu) cycle of damping omega below; needs
- *            the grid hierarchy (PGX_ESTATE otherwise); x0 must be NULL
+ *            the grid hierarchy or an attached one (PGX_ESTATE otherwise); x0 must be NULL
  * nu and omega are read by stage 0 only (the sweeps use patch_nu and patch_omega of the handle). */
 int pgx_p2_cycle_apply(pgx_handle* h, int stage, int nu, double omega, const double* b, const double* x0, double* z);
 

@@ -376,6 +376,7 @@ SYMBOLS = [
     ("pgx_umg_cycle_apply", C.c_int, [_H, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p]),
     ("pgx_p2_cycle_info", C.c_int, [_H, c_int32_p, c_double_p]),
     ("pgx_p2_patch_export", C.c_int, [_H, c_int32_p, c_double_p]),
+    ("pgx_p2_wide_export", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p, c_double_p]),
     ("pgx_p2_cycle_apply", C.c_int, [_H, C.c_int, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p]),
     ("pgx_spmv_select", C.c_int, [_H, C.c_int, C.POINTER(C.c_int)]),
     ("pgx_p2_stencil_info", C.c_int, [_H, C.POINTER(C.c_int32)]),

@@ -403,10 +403,22 @@ static int build_plan_p2(pgx_handle* h, const pgx_mesh* m, const std::vector<uin
     int maxdeg = 0;
     for (int v = 0; v < nv; ++v) maxdeg = std::max(maxdeg, eptr[v + 1] - eptr[v]);
     h->patch_nn = maxdeg + 1 <= 7 ? 7 : (maxdeg + 1 <= 8 ? 8 : 0);
+    // degree 8 ... 15 somewhere: those vertices form the wide set (32 lanes per star), every other star keeps its 16 lanes
+    const bool wide = !h->patch_nn && maxdeg + 1 <= PGX_PATCH_WIDE_NN && h->patch_wide && !h->dist.on;
+    if (wide) h->patch_nn = 8;
     if (h->patch_nn) {
       const int NN = h->patch_nn;
       h->patch_dof_host.assign((size_t)nv * NN, -1);
       for (int v = 0; v < nv; ++v) {
+        const int deg = eptr[v + 1] - eptr[v];
+        if (deg + 1 > NN) {  // its row of the narrow table stays all -1: an identity patch there, nothing stored by its lanes
+          h->wide_v_host.push_back(v);
+          h->wide_dof_host.resize(h->wide_dof_host.size() + PGX_PATCH_WIDE_NN, -1);
+          int32_t* d = h->wide_dof_host.data() + h->wide_dof_host.size() - PGX_PATCH_WIDE_NN;
+          d[0] = v;
+          for (int k = 0; k < deg; ++k) d[1 + k] = elist[eptr[v] + k];
+          continue;
+        }
         int32_t* d = h->patch_dof_host.data() + (size_t)v * NN;
         d[0] = v;
         for (int k = eptr[v]; k < eptr[v + 1]; ++k) d[1 + k - eptr[v]] = elist[k];
@@ -1049,6 +1061,8 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_COARSE_SWEEPS")) h->coarse_sweeps = atoi(e);
   if (const char* e = pgx_tune("PGX_UMG")) h->umg_enable = atoi(e);
   if (const char* e = pgx_tune("PGX_UMG_MIN")) h->umg_min = atoi(e);
+  if (const char* e = pgx_tune("PGX_UMG_MIN_P2")) h->umg_min_p2 = atoi(e);
+  if (const char* e = pgx_tune("PGX_P2_PATCH_WIDE")) h->patch_wide = atoi(e);
   if (const char* e = pgx_tune("PGX_UMG_COARSE_SWEEPS")) h->umg_coarse_sweeps = std::max(1, atoi(e));
   if (const char* e = pgx_tune("PGX_UMG_COARSE_LDS")) h->umg_coarse_lds = atoi(e);
   auto fail = [&](int rc) {
@@ -2077,9 +2091,29 @@ static int ensure_patches(pgx_handle* h) {
     HIPCHK(hipMemcpy(h->pdof, h->patch_dof_host.data(), sizeof(int32_t) * h->patch_dof_host.size(), hipMemcpyHostToDevice));
     std::vector<int32_t>().swap(h->patch_dof_host);
     pgxk_patch_positions(h->st, nv, NN, h->pdof, h->s_rowptr, h->s_colm, h->ppos);
+    if (!h->wide_v_host.empty()) {  // wide stars: their own tables and full-row inverses, float unless the narrow form is double
+      // (filled in place: whatever an early return leaves behind is the handle's - dalloc lists every allocation in h->allocs -, and
+      // nw, which switches the wide launches on, is set last)
+      PgxWidePatches& W = h->wide;
+      const int nw = (int)h->wide_v_host.size();
+      W.f32 = h->patch_f32 ? 1 : 0;
+      DALLOC(W.verts, nw);
+      DALLOC(W.dof, (size_t)nw * PGX_PATCH_WIDE_NN);
+      DALLOC(W.pos, (size_t)nw * PGX_PATCH_WIDE_NN * PGX_PATCH_WIDE_NN);
+      {
+        uint8_t* q = nullptr;
+        DALLOC(q, pgxk_patch_wide_inverse_bytes(nw, W.f32));
+        W.inv = q;
+      }
+      HIPCHK(hipMemcpy(W.verts, h->wide_v_host.data(), sizeof(int32_t) * h->wide_v_host.size(), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(W.dof, h->wide_dof_host.data(), sizeof(int32_t) * h->wide_dof_host.size(), hipMemcpyHostToDevice));
+      pgxk_patch_positions(h->st, nw, PGX_PATCH_WIDE_NN, W.dof, h->s_rowptr, h->s_colm, W.pos);
+      W.nw = nw;
+    }
   }
   if (!h->patch_fresh) {
     pgxk_patch_invert(h->st, nv, NN, h->pdof, h->ppos, h->s_K, h->s_M, h->s_D, h->mask, h->alpha, h->pinv, h->patch_f32, h->patch_sym);
+    pgxk_patch_invert_wide(h->st, h->wide, h->s_K, h->s_M, h->s_D, h->mask, h->alpha);
     if (h->s_Df) pgxk_to_float(h->st, (size_t)h->s_nnz, h->s_D, h->s_Df);
     h->patch_fresh = true;
   }
@@ -2108,7 +2142,8 @@ static void p2_cycle_resid(pgx_handle* h, int kind, const double* xu, const doub
 // x += patch_omega * (averaged patch solves of r)
 static void p2_cycle_patch(pgx_handle* h, const double* ru, const double* rp, double* xu, double* xp) {
   const int nd = h->nd, nv = h->n;
-  pgxk_patch_sweep(h->st, nv, h->patch_nn, nv, nd, h->pdof, h->edge_ends, h->pinv, h->patch_f32, h->patch_sym, ru, rp, h->patch_omega, xu, xp, h->p2_su, h->p2_sp);
+  pgxk_patch_sweep(h->st, nv, h->patch_nn, nv, nd, h->pdof, h->edge_ends, h->pinv, h->patch_f32, h->patch_sym, ru, rp, h->patch_omega, xu, xp, h->p2_su, h->p2_sp,
+                   h->wide.nw ? &h->wide : nullptr);
 }
 
 // Two-level cycle with the vertex-star patch smoother (round 3): patch_nu additive sweeps | P1 hierarchy on T^T (b - J x) |
@@ -2379,7 +2414,7 @@ int precond(pgx_handle* h, const double* b, double* z, int nu, double omega) {
     const int rc = ensure_patches(h);
     if (rc) return rc;
     pcycle_p2_patch(h, b, b + h->nd, z, z + h->nd, nu, omega);
-  } else if (h->degree == 2)  // round-1 cycle: point-collective Jacobi on the P2 level (meshes with vertex degree > 7, A/B)
+  } else if (h->degree == 2)  // round-1 cycle: point-collective Jacobi on the P2 level (meshes with vertex degree > 15, A/B)
     pcycle_p2(h, b, b + h->nd, z, z + h->nd, nu, omega);
   else
     vcycle(h, 0, b, b + h->n, z, z + h->n, nu, omega);
@@ -2483,10 +2518,7 @@ extern "C" int pgx_smoother_bench(pgx_handle* h, int reps, double* avg_ms, doubl
     const int nd = h->nd, nv = h->n, NN = h->patch_nn, P = 2 * NN;
     pgxk_set(h->st, 2 * (size_t)nd, 1.0, h->rhs);
     HIPCHK(hipMemsetAsync(h->w, 0, sizeof(double) * 2 * nd, h->st));
-    auto sweep = [&]() {
-      pgxk_patch_sweep(h->st, nv, NN, nv, nd, h->pdof, h->edge_ends, h->pinv, h->patch_f32, h->patch_sym, h->rhs, h->rhs + nd, h->patch_omega,
-                       h->w, h->w + nd, h->p2_su, h->p2_sp);
-    };
+    auto sweep = [&]() { p2_cycle_patch(h, h->rhs, h->rhs + nd, h->w, h->w + nd); };
     for (int k = 0; k < 3; ++k) sweep();
     HIPCHK(hipEventRecord(h->e0, h->st));
     for (int k = 0; k < reps; ++k) sweep();
@@ -2773,9 +2805,9 @@ extern "C" int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32
     h->err = "pgx_set_hierarchy comes before the first Jacobian fill";
     return PGX_ESTATE;
   }
-  if (h->structured || h->dist.on || h->lu_comm || h->degree != 1) {
-    h->err = "pgx_set_hierarchy: for single degree-1 handles on general meshes (structured meshes have their grid hierarchy; sharded, "
-             "LU-distributed and degree-2 handles have none of this kind)";
+  if (h->structured || h->dist.on || h->lu_comm) {
+    h->err = "pgx_set_hierarchy: for single handles on general meshes (structured meshes have their grid hierarchy; sharded and "
+             "LU-distributed handles have none of this kind)";
     return PGX_EINVAL;
   }
   if (n_transfers < 1 || !n_coarse || !parents) {
@@ -2815,7 +2847,7 @@ extern "C" int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32
     }
   }
   std::vector<UmgLevel> lv(n_transfers + 1);
-  {
+  {  // level 0 = the handle's P1 block CSR on its vertices; under a degree-2 handle Dv is T^T D_P2 T, refreshed by every fill
     UmgLevel& L0 = lv[0];
     L0.n = h->n;
     L0.nnz = h->nnz;
@@ -2974,6 +3006,18 @@ extern "C" int pgx_umg_cycle_apply(pgx_handle* h, int level, int nu, double omeg
     h->err = "pgx_umg_cycle_apply: bad argument (an existing level, nu >= 1, b and z)";
     return PGX_EINVAL;
   }
+  if (level == 0 && h->degree == 2) {  // fgmres enters the two-level cycle there: level 0 as pcycle_p2_patch enters it
+    const size_t n = (size_t)h->n;
+    HIPCHK(hipMemcpyAsync(h->c1_bu, b, sizeof(double) * n, hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipMemcpyAsync(h->c1_bp, b + n, sizeof(double) * n, hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    vcycle_umg(h, 0, h->c1_bu, h->c1_bp, h->c1_xu, h->c1_xp, nu, omega);
+    HIPCHK(hipStreamSynchronize(h->st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(z, h->c1_xu, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(z + n, h->c1_xp, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return PGX_OK;
+  }
   if (level == 0) {  // as fgmres enters the preconditioner: right-hand side in h->rhs, result in h->w
     int rc = copy_in(h, h->rhs, b);
     if (rc) return rc;
@@ -3006,7 +3050,7 @@ extern "C" int pgx_umg_cycle_apply(pgx_handle* h, int level, int nu, double omeg
 // ------------------------------------------------------------------------------------------------
 static int p2_hook_ready(pgx_handle* h, const char* who) {
   if (h->degree != 2 || !h->patch_nn || !h->p2_patch || !h->jac_valid || h->dist.on || h->lu_comm || h->lu_active) {
-    h->err = std::string(who) + " needs a single-GPU P2 handle with the vertex-star patch smoother (vertex degree <= 7, PGX_P2_PATCH on), "
+    h->err = std::string(who) + " needs a single-GPU P2 handle with the vertex-star patch smoother (vertex degree <= 15, PGX_P2_PATCH on), "
                                 "a filled Jacobian and the sparse LU not active";
     return PGX_ESTATE;
   }
@@ -3027,7 +3071,7 @@ extern "C" int pgx_p2_cycle_info(pgx_handle* h, int32_t out[8], double* patch_om
   out[4] = kind;
   out[5] = h->p2_fallbacks;
   out[6] = (kind == 1 && h->s_code && h->s_tab) ? 1 : 0;
-  out[7] = (h->structured && h->lev.size() > 1) ? 1 : 0;
+  out[7] = ((h->structured && h->lev.size() > 1) || umg_on(h)) ? 1 : 0;
   if (patch_omega) *patch_omega = h->patch_omega;
   HIPCHK(hipStreamSynchronize(h->st));
   return PGX_OK;
@@ -3050,6 +3094,26 @@ extern "C" int pgx_p2_patch_export(pgx_handle* h, int32_t* pdof, double* Ainv) {
   return PGX_OK;
 }
 
+extern "C" int pgx_p2_wide_export(pgx_handle* h, int32_t* nw, int32_t* verts, int32_t* wdof, double* Ainv) {
+  NEED(h);
+  int rc = p2_hook_ready(h, "pgx_p2_wide_export");
+  if (rc) return rc;
+  if ((rc = ensure_patches(h))) return rc;
+  HIPCHK(hipStreamSynchronize(h->st));
+  HIPCHK(hipGetLastError());
+  const PgxWidePatches& W = h->wide;
+  if (nw) *nw = W.nw;
+  if (!W.nw) return PGX_OK;
+  if (verts) memcpy(verts, h->wide_v_host.data(), sizeof(int32_t) * W.nw);
+  if (wdof) memcpy(wdof, h->wide_dof_host.data(), sizeof(int32_t) * (size_t)W.nw * PGX_PATCH_WIDE_NN);
+  if (Ainv) {
+    std::vector<uint8_t> raw(pgxk_patch_wide_inverse_bytes(W.nw, W.f32));
+    HIPCHK(hipMemcpy(raw.data(), W.inv, raw.size(), hipMemcpyDeviceToHost));
+    pgxk_patch_wide_decode(W.nw, W.f32, raw.data(), Ainv);
+  }
+  return PGX_OK;
+}
+
 extern "C" int pgx_p2_cycle_apply(pgx_handle* h, int stage, int nu, double omega, const double* b, const double* x0, double* z) {
   NEED(h);
   int rc = p2_hook_ready(h, "pgx_p2_cycle_apply");
@@ -3058,8 +3122,8 @@ extern "C" int pgx_p2_cycle_apply(pgx_handle* h, int stage, int nu, double omega
     h->err = "pgx_p2_cycle_apply: bad argument (stages 0 .. 4; stage 2 needs x0, stage 0 takes none and nu >= 1)";
     return PGX_EINVAL;
   }
-  if (stage == 0 && !(h->structured && h->lev.size() > 1)) {
-    h->err = "pgx_p2_cycle_apply: the whole cycle needs the P1 grid hierarchy of a structured mesh";
+  if (stage == 0 && !(h->structured && h->lev.size() > 1) && !umg_on(h)) {
+    h->err = "pgx_p2_cycle_apply: the whole cycle needs the P1 grid hierarchy of a structured mesh or an attached one (pgx_set_hierarchy)";
     return PGX_ESTATE;
   }
   if ((rc = ensure_patches(h))) return rc;
@@ -3311,10 +3375,11 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
   // iterations per Newton step at every size, a fifth of a factorisation's time) and the sparse LU only for a Newton solve in
   // which that cycle stagnates - the overshot iterates of settings B's large alpha jumps, where exp(psi) is rough on the mesh
   // scale; the LU then stays in place for the rest of that pgx_newton_solve call.
-  const bool mg_first = optv.pc_type == 0 && h->degree == 2 && h->structured && h->lev.size() > 1 && h->patch_nn && h->p2_patch &&
-                        !h->dist.on && !h->lu_comm;
+  // P2 on a refined general mesh with its hierarchy attached: the same, from umg_min_p2 vertices up (the coarse solve is vcycle_umg)
+  const bool p2_hier = h->structured ? h->lev.size() > 1 : (umg_on(h) && h->n >= h->umg_min_p2);
+  const bool mg_first = optv.pc_type == 0 && h->degree == 2 && p2_hier && h->patch_nn && h->p2_patch && !h->dist.on && !h->lu_comm;
   // a refined general mesh with its hierarchy attached (pgx_set_hierarchy): auto takes the multilevel cycle from umg_min vertices up
-  const bool umg_auto = umg_on(h) && h->n >= h->umg_min;
+  const bool umg_auto = h->degree == 1 && umg_on(h) && h->n >= h->umg_min;
   bool use_lu = h->lu_comm || optv.pc_type == 2 ||
                 (optv.pc_type == 0 && (h->degree == 2 || !h->structured) && !h->dist.on && !mg_first && !umg_auto);
   h->lu_active = false;
@@ -3341,7 +3406,7 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
       h->umg_idle = false;
     }
   } jac_stale{h};
-  h->umg_idle = use_lu;  // degree 1: use_lu does not change within the solve
+  h->umg_idle = use_lu;  // set again where a degree-2 solve switches to the LU (the rescue below): nothing reads the coarse D after it
   PgxRange range("pgx:newton_solve");
   int its = 0, lin = 0, rsn = 0;
   double fnorm = 0, fnorm0 = 0, ttol = 0;
@@ -3406,6 +3471,7 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
         if ((rc = lu_factor(h))) return rc;
         h->lu_active = true;
         use_lu = true;
+        h->umg_idle = true;
         ++h->p2_fallbacks;
         rc = fgmres(h, h->rhs, h->dx, opts, &kits, &relres, fnorm);
         if (rc) return rc;

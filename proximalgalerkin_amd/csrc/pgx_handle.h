@@ -97,7 +97,7 @@ struct pgx_handle {
   double *p2_xu = nullptr, *p2_xp = nullptr, *p2_ru = nullptr, *p2_rp = nullptr;
   double* p2_stash = nullptr;  // [16 * nc] element residual vectors of the P2 assembly (deterministic scatter, pgx_p2.hip)
   double *c1_bu = nullptr, *c1_bp = nullptr, *c1_xu = nullptr, *c1_xp = nullptr;
-  // vertex-star patch smoother of the P2 level (pgx_patch.hip): NN = slots per patch (0: vertex degree > 7, smoother unavailable)
+  // vertex-star patch smoother of the P2 level (pgx_patch.hip): NN = slots per patch (0: vertex degree > 15, smoother unavailable; 8 ... 15: see `wide`)
   int patch_nn = 0, p2_patch = 1, patch_nu = 2;
   int p2_fallback_its = 60, p2_fallbacks = 0;  // patch cycle -> sparse LU after this many Krylov iterations without convergence
   double patch_omega = 0.8;
@@ -122,6 +122,11 @@ struct pgx_handle {
   int p2_resid_f32 = 1;
   int patch_sym = 1;     // float inverses in symmetric packing (pgx_patch.hip: 512 instead of 896 B per patch); PGX_P2_PATCH_SYM=0: full rows
   double *p2_su = nullptr, *p2_sp = nullptr;
+  // wide stars: the vertices of degree 8 ... 15 of a mesh whose other stars fit the 16-lane kernels (patch_nn = 8; their rows of the
+  // narrow table are all -1).  PGX_P2_PATCH_WIDE=0: no wide set, such a mesh has no patch smoother (patch_nn = 0), as before (A/B)
+  int patch_wide = 1;
+  PgxWidePatches wide;
+  std::vector<int32_t> wide_v_host, wide_dof_host;
   // state
   double *x = nullptr, *xk = nullptr, *F = nullptr, *dx = nullptr, *xw = nullptr, *rhs = nullptr;
   // Krylov workspace
@@ -181,6 +186,9 @@ struct pgx_handle {
   int umg_min = 20000;         // PGX_UMG_MIN: pc_type auto takes the cycle from this many vertices up, the sparse LU below.  20 381 vertices
                                // (disk_3) is the smallest size measured, and the cycle is already the faster of the two there; the crossover
                                // lies below and is not located (with what the figures include)
+  int umg_min_p2 = 20000;      // PGX_UMG_MIN_P2: the same for a degree-2 handle (the patch cycle over this hierarchy first, the sparse LU as
+                               // its rescue).  Handle creation plus all solves of a settings-B run: 0.18 against 0.44 s at 20 381 vertices,
+                               // the smallest size measured, 0.39 / 1.24 s at 81 017, 1.32 / 4.29 s at 323 057 (profiles/p2_umg_disk_scaling.json)
   int umg_coarse_sweeps = 60;  // PGX_UMG_COARSE_SWEEPS
   int umg_coarse_lds = 1;      // PGX_UMG_COARSE_LDS=0: the coarsest level as repeated k_bspmv<2> launches although it fits one workgroup's LDS
   bool umg_coarse_fits = false;  // the coarsest level fits k_umg_coarse and this handle's device took its LDS limit (pgx_set_hierarchy)

@@ -297,9 +297,21 @@ void pgxk_patch_positions(hipStream_t st, int np, int NN, const int32_t* pdof, c
                           int32_t* ppos);
 void pgxk_patch_invert(hipStream_t st, int np, int NN, const int32_t* pdof, const int32_t* ppos, const double* K, const double* M,
                        const double* D, const uint8_t* mask, double alpha, void* pinv, int f32, int sym);
+// wide stars (vertex degree 8 ... 15; pgx_patch.hip): nw patches of PGX_PATCH_WIDE_NN slots - their vertices, dof table [nw][16],
+// positions [nw][16][16] and inverses in full rows [nw][8][32][4], float (f32) or double
+#define PGX_PATCH_WIDE_NN 16
+struct PgxWidePatches {
+  int nw = 0, f32 = 1;
+  int32_t *verts = nullptr, *dof = nullptr, *pos = nullptr;
+  void* inv = nullptr;
+};
 void pgxk_patch_sweep(hipStream_t st, int np, int NN, int nv, int nd, const int32_t* pdof, const int32_t* edge_ends,
                       const void* pinv, int f32, int sym, const double* ru, const double* rp, double omega, double* xu, double* xp,
-                      double* su, double* sp);
+                      double* su, double* sp, const PgxWidePatches* wide = nullptr);
+size_t pgxk_patch_wide_inverse_bytes(int nw, int f32);
+void pgxk_patch_invert_wide(hipStream_t st, const PgxWidePatches& W, const double* K, const double* M, const double* D,
+                            const uint8_t* mask, double alpha);
+void pgxk_patch_wide_decode(int nw, int f32, const void* raw, double* out);  // [nw][32][32] as k_patch_apply_wide reads them
 size_t pgxk_patch_inverse_bytes(int np, int NN, int f32, int sym);  // sym: symmetric packing (float form only)
 // host decode of a copy of pinv into full [np][2 NN][2 NN] matrices, as k_patch_apply reads them (test hook pgx_p2_patch_export)
 void pgxk_patch_decode(int np, int NN, int f32, int sym, const void* raw, double* out);

@@ -18,6 +18,10 @@
 // Mapping: a group of 16 lanes owns one patch, lane l its row l (four patches per 64-wide wavefront); rows meet through
 // width-16 shuffles.  The kernels are streaming kernels over pinv (HBM-bound): 512 B per patch and sweep (packed float; 896 B full
 // float, 1792 B in double).
+//
+// Stars of degree 8 ... 15 (a handful on an ordinary unstructured mesh) do not fit 16 lanes: they form the WIDE set with tables and
+// full-row inverses of their own and 32 lanes per star (k_patch_invert_wide, k_patch_apply_wide, below the narrow kernels); their
+// rows of pdof are all -1, so the narrow kernels invert an identity for them and store nothing in a sweep.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -272,7 +276,166 @@ __global__ void __launch_bounds__(256) k_patch_edges(int ne, int nv, double omeg
   xp[nv + e] += omega * 0.5 * ((double)b.x + (double)b.y);
 }
 
+// ---- wide stars: vertices of degree 8 ... 15 ----
+// A mesh with a few such vertices (a crossed rectangle, a coarse gmsh disk) keeps the 16-lane kernels above for every other star;
+// the wide ones - a handful - go through 32 lanes per patch, two patches per wavefront: NNW = 16 slots, P = 32 rows, lane l holds
+// row l (u slots 0..15, then psi slots).  The same unpivoted Gauss-Jordan in the same order with the same reciprocal; pivot rows and
+// right-hand sides travel by width-32 shuffles.  Inverses in full rows [patch][8][32][4], float or double: no packing, their bytes
+// do not matter.  Register budget: the row (64 VGPRs of doubles) and one pivot-row entry at a time; one wavefront per block.
+constexpr int WGRP = 32, NNW = PGX_PATCH_WIDE_NN, PW = 2 * NNW, PQW = PW / 4;
+
+// Step K of the in-place Gauss-Jordan on the 32 rows a group of lanes holds, and the steps after it.  (A template recursion, not a
+// loop: 32 steps of 32 shuffles are beyond what the compiler unrolls on request, and a rolled loop would index the row in scratch.)
+template <int K>
+__device__ __forceinline__ void patch_wide_eliminate(double (&a)[PW], int l) {
+  if constexpr (K < PW) {
+    const double pk = __shfl(a[K], K, WGRP);
+    double piv = __builtin_amdgcn_rcp(pk);  // as k_patch_invert: v_rcp_f64 + two Newton steps
+    piv = fma(fma(-pk, piv, 1.0), piv, piv);
+    piv = fma(fma(-pk, piv, 1.0), piv, piv);
+    const double f = a[K];
+    const bool own = l == K;
+#pragma unroll
+    for (int j = 0; j < PW; ++j) {
+      const double prj = __shfl(a[j], K, WGRP);  // entry j of the pivot row, which this step has not updated yet
+      if (own)
+        a[j] = (j == K) ? piv : prj * piv;
+      else
+        a[j] = (j == K) ? -f * piv : a[j] - f * (prj * piv);
+    }
+    patch_wide_eliminate<K + 1>(a, l);
+  }
+}
+
+template <typename PT>
+__global__ void __launch_bounds__(64) k_patch_invert_wide(int nw, const int32_t* __restrict__ wdof, const int32_t* __restrict__ wpos,
+                                                          const double* __restrict__ K, const double* __restrict__ M,
+                                                          const double* __restrict__ D, const uint8_t* __restrict__ mask, double alpha,
+                                                          PT* __restrict__ winv) {
+  const int p = (int)blockIdx.x * 2 + ((int)threadIdx.x >> 5);
+  const int l = threadIdx.x & (WGRP - 1);
+  const bool live = p < nw;
+  const int pp = live ? p : nw - 1;  // the idle half of the last wavefront repeats the last patch (its shuffles run) and does not store
+  const int32_t* d = wdof + (size_t)pp * NNW;
+  int dof[NNW];
+  bool bc[NNW];
+#pragma unroll
+  for (int j = 0; j < NNW; ++j) {
+    dof[j] = d[j];
+    bc[j] = dof[j] >= 0 && mask[dof[j]];
+  }
+  double a[PW];
+#pragma unroll
+  for (int j = 0; j < PW; ++j) a[j] = 0.0;
+  {
+    const int i = l & (NNW - 1);
+    const bool urow = l < NNW;
+    bool ident = false;
+#pragma unroll
+    for (int j = 0; j < NNW; ++j)
+      if (j == i) ident = dof[j] < 0 || (urow && bc[j]);
+    if (ident) {
+#pragma unroll
+      for (int j = 0; j < PW; ++j)
+        if (j == l) a[j] = 1.0;  // identity row (unused slot / Dirichlet dof of u)
+    } else {
+      const int32_t* pos = wpos + ((size_t)pp * NNW + i) * NNW;
+#pragma unroll
+      for (int j = 0; j < NNW; ++j) {
+        const int k = pos[j];
+        if (k < 0 || dof[j] < 0) continue;
+        if (urow) {
+          a[j] = bc[j] ? 0.0 : alpha * K[k];
+          a[NNW + j] = M[k];
+        } else {
+          a[j] = bc[j] ? 0.0 : M[k];
+          a[NNW + j] = -D[k];
+        }
+      }
+    }
+  }
+  patch_wide_eliminate<0>(a, l);
+  if (live) {
+    typedef PT v4 __attribute__((ext_vector_type(4)));
+    PT* out = winv + (size_t)p * PQW * PW * 4 + (size_t)l * 4;
+#pragma unroll
+    for (int q = 0; q < PQW; ++q)
+      *(v4*)(out + (size_t)q * PW * 4) = (v4){(PT)a[4 * q], (PT)a[4 * q + 1], (PT)a[4 * q + 2], (PT)a[4 * q + 3]};
+  }
+}
+
+// The wide stars' share of a sweep, between k_patch_apply (whose table rows of these vertices are all -1: it stores nothing for them)
+// and k_patch_edges: x += omega y on the vertex dof, edge contributions into the same stash slots 2 e + side.
+template <typename PT>
+__global__ void __launch_bounds__(64) k_patch_apply_wide(int nw, int nv, const int32_t* __restrict__ wide_v,
+                                                         const int32_t* __restrict__ wdof, const int32_t* __restrict__ edge_ends,
+                                                         const PT* __restrict__ winv, const double* __restrict__ ru,
+                                                         const double* __restrict__ rp, double omega, double* __restrict__ xu,
+                                                         double* __restrict__ xp, float* __restrict__ su, float* __restrict__ sp) {
+  const int p = (int)blockIdx.x * 2 + ((int)threadIdx.x >> 5);
+  const int l = threadIdx.x & (WGRP - 1);
+  const bool live = p < nw;
+  const int pp = live ? p : nw - 1;
+  const int i = l & (NNW - 1);
+  const int dof = wdof[(size_t)pp * NNW + i];
+  double r = 0.0;
+  if (dof >= 0) r = (l < NNW) ? ru[dof] : rp[dof];
+  typedef PT v4 __attribute__((ext_vector_type(4)));
+  const PT* in = winv + (size_t)pp * PQW * PW * 4 + (size_t)l * 4;
+  double row[PW];
+#pragma unroll
+  for (int q = 0; q < PQW; ++q) {
+    const v4 v = *(const v4*)(in + (size_t)q * PW * 4);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) row[4 * q + t] = (double)v[t];
+  }
+  double y0 = 0.0, y1 = 0.0;
+#pragma unroll
+  for (int j = 0; j < PW; ++j) {
+    const double rj = __shfl(r, j, WGRP);
+    if (j & 1)
+      y1 = fma(row[j], rj, y1);
+    else
+      y0 = fma(row[j], rj, y0);
+  }
+  const double y = y0 + y1;
+  if (!live || dof < 0) return;
+  const int v = wide_v[pp];
+  if (i == 0) {
+    if (l < NNW)
+      xu[v] += omega * y;
+    else
+      xp[v] += omega * y;
+  } else {
+    const int e = dof - nv;
+    const int side = (edge_ends[2 * e] == v) ? 0 : 1;
+    (l < NNW ? su : sp)[2 * (size_t)e + side] = (float)y;
+  }
+}
+
 }  // namespace
+
+size_t pgxk_patch_wide_inverse_bytes(int nw, int f32) { return (size_t)nw * PW * PW * (f32 ? sizeof(float) : sizeof(double)); }
+
+void pgxk_patch_invert_wide(hipStream_t st, const PgxWidePatches& W, const double* K, const double* M, const double* D,
+                            const uint8_t* mask, double alpha) {
+  if (W.nw <= 0) return;
+  const unsigned blocks = (unsigned)((W.nw + 1) / 2);
+  if (W.f32)
+    hipLaunchKernelGGL((k_patch_invert_wide<float>), dim3(blocks), dim3(64), 0, st, W.nw, W.dof, W.pos, K, M, D, mask, alpha, (float*)W.inv);
+  else
+    hipLaunchKernelGGL((k_patch_invert_wide<double>), dim3(blocks), dim3(64), 0, st, W.nw, W.dof, W.pos, K, M, D, mask, alpha, (double*)W.inv);
+}
+
+// host decode of a copy of the wide inverses into [nw][32][32], entry (l, j) = the factor lane l multiplies r_j with
+void pgxk_patch_wide_decode(int nw, int f32, const void* raw, double* out) {
+  for (int p = 0; p < nw; ++p)
+    for (int l = 0; l < PW; ++l)
+      for (int j = 0; j < PW; ++j) {
+        const size_t at = (size_t)p * PW * PW + ((size_t)(j / 4) * PW + l) * 4 + (j % 4);
+        out[((size_t)p * PW + l) * PW + j] = f32 ? (double)((const float*)raw)[at] : ((const double*)raw)[at];
+      }
+}
 
 void pgxk_patch_positions(hipStream_t st, int np, int NN, const int32_t* pdof, const int32_t* rowptr, const int32_t* colm,
                           int32_t* ppos) {
@@ -353,7 +516,7 @@ void pgxk_patch_decode(int np, int NN, int f32, int sym, const void* raw, double
 
 void pgxk_patch_sweep(hipStream_t st, int np, int NN, int nv, int nd, const int32_t* pdof, const int32_t* edge_ends,
                       const void* pinv, int f32, int sym, const double* ru, const double* rp, double omega, double* xu, double* xp,
-                      double* su, double* sp) {
+                      double* su, double* sp, const PgxWidePatches* W) {
   const unsigned blocks = (unsigned)(((int64_t)np * GRP + 255) / 256);
 #define PGX_APP(N, T, S)                                                                                                          \
   hipLaunchKernelGGL((k_patch_apply<N, T, S>), dim3(blocks), dim3(256), 0, st, np, nv, nd, pdof, edge_ends, (const T*)pinv, ru, rp, \
@@ -366,6 +529,15 @@ void pgxk_patch_sweep(hipStream_t st, int np, int NN, int nv, int nd, const int3
     else if (f32 && sym) PGX_APP(8, float, true); else if (f32) PGX_APP(8, float, false); else PGX_APP(8, double, false);
   }
 #undef PGX_APP
+  if (W && W->nw > 0) {  // stars of degree 8 ... 15: after the narrow stars (same stream), before the edge averages
+    const unsigned wb = (unsigned)((W->nw + 1) / 2);
+    if (W->f32)
+      hipLaunchKernelGGL((k_patch_apply_wide<float>), dim3(wb), dim3(64), 0, st, W->nw, nv, W->verts, W->dof, edge_ends,
+                         (const float*)W->inv, ru, rp, omega, xu, xp, (float*)su, (float*)sp);
+    else
+      hipLaunchKernelGGL((k_patch_apply_wide<double>), dim3(wb), dim3(64), 0, st, W->nw, nv, W->verts, W->dof, edge_ends,
+                         (const double*)W->inv, ru, rp, omega, xu, xp, (float*)su, (float*)sp);
+  }
   const int ne = nd - nv;
   hipLaunchKernelGGL(k_patch_edges, dim3((ne + 255) / 256), dim3(256), 0, st, ne, nv, omega, (const float*)su, (const float*)sp, xu, xp);
 }

@@ -224,10 +224,11 @@ class NonlinearProblem:
             _lib.check(lib, None, rc, "pgx_create_sharded")
         self._h = h
         self.ndofs = V.num_dofs
-        # a refined general mesh (fem.refine) hands its nested P1 hierarchy to a degree-1 handle: FGMRES can then precondition with the
-        # multilevel cycle (include/pgx.h: pgx_set_hierarchy).  Meshes without one - files, structured grids - are solved as before
+        # a refined general mesh (fem.refine) hands its nested P1 hierarchy to the handle: FGMRES can then precondition with the
+        # multilevel cycle (degree 1) or with the two-level patch cycle over it (degree 2; include/pgx.h: pgx_set_hierarchy).  Meshes
+        # without one - files, structured grids - are solved as before
         hier = getattr(mesh, "hierarchy", None)
-        if hier and V.degree == 1 and part is None and lu_comm is None and not mesh.structured:
+        if hier and V.degree in (1, 2) and part is None and lu_comm is None and not mesh.structured:
             self.set_hierarchy(hier)
         F.sol.x._binding = (self, "state")
         F.sol_k.x._binding = (self, "prev")
@@ -486,6 +487,19 @@ class NonlinearProblem:
         Ainv = np.empty((nv, 2 * NN, 2 * NN))
         self._check_code(self._lib.pgx_p2_patch_export(self._h, _lib.iptr(pdof), _lib.dptr(Ainv)), "pgx_p2_patch_export")
         return pdof, Ainv
+
+    def p2_wide_export(self):
+        """(verts [nw] int32, wdof [nw, 16] int32, Ainv [nw, 32, 32]) of the wide stars - vertices of degree 8 ... 15 - at the last
+        assemble_jacobian (include/pgx.h: pgx_p2_wide_export; a test hook).  nw = 0 on a mesh without such vertices."""
+        nw = C.c_int32(0)
+        self._check_code(self._lib.pgx_p2_wide_export(self._h, C.byref(nw), None, None, None), "pgx_p2_wide_export")
+        verts = np.empty(nw.value, dtype=np.int32)
+        wdof = np.empty((nw.value, 16), dtype=np.int32)
+        Ainv = np.empty((nw.value, 32, 32))
+        if nw.value:
+            self._check_code(self._lib.pgx_p2_wide_export(self._h, None, _lib.iptr(verts), _lib.iptr(wdof), _lib.dptr(Ainv)),
+                             "pgx_p2_wide_export")
+        return verts, wdof, Ainv
 
     def p2_cycle_apply(self, stage, b, x0=None, nu=6, omega=0.75):
         """One stage of the P2 two-level cycle on host vectors (include/pgx.h: pgx_p2_cycle_apply; a test hook): 1 one sweep from x0

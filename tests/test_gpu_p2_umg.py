@@ -1,0 +1,515 @@
+"""Degree 2 on refined general meshes: the two-level patch cycle over the block-CSR hierarchy (include/pgx.h: pgx_set_hierarchy on a
+degree-2 handle; csrc/pgx_api.hip: pcycle_p2_patch -> vcycle_umg) and the wide stars of degree 8 ... 15 (csrc/pgx_patch.hip:
+k_patch_invert_wide, k_patch_apply_wide), against tests/p2_umg_reference.py.
+
+Meshes (tests/p2_umg_reference.build_mesh): D34 469 vertices, degree <= 6, 7 slots; D5 227, one vertex of degree 7, 8 slots; W4 =
+create_disk(0.4, refinements=2) 289, ONE wide star; X42 = the crossed 4 x 2 rectangle refined twice, 281, THREE wide stars - an odd
+count, the second half of the last wavefront idles; F12 = the 12-fan refined twice, 121, the centre star with 26 of 32 rows live; F16 =
+the 16-fan: no patch smoother, as before.  States (_p2_state): tests/umg_reference.state on the P2 dof coordinates for the stored
+levels (exact zeros in D near (0.3, 0.2)), the same without its push by -800 for whatever runs the cycle; alpha in {2.5, 100}.
+
+Bounds, each taken from the test that set it:
+  level-0 D            T^T D_P2 T of the exported P2 blocks, 1e-12 of its largest entry (test_hierarchy_d_under_the_p2_handle)
+  coarser levels       the twin's triple products of the exported level 0, 1e-13 of the level's largest entry (tests/test_gpu_umg.py)
+  wide inverses        double: e(device) <= 16 (E_p + 4 eps size) against 60-digit inverses, E_p from the float64 twin of the elimination
+                       at P = 32; float = float32(double), bit for bit (test_stored_inverses_in_every_form)
+  one sweep            1e-13 s_i on vertex dofs, + omega 2^-23 max(|y_a|, |y_b|) on edge dofs (test_one_sweep)
+  whole cycle          16 E + 1e-12 max |z| per block, E = |twin with float stash and float D - twin in float64| (test_whole_cycle)
+  cycle on a level     1e-12 of max |z_ref| per half (test_cycle_against_the_twin_on_every_level)
+  full runs            Newton counts equal to the LU run's, u within 1e-10 relative L2, no rescue; Krylov counts per Newton step
+                       equal to the twin's run (double form) and to the double form's (default form, forced auto)
+Every figure is printed before it is asserted (`P2UMG ...` lines)."""
+import contextlib
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+from oracle import pg_oracle as O
+from tests import p2_cycle_reference as PR
+from tests import p2_umg_reference as Q
+from tests import umg_reference as UR
+
+pytestmark = pytest.mark.gpu
+PGX_EINVAL, PGX_EHIP, PGX_ESTATE = -1, -2, -5
+ALPHAS = (2.5, 100.0)
+NU, OMEGA, MARGIN, COARSE_SWEEPS = 6, 0.75, 16.0, 60
+FORMS = {"double": {"PGX_P2_PATCH_F32": 0}, "float": {"PGX_P2_PATCH_F32": 1, "PGX_P2_PATCH_SYM": 0},
+         "float-sym": {"PGX_P2_PATCH_F32": 1, "PGX_P2_PATCH_SYM": 1}}
+MG = {"ksp_type": "preonly", "pc_type": "pgx_mg", "ksp_error_if_not_converged": True, "snes_error_if_not_converged": True,
+      "snes_linesearch_type": "none", "snes_rtol": 1e-6, "snes_max_it": 100}
+LU = dict(MG, pc_type="pgx_lu")
+AUTO = dict(MG, pc_type="lu")
+
+_meshes, _probs, _live = {}, {}, None  # ONE live handle: tuning keys are process-wide
+
+
+def _mesh(name):
+    if name not in _meshes:
+        _meshes[name] = Q.build_mesh(name)
+    return _meshes[name]
+
+
+def _prob(name):
+    if name not in _probs:
+        msh = _mesh(name)
+        _probs[name] = O.ObstacleLagrange(msh.geometry, msh.cells, 2)
+        assert np.array_equal(_probs[name].edges, msh.edges()[0])
+    return _probs[name]
+
+
+def _p2_state(name, push=False):
+    """(x, xk) on the P2 dofs.  push: tests/umg_reference.state - the dofs within 0.25 of (0.3, 0.2) pushed down by 800, exact zeros in
+    D; the stored levels are tested there.  A P2 psi_h overshoots between such nodes (a vertex function is -1/8 at an edge midpoint:
+    +100), exp(psi_h) then exceeds the float range and the float copy of D that the cycle's residual reads holds inf - on a state no
+    solve produces.  The cycle and its stages are tested on the same state without the push."""
+    prob = _prob(name)
+    x = _mesh(name).geometry
+    dofs = np.concatenate([x, 0.5 * (x[prob.edges[:, 0]] + x[prob.edges[:, 1]])])
+    return UR.state(dofs) if push else Q.smooth_state(2 * len(dofs), 11)
+
+
+class _Handle:
+    def __init__(self, name, alpha, keys, push):
+        from proximalgalerkin_amd import _lib
+        from proximalgalerkin_amd.obstacle import setup_problem
+
+        self.key, self.keys, self.problem = (name, alpha, tuple(sorted(keys.items())), push), dict(keys), None
+        self.name, self.alpha, self.prob, self.push = name, alpha, _prob(name), push
+        for k, v in self.keys.items():
+            _lib.tuning_set(k, v)
+        try:
+            self.problem, sol, sol_k, a = setup_problem(_mesh(name), 2)  # NonlinearProblem attaches mesh.hierarchy
+            self.x, self.xk = _p2_state(name, push)
+            sol_k.x.array[:] = self.xk
+            a.value = alpha
+            self.problem.assemble_jacobian(self.x)
+            self.info = self.problem.p2_cycle_info()
+        except BaseException:
+            self.close()
+            raise
+
+    def blocks(self):
+        prob = self.prob
+        rowptr, col, K, M, D = self.problem.export_blocks()
+        assert np.array_equal(rowptr, prob.indptr_s.astype(np.int32)) and np.array_equal(col, prob.indices_s)
+        return tuple(sp.csr_matrix((v, col, rowptr), shape=(prob.n, prob.n)) for v in (K, M, D))
+
+    def levels(self):
+        return [self.problem.umg_level_export(l) for l in range(self.problem.umg_levels())]
+
+    def exports(self):
+        pdof, Ainv = self.problem.p2_patch_export()
+        verts, wdof, Winv = self.problem.p2_wide_export()
+        return pdof, Ainv, verts, wdof, Winv
+
+    def twin(self, slots=None):
+        """(reference on the exported blocks and the exported level 0, in the device's slot order; the exported inverses)"""
+        prob = self.prob
+        pdof, Ainv, verts, wdof, Winv = self.exports()
+        Q.check_tables(prob.edges, prob.nv, self.info["patch_nn"], pdof, verts, wdof)
+        table, inv = Q.scatter_exports(prob.nv, pdof, Ainv, verts, wdof, Winv, slots)
+        L0 = self.problem.umg_level_export(0)
+        coarse = tuple(sp.csr_matrix((L0[v], L0["col"], L0["rowptr"]), shape=(L0["n"], L0["n"])) for v in ("K", "M", "D"))
+        K, M, D = self.blocks()
+        ref = Q.P2UmgReference(K, M, D, self.alpha, prob.isbc, prob.edges, prob.nv, _mesh(self.name).hierarchy, coarse_blocks=coarse,
+                               coarse_sweeps=COARSE_SWEEPS, patch_nu=self.info["patch_nu"], patch_omega=self.info["patch_omega"], table=table)
+        return ref, inv
+
+    def close(self):
+        from proximalgalerkin_amd import _lib
+
+        if self.problem is not None:
+            self.problem.close()
+        for k in self.keys:
+            _lib.tuning_set(k, None)
+
+
+def _drop():
+    global _live
+    if _live is not None:
+        live, _live = _live, None
+        live.close()
+
+
+def _handle(name, alpha, keys=None, push=False):
+    global _live
+    keys = dict({"PGX_UMG_COARSE_SWEEPS": COARSE_SWEEPS}, **(keys or {}))
+    key = (name, alpha, tuple(sorted(keys.items())), push)
+    if _live is None or _live.key != key:
+        _drop()
+        _live = _Handle(name, alpha, keys, push)
+    return _live
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _close_last_handle():
+    yield
+    _drop()
+
+
+def _hip_guard(call, *a, **kw):
+    """A HIP runtime error ends the session: nothing more is launched on a device that reported one."""
+    from proximalgalerkin_amd._lib import PgxError
+
+    try:
+        return call(*a, **kw)
+    except PgxError as e:
+        if getattr(e, "code", 0) == PGX_EHIP:
+            pytest.exit(f"HIP error: {e}", returncode=3)
+        raise
+
+
+def _refused(call, code):
+    from proximalgalerkin_amd._lib import PgxError
+
+    with pytest.raises(PgxError) as e:
+        call()
+    assert e.value.code == code, (e.value.code, code, str(e.value))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# stored levels
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("alpha", ALPHAS)
+@pytest.mark.parametrize("name", ["D34", "D5", "W4"])
+def test_stored_levels(require_gpu, name, alpha):
+    h = _handle(name, alpha, push=True)
+    assert h.info["hierarchy"]
+    msh, prob = _mesh(name), h.prob
+    levels = h.levels()
+    assert [L["n"] for L in levels] == [len(p) for p in msh.hierarchy] + [UR.coarse_sizes(msh.hierarchy)[-1]]
+    K, M, D = h.blocks()
+    T = PR.p1_to_p2(prob.edges, prob.nv)
+    L0 = levels[0]
+    dense = lambda L, v: sp.csr_matrix((L[v], L["col"], L["rowptr"]), shape=(L["n"], L["n"])).toarray()  # noqa: E731
+    assert np.count_nonzero(D.data == 0.0) > 0 and np.ptp(np.log10(D.data[D.data > 0])) > 4
+    for v, X in (("K", K), ("M", M), ("D", D)):
+        want = (T.T @ X @ T).toarray()
+        err = np.abs(dense(L0, v) - want).max() / np.abs(want).max()
+        print(f"P2UMG level 0 {name} alpha {alpha} {v}: |stored - T^T . T| = {err:.2e} of the largest entry")
+        assert err <= 1e-12, (name, alpha, v, err)
+    assert np.array_equal(L0["mask"], prob.isbc[: prob.nv])
+    ref = UR.UmgReference(*(sp.csr_matrix((L0[v], L0["col"], L0["rowptr"]), shape=(L0["n"], L0["n"])) for v in ("K", "M", "D")), alpha,
+                          L0["mask"], msh.hierarchy, coarse_sweeps=COARSE_SWEEPS)
+    for l, (L, R) in enumerate(zip(levels, ref.levels)):
+        assert np.array_equal(L["rowptr"], R["M"].indptr) and np.array_equal(L["col"], R["M"].indices), (name, l)
+        assert np.array_equal(L["mask"], R["mask"]), (name, l)
+        for v in ("K", "M", "D"):
+            want = R[v].toarray()
+            err, top = np.abs(dense(L, v) - want).max(), np.abs(want).max()
+            print(f"P2UMG stored {name} alpha {alpha} level {l} {v}: {err / top:.2e} of the largest entry")
+            assert err <= 1e-13 * top, (name, alpha, l, v, err / top)
+    # two fills of one state: identical bytes on every level
+    h.problem.assemble_jacobian(h.x)
+    for a, b in zip(levels, h.levels()):
+        for v in ("rowptr", "col", "K", "M", "D", "mask"):
+            assert a[v].tobytes() == b[v].tobytes(), (name, v)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# wide patches: tables, inverses, one sweep
+# ---------------------------------------------------------------------------------------------------------------------
+WIDE = {"W4": 1, "X42": 3, "F12": 1}
+
+
+@pytest.mark.parametrize("alpha", ALPHAS)
+@pytest.mark.parametrize("name", list(WIDE))
+def test_wide_tables_and_inverses(require_gpu, name, alpha):
+    out = {}
+    for form in ("double", "float", "float-sym"):
+        h = _handle(name, alpha, FORMS[form])
+        assert h.info["form"] == form and h.info["patch_nn"] == 8
+        out[form] = h.exports()
+        assert len(out[form][2]) == WIDE[name] and np.isfinite(out[form][4]).all()
+    pdof, Ainv, verts, wdof, Winv = out["double"]
+    prob = h.prob
+    Q.check_tables(prob.edges, prob.nv, 8, pdof, verts, wdof)
+    assert np.array_equal(Ainv[verts], np.tile(np.eye(16), (len(verts), 1, 1)))  # all -1 rows: identity patches in the narrow form
+    if name == "F12":
+        assert int((wdof[0] >= 0).sum()) == 13  # 26 of the 32 rows hold the star
+    # the patch matrices in the device's 16 slots (P = 32), from the exported blocks
+    ref, _ = h.twin(slots=Q.WIDE_SLOTS)
+    A = ref.patch_matrices()[verts]
+    X = PR.exact_inverse(A)
+    Ep = PR.inverse_error(A, PR.gauss_jordan_inverse(A), X)
+    size = PR.inverse_size(A, X)
+    e = PR.inverse_error(A, Winv, X)
+    ratio = e / (Ep + 4.0 * PR.EPS * size)
+    print(f"P2UMG wide inverse {name} alpha {alpha}: max E_p {Ep.max():.2e} max e(device) {e.max():.2e} worst e / bracket {ratio.max():.2f} "
+          f"max scaled |X| {size.max():.2e}")
+    assert np.all(e <= MARGIN * (Ep + 4.0 * PR.EPS * size)), (name, alpha, ratio.max())
+    with np.errstate(over="ignore"):
+        f32 = Winv.astype(np.float32)
+    for form in ("float", "float-sym"):  # the wide stars have one float form: full rows, float32(double) entry for entry
+        got = out[form][4]
+        assert np.array_equal(out[form][2], verts) and np.array_equal(out[form][3], wdof)
+        assert np.array_equal(got.astype(np.float32).astype(np.float64), got)
+        assert np.array_equal(got.astype(np.float32).view(np.uint32), f32.view(np.uint32)), (name, form)
+
+
+def _check_sweep(tag, ref, z, zref, s, ymax, omega):
+    n, nv = ref.n, ref.nv
+    edge = np.tile(np.arange(n) >= nv, 2)
+    bound = 1e-13 * s + np.where(edge, omega * 2.0 ** -23 * ymax, 0.0)
+    err = np.abs(z - zref)
+    tiny = np.finfo(np.float64).tiny
+    rv = (err[~edge] / np.maximum(1e-13 * s[~edge], tiny)).max()
+    re = (err[edge] / np.maximum(bound[edge], tiny)).max()
+    print(f"P2UMG sweep {tag}: vertex dofs error / bound {rv:.2e}, edge dofs {re:.2e}")
+    assert np.all(err <= bound), (tag, rv, re)
+
+
+@pytest.mark.parametrize("form", ["double", "float-sym"])
+@pytest.mark.parametrize("name", list(WIDE))
+def test_one_sweep_with_wide_stars(require_gpu, name, form):
+    """Stage 1 from x = 0 and from an x0, against the twin's sweep on the scattered exports: random right-hand sides, an impulse at a
+    wide vertex and one at an edge of its star.  Two sweeps of one state are byte-identical."""
+    h = _handle(name, 100.0, FORMS[form])
+    ref, inv = h.twin()
+    n, omega = ref.n, h.info["patch_omega"]
+    verts, wdof = h.exports()[2:4]
+    rng = np.random.default_rng(17)
+
+    def impulse(dof):
+        b = np.zeros(2 * n)
+        b[dof], b[n + dof] = 1.0, -1.0
+        return b
+
+    rhs = {"random": rng.standard_normal(2 * n), "wide-vertex": impulse(int(verts[-1])), "wide-edge": impulse(int(wdof[-1, 3]))}
+    for bname, b in rhs.items():
+        z = _hip_guard(h.problem.p2_cycle_apply, 1, b)
+        assert z.tobytes() == _hip_guard(h.problem.p2_cycle_apply, 1, b).tobytes()
+        s, ymax = ref.sweep_scales(b, inv)
+        zref = ref.sweep(np.zeros_like(b), b, inv, stash_f32=True)
+        if bname != "random":
+            assert np.count_nonzero(z[verts[-1]]) == 1  # the wide star's own vertex dof moved
+        _check_sweep(f"{name} {form} {bname} first", ref, z, zref, s, ymax, omega)
+        x0 = zref * (1.0 + rng.uniform(-0.5, 0.5, len(zref)))
+        r = _hip_guard(h.problem.p2_cycle_apply, 2, b, x0)
+        z = _hip_guard(h.problem.p2_cycle_apply, 1, b, x0)
+        s, ymax = ref.sweep_scales(r, inv)
+        _check_sweep(f"{name} {form} {bname} from x0", ref, z, ref.sweep(x0, r, inv, stash_f32=True), s, ymax, omega)
+
+
+@pytest.mark.parametrize("name", ["D34", "D5"])
+def test_narrow_exports_do_not_change_with_the_wide_key(require_gpu, name):
+    got = {}
+    for wide in (1, 0):
+        h = _handle(name, 2.5, {"PGX_P2_PATCH_WIDE": wide})
+        pdof, Ainv = h.problem.p2_patch_export()
+        verts, wdof, Winv = h.problem.p2_wide_export()
+        assert len(verts) == 0 and wdof.shape == (0, 16) and Winv.shape == (0, 32, 32)  # nw = 0
+        b = np.random.default_rng(3).standard_normal(2 * h.prob.n)
+        got[wide] = (h.info["patch_nn"], pdof.tobytes(), Ainv.tobytes(), _hip_guard(h.problem.p2_cycle_apply, 1, b).tobytes())
+    assert got[1] == got[0] and got[1][0] == (7 if name == "D34" else 8)
+
+
+def test_degree_16_has_no_patch_smoother_and_degree_8_none_without_the_wide_key(require_gpu):
+    from proximalgalerkin_amd import _lib
+    from proximalgalerkin_amd.obstacle import setup_problem
+
+    _drop()
+    for name, keys in (("F16", {}), ("W4", {"PGX_P2_PATCH_WIDE": 0})):
+        for k, v in keys.items():
+            _lib.tuning_set(k, v)
+        try:
+            problem = setup_problem(_mesh(name), 2)[0]
+            try:
+                problem.assemble_jacobian(_p2_state(name)[0])
+                _refused(problem.p2_cycle_info, PGX_ESTATE)  # patch_nn == 0
+                _refused(problem.p2_wide_export, PGX_ESTATE)
+            finally:
+                problem.close()
+        finally:
+            for k in keys:
+                _lib.tuning_set(k, None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the whole cycle, and the hierarchy's own cycle on every level
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", ["double", "float-sym"])
+@pytest.mark.parametrize("name", ["D34", "W4", "X42"])
+def test_whole_cycle(require_gpu, name, form):
+    """Stage 0 at nu = 6, omega = 0.75, entered as FGMRES enters the preconditioner, against the twin's cycle on the exported
+    inverses, with the float stash and the D that the residual reads."""
+    for alpha in ALPHAS:
+        h = _handle(name, alpha, FORMS[form])
+        assert h.info["hierarchy"] and h.info["resid_kernel"] != "structured"
+        ref, inv = h.twin()
+        n, nv = ref.n, ref.nv
+        rows = bool(h.info["resid_f32"])
+        rng = np.random.default_rng(31)
+        b_edge = next(e for e in range(n - nv) if ref.isbc[nv + e])
+        rhs = {"random": rng.standard_normal(2 * n), "boundary-edge": np.zeros(2 * n), "-F": -h.prob.residual(h.x, h.xk, alpha)}
+        rhs["boundary-edge"][[nv + b_edge, n + nv + b_edge]] = 1.0, -1.0
+        verts = h.exports()[2]
+        if len(verts):
+            rhs["wide-vertex"] = np.zeros(2 * n)
+            rhs["wide-vertex"][[verts[0], n + verts[0]]] = 1.0, -1.0
+        for bname, b in rhs.items():
+            z = _hip_guard(h.problem.p2_cycle_apply, 0, b, None, nu=NU, omega=OMEGA)
+            z32 = ref.cycle(b, inv, nu=NU, omega=OMEGA, stash_f32=True, d_f32=rows)
+            z64 = ref.cycle(b, inv, nu=NU, omega=OMEGA, stash_f32=False, d_f32=False)
+            for blk, s in (("u", slice(0, n)), ("psi", slice(n, 2 * n))):
+                E = np.abs(z32[s] - z64[s]).max()
+                dev = np.abs(z[s] - z32[s]).max()
+                bound = MARGIN * E + 1e-12 * np.abs(z32[s]).max()
+                print(f"P2UMG cycle {name} {form} alpha {alpha} float-D {rows} {bname} {blk}: E {E:.2e} device {dev:.2e} "
+                      f"max |z| {np.abs(z32[s]).max():.2e} device / bound {dev / bound:.3f}")
+                assert E > 0.0 and dev <= bound, (name, form, alpha, bname, blk, dev, E)
+
+
+@pytest.mark.parametrize("name", ["D34", "W4"])
+def test_hierarchy_cycle_on_every_level_of_a_p2_handle(require_gpu, name):
+    """pgx_umg_cycle_apply: level-l vectors have 2 n_l vertex entries; level 0 is entered as the two-level cycle enters it."""
+    for alpha in ALPHAS:
+        h = _handle(name, alpha)
+        levels = h.levels()
+        L0 = levels[0]
+        ref = UR.UmgReference(*(sp.csr_matrix((L0[v], L0["col"], L0["rowptr"]), shape=(L0["n"], L0["n"])) for v in ("K", "M", "D")),
+                              alpha, L0["mask"], _mesh(name).hierarchy, coarse_sweeps=COARSE_SWEEPS)
+        worst = 0.0
+        for level, L in enumerate(levels):
+            n = L["n"]
+            rng = np.random.default_rng(10 * level + n)
+            free = np.flatnonzero(~L["mask"])
+            rhs = {"random": rng.standard_normal(2 * n), "impulse": np.zeros(2 * n)}
+            rhs["impulse"][[free[len(free) // 2], n + free[len(free) // 2]]] = 1.0, -0.7
+            for b in rhs.values():
+                if level > 0:
+                    b[:n][L["mask"]] = 0.0
+                for nu in (1, 2, 6):
+                    zr = ref.cycle(level, b, nu, OMEGA)
+                    z = _hip_guard(h.problem.umg_cycle_apply, level, b, nu=nu, omega=OMEGA)
+                    for s in (slice(0, n), slice(n, 2 * n)):
+                        err = np.abs(z[s] - zr[s]).max() / np.abs(zr[s]).max()
+                        worst = max(worst, err)
+                        assert err <= 1e-12, (name, alpha, level, nu, err)
+        print(f"P2UMG hierarchy cycle {name} alpha {alpha}: worst {worst:.2e} of max |z_ref|")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# full runs
+# ---------------------------------------------------------------------------------------------------------------------
+def _solve(msh, options, keys=None, tmp=None):
+    """Settings B: (u on the P2 dofs, Newton counts, Krylov iterations per LVPP solve, rescues by the sparse LU, Krylov iterations
+    per Newton step).  The last from the library's own monitor lines, one "KSP its N" per Newton step, where `tmp` names a directory
+    (None otherwise)."""
+    from proximalgalerkin_amd import _lib
+    from proximalgalerkin_amd.obstacle import run_outer_loop, setup_problem
+
+    _drop()
+    keys = keys or {}
+    for k, v in keys.items():
+        _lib.tuning_set(k, v)
+    try:
+        options = dict(options)
+        if tmp is not None:
+            options["snes_monitor"] = None
+            monitor = str(tmp / "monitor.txt")
+        problem, sol, sol_k, alpha = setup_problem(msh, 2, petsc_options=options)
+        try:
+            lin, solve = [], problem.solve
+
+            def counted():
+                r = solve()
+                lin.append(problem.solver.getLinearSolveIterations())
+                return r
+
+            problem.solve = counted
+            with (Q.c_stdout_to(monitor) if tmp is not None else contextlib.nullcontext()):
+                hist = run_outer_loop(problem, sol, sol_k, alpha, 500, "double_exponential", 1e2, 1e-4)
+            u = sol.x.array[: sol.function_space.block_size].copy()
+            problem.assemble_jacobian()
+            fallbacks = problem.p2_cycle_info()["fallbacks"]
+        finally:
+            problem.close()
+    finally:
+        for k in keys:
+            _lib.tuning_set(k, None)
+    steps = Q.krylov_per_newton_step(monitor) if tmp is not None else None
+    return u, [int(v) for v in hist["Newton steps"]], lin, fallbacks, steps
+
+
+@pytest.mark.parametrize("name", ["D34", "W4"])
+def test_full_runs(require_gpu, name, tmp_path):
+    """"pgx_mg" against "pgx_lu", and pc_type auto forced onto the cycle (PGX_UMG_MIN_P2=0) without a rescue.  Krylov iterations PER
+    NEWTON STEP, read from the library's monitor lines: the double form's list equals the twin's run through
+    oracle.pg_oracle.newton_solve, the default form's and the forced-auto run's equal the double form's.  (Measured: equal, no entry
+    off by one - D34 7, 7, 8, 8, 8, 7, 8, 9, 9, 7, 10, 10, 8, 10, 10, 8, 11, 10, 8, 11, 11, 9, 13, 12, 10, 10, 9.)"""
+    msh, prob = _mesh(name), _prob(name)
+    u_lu, newton_lu, lin_lu, _, _ = _solve(msh, LU)
+    u, newton, lin, fb, steps = _solve(msh, MG, tmp=tmp_path)
+    u_d, newton_d, lin_d, _, steps_d = _solve(msh, MG, FORMS["double"], tmp=tmp_path)
+    u_a, newton_a, lin_a, fb_a, steps_a = _solve(msh, AUTO, {"PGX_UMG_MIN_P2": 0}, tmp=tmp_path)
+    stats = []
+    _, hist = O.solve_problem(prob, 500, "double_exponential", 1e2, 1e-4,
+                              linear_solve=Q.make_linear_solve(prob, msh.hierarchy, nu=NU, omega=OMEGA, stats=stats))
+    print(f"P2UMG run {name}: Newton {newton} (LU {newton_lu}, double {newton_d}, auto {newton_a}); Krylov per Newton step default {steps} "
+          f"double {steps_d} auto {steps_a} twin {stats}; per LVPP solve {lin}, LU {lin_lu}; rescues {fb} / {fb_a}")
+    assert newton == newton_lu == newton_d == newton_a == [int(v) for v in hist["Newton steps"]]
+    for tag, v in (("default", u), ("double", u_d), ("auto", u_a)):
+        err = np.linalg.norm(v - u_lu) / np.linalg.norm(u_lu)
+        print(f"P2UMG run {name} {tag}: rel-L2(u) against the LU run {err:.2e}")
+        assert err <= 1e-10, (name, tag, err)
+    top = 13 if name == "D34" else 12  # the prototype's largest counts on these two meshes
+    assert fb == 0 and fb_a == 0
+    for s_, l_ in ((steps, lin), (steps_d, lin_d), (steps_a, lin_a)):  # one monitor line per Newton step, consistent with the sums
+        ends = np.cumsum(newton)
+        assert len(s_) == sum(newton) and [int(sum(s_[a:b])) for a, b in zip(np.concatenate([[0], ends[:-1]]), ends)] == l_, (s_, l_)
+        assert max(s_) <= top, (max(s_), top)
+    assert max(stats) <= top
+    assert steps_d == stats, (steps_d, stats)
+    assert steps == steps_d and steps_a == steps_d, (steps, steps_d, steps_a)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# refusals
+# ---------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_p2_handle_usable(require_gpu):
+    from proximalgalerkin_amd import fem
+    from proximalgalerkin_amd.obstacle import setup_problem
+
+    _drop()
+    fine = _mesh("D5")
+    par = [p.copy() for p in fine.hierarchy]
+    sizes = UR.coarse_sizes(par)
+    plain = fem.Mesh(fine.geometry, fine.cells)  # as a mesh read from a file: nothing is attached when the handle is created
+    x, xk = _p2_state("D5")
+    other = setup_problem(fem.create_rectangle(Q.DOMAIN, (8, 8)), 2)[0]  # a structured P2 handle has its grid hierarchy
+    try:
+        _refused(lambda: other.set_hierarchy(par), PGX_EINVAL)
+    finally:
+        other.close()
+    problem, sol, sol_k, a = setup_problem(plain, 2)
+    try:
+        sol_k.x.array[:] = xk
+        a.value = 2.5
+        bad = [p.copy() for p in par]
+        bad[1][sizes[1] + 3, 1] = sizes[1]  # a parent index outside the coarse level
+        _refused(lambda: problem.set_hierarchy(bad), PGX_EINVAL)
+        bad = [p.copy() for p in par]
+        bad[0][5] = (5, 6)  # an inherited row that is not (v, v)
+        _refused(lambda: problem.set_hierarchy(bad), PGX_EINVAL)
+        problem.set_hierarchy(par)  # the handle took no harm: the right hierarchy goes in ...
+        _refused(lambda: problem.set_hierarchy(par), PGX_ESTATE)  # ... once
+        _refused(lambda: problem.umg_level_export(0), PGX_ESTATE)  # no Jacobian yet
+        problem.assemble_jacobian(x)
+        assert problem.p2_cycle_info()["hierarchy"] and [problem.umg_level_export(l)["n"] for l in range(3)] == [len(par[0])] + sizes
+        assert len(problem.p2_wide_export()[0]) == 0  # degree 7: no wide star
+        z = problem.p2_cycle_apply(0, np.ones(problem.ndofs))
+        assert np.isfinite(z).all() and np.abs(z).max() > 0.0
+    finally:
+        problem.close()
+    problem = setup_problem(plain, 2)[0]
+    try:
+        problem.assemble_jacobian(x)
+        _refused(lambda: problem.set_hierarchy(par), PGX_ESTATE)  # after the first fill
+        assert not problem.p2_cycle_info()["hierarchy"]
+        _refused(lambda: problem.p2_cycle_apply(0, np.zeros(problem.ndofs)), PGX_ESTATE)
+        z = problem.p2_cycle_apply(1, np.ones(problem.ndofs))  # still the handle it was
+        assert np.isfinite(z).all()
+    finally:
+        problem.close()

@@ -2,6 +2,7 @@
 """Example 01 on the reference's disk family with the multilevel cycle of refined general meshes.
 
     python3 tools/disk_mg_check.py [--levels 3 4 5 6] [--modes mg single lu] [--trace-level 5] [--out profiles/umg_disk_scaling.json]
+    python3 tools/disk_mg_check.py --degree 2 [--levels 3 4 5] [--modes mg lu auto]          (-> profiles/p2_umg_disk_scaling.json)
 
 For every L: create_disk(0.1, refinements=L) - the construction of generate_mesh_gmsh.py's disk_L - solved with settings B
 (double_exponential, alpha_max 100, tol 1e-4) under "pgx_mg" (the cycle), "pgx_mg" with PGX_UMG=0 (the single-level smoother) and
@@ -13,7 +14,13 @@ mean over all solves, the first solve and the mean without it are recorded separ
 the first mesh before anything is timed (code objects loaded); one timed run per entry, so no spread.  --trace-level L runs the "mg" solve of that L once more under rocprofv3 --kernel-trace
 and adds the per-launch times of the k_umg_* kernels per grid size, with the achieved bandwidth of k_umg_rap and
 k_umg_resid_restrict on the finest transfer against their algorithmic bytes.  A mode that fails (the single-level smoother runs into
-the Krylov iteration cap on the large meshes) is recorded with its message.  Needs an MI355X."""
+the Krylov iteration cap on the large meshes) is recorded with its message.  Needs an MI355X.
+
+--degree 2: the same family at degree 2 (obstacle_pg.py -p 2).  "mg" is the two-level patch cycle over the hierarchy, "lu" the sparse
+LU, "auto" pc_type auto forced onto the cycle at every size (PGX_UMG_MIN_P2=0): the cycle first, the sparse LU for a Newton solve in
+which it stagnates.  Recorded in addition: create_seconds (the handle, pgx_set_hierarchy included), fallbacks (Newton solves rescued
+by the LU) and nw (wide stars).  setup_and_solve_seconds - handle creation plus every solve, rescues included - of "auto" against
+"lu" is what PGX_UMG_MIN_P2's default is taken from."""
 import argparse
 import contextlib
 import csv
@@ -34,7 +41,7 @@ ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 BASE = {"ksp_type": "preonly", "ksp_error_if_not_converged": True, "snes_error_if_not_converged": True, "snes_linesearch_type": "none",
         "snes_rtol": 1e-6, "snes_max_it": 100}
-MODES = {"mg": ("pgx_mg", {}), "single": ("pgx_mg", {"PGX_UMG": 0}), "lu": ("pgx_lu", {})}
+MODES = {"mg": ("pgx_mg", {}), "single": ("pgx_mg", {"PGX_UMG": 0}), "lu": ("pgx_lu", {}), "auto": ("lu", {"PGX_UMG_MIN_P2": 0})}
 
 
 @contextlib.contextmanager
@@ -53,7 +60,7 @@ def c_stdout_to(path):
             os.close(saved)
 
 
-def solve(msh, mode, monitor_file=None):
+def solve(msh, mode, monitor_file=None, degree=1):
     from proximalgalerkin_amd import _lib
     from proximalgalerkin_amd.obstacle import run_outer_loop, setup_problem
 
@@ -75,7 +82,10 @@ def solve(msh, mode, monitor_file=None):
         opts = dict(BASE, pc_type=pc)
         if monitor_file:
             opts["snes_monitor"] = None
-        problem, sol, sol_k, alpha = setup_problem(msh, 1, petsc_options=opts)
+        t_create = time.perf_counter()
+        problem, sol, sol_k, alpha = setup_problem(msh, degree, petsc_options=opts)
+        t_create = time.perf_counter() - t_create
+        extra = {}
         try:
             lin, ms, inner = [], [], problem.solve
 
@@ -89,7 +99,10 @@ def solve(msh, mode, monitor_file=None):
             problem.solve = counted
             with (c_stdout_to(monitor_file) if monitor_file else contextlib.nullcontext()):
                 hist = run_outer_loop(problem, sol, sol_k, alpha, 500, "double_exponential", 1e2, 1e-4)
-            u = sol.x.array[: msh.num_vertices].copy()
+            u = sol.x.array[: sol.function_space.block_size].copy()
+            if degree == 2:
+                problem.assemble_jacobian()
+                extra = dict(fallbacks=problem.p2_cycle_info()["fallbacks"], nw=int(len(problem.p2_wide_export()[0])))
         finally:
             problem.close()
     finally:
@@ -99,7 +112,8 @@ def solve(msh, mode, monitor_file=None):
     rec = dict(newton=[int(v) for v in hist["Newton steps"]], krylov_per_lvpp_solve=lin, ms_per_lvpp_solve=[round(v, 3) for v in ms],
                ms_per_lvpp_solve_mean=round(float(np.mean(ms)), 3), ms_first_solve=round(ms[0], 3),
                ms_per_lvpp_solve_mean_without_first=round(float(np.mean(ms[1:])), 3) if len(ms) > 1 else None,
-               ms_total=round(float(np.sum(ms)), 3), set_hierarchy_seconds=round(hier_s[0], 4) if hier_s else None)
+               ms_total=round(float(np.sum(ms)), 3), set_hierarchy_seconds=round(hier_s[0], 4) if hier_s else None,
+               create_seconds=round(t_create, 3), **extra)
     if monitor_file:
         steps = [int(m) for m in re.findall(r"KSP its (\d+)", pathlib.Path(monitor_file).read_text())]
         rec = dict(krylov_per_newton_step=steps, krylov_per_newton_step_range=[min(steps), max(steps)] if steps else None)
@@ -142,21 +156,26 @@ def kernel_times(trace_dir):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--levels", type=int, nargs="+", default=[3, 4, 5, 6])
-    ap.add_argument("--modes", nargs="+", default=["mg", "single", "lu"], choices=sorted(MODES))
+    ap.add_argument("--degree", type=int, default=1, choices=[1, 2])
+    ap.add_argument("--modes", nargs="+", default=None, choices=sorted(MODES), help="default: mg single lu; degree 2: mg lu auto")
     ap.add_argument("--h", type=float, default=0.1)
     ap.add_argument("--lu-max-level", type=int, default=5, help="largest L solved under pgx_lu")
     ap.add_argument("--single-max-level", type=int, default=5, help="largest L solved with the single-level smoother")
     ap.add_argument("--trace-level", type=int, default=None)
     ap.add_argument("--trace-timeout", type=float, default=300.0, help="seconds the traced child process may take")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "umg_disk_scaling.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/umg_disk_scaling.json; degree 2: profiles/p2_umg_disk_scaling.json")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    a.modes = a.modes or (["mg", "single", "lu"] if a.degree == 1 else ["mg", "lu", "auto"])
+    a.out = a.out or str(ROOT / "profiles" / ("umg_disk_scaling.json" if a.degree == 1 else "p2_umg_disk_scaling.json"))
+    if a.degree == 2 and (a.trace_level is not None or "single" in a.modes):
+        ap.error("--degree 2 has the modes mg, lu, auto and no kernel trace")
     from proximalgalerkin_amd import fem
 
     if a.child:  # under rocprofv3: one "mg" run of one mesh, nothing else
         solve(fem.create_disk(a.h, refinements=a.levels[0]), "mg")
         return
-    out = dict(h=a.h, settings="B: double_exponential, alpha_max 100, tol 1e-4; V(6,6), omega 0.75, 60 coarse sweeps", levels={})
+    out = dict(h=a.h, degree=a.degree, settings="B: double_exponential, alpha_max 100, tol 1e-4; V(6,6), omega 0.75, 60 coarse sweeps", levels={})
     warm = set()
     for L in a.levels:
         t0 = time.perf_counter()
@@ -171,15 +190,15 @@ def main():
                 continue
             try:
                 if mode not in warm:  # once per process and mode: code objects, first-use allocations
-                    solve(msh, mode)
+                    solve(msh, mode, degree=a.degree)
                     warm.add(mode)
                 t0 = time.perf_counter()
-                r, u = solve(msh, mode)
+                r, u = solve(msh, mode, degree=a.degree)
                 r["setup_and_solve_seconds"] = round(time.perf_counter() - t0, 2)
                 u_ref[mode] = u
                 if mode != "lu":
                     with tempfile.TemporaryDirectory() as tmp:
-                        r.update(solve(msh, mode, os.path.join(tmp, "monitor.txt"))[0])
+                        r.update(solve(msh, mode, os.path.join(tmp, "monitor.txt"), degree=a.degree)[0])
                 rec[mode] = r
                 print(f"  {mode}: Newton {r['newton']}, Krylov per Newton step {r.get('krylov_per_newton_step_range')}, "
                       f"ms per LVPP solve: mean {r['ms_per_lvpp_solve_mean']}, first {r['ms_first_solve']}, without the first "
@@ -188,7 +207,7 @@ def main():
                 rec[mode] = f"failed: {type(e).__name__}: {e}"
                 print(f"  {mode}: {rec[mode]}", flush=True)
         if "lu" in u_ref:
-            for mode in ("mg", "single"):
+            for mode in ("mg", "single", "auto"):
                 if mode in u_ref:
                     rec[f"rel_l2_u_{mode}_vs_lu"] = float(np.linalg.norm(u_ref[mode] - u_ref["lu"]) / np.linalg.norm(u_ref["lu"]))
         out["levels"][str(L)] = rec
