@@ -34,6 +34,10 @@ def main():
     ap.add_argument("--max_iter", type=int, default=500)  # compare_all.py:32
     ap.add_argument("--tol", type=float, default=1e-4)  # compare_all.py:31
     ap.add_argument("--first-order-max-iter", type=int, default=20000)
+    ap.add_argument("--pc-type", dest="pc_type", choices=["auto", "pgx_mg", "pgx_lu"], default="auto",
+                    help="preconditioner of the two proximal Galerkin solves: auto (sparse LU on a general mesh without a hierarchy), "
+                         "pgx_mg (on such a mesh of 2 000 vertices or more: the multilevel cycle over a hierarchy built from the "
+                         "matrix), pgx_lu")
     a = ap.parse_args()
     if a.infile:
         mesh = io.read_mesh(a.infile)
@@ -45,8 +49,9 @@ def main():
     problem = ObstacleProblem(S, M, f)
     x_g, it_g = galahad_solver(problem, np.zeros(len(f)), bounds, log_level=0, use_hessian=True, max_iter=a.max_iter, tol=a.tol,
                                coords=coords)
-    u1, it_p1 = solve_problem(mesh, 1, a.max_iter, "double_exponential", 1e2, a.tol, verbose=False)
-    u2, it_p2 = solve_problem(mesh, 2, a.max_iter, "double_exponential", 1e2, a.tol, verbose=False)
+    pc = None if a.pc_type == "auto" else a.pc_type
+    u1, it_p1 = solve_problem(mesh, 1, a.max_iter, "double_exponential", 1e2, a.tol, verbose=False, pc_type=pc)
+    u2, it_p2 = solve_problem(mesh, 2, a.max_iter, "double_exponential", 1e2, a.tol, verbose=False, pc_type=pc)
     x_f, it_f = galahad_solver(problem, np.zeros(len(f)), bounds, log_level=0, use_hessian=False, max_iter=a.first_order_max_iter,
                                tol=a.tol, coords=coords)
     u_vi, it_vi = vi_newton_solver(S, M @ f, bounds[0], bounds[1], coords=coords)

@@ -23,7 +23,7 @@ if __name__ == "__main__":
                              "gmsh script writes (obstacle_pg.py:276-280); HDF5 is not available offline")
     parser.add_argument("--disk", dest="disk_h", type=float, default=0.0,
                         help="mesh size of a unit-DISK mesh (the reference's own domain, generate_mesh_gmsh.py:23) instead of "
-                             "the square; general mesh -> sparse-LU preconditioner")
+                             "the square; general mesh -> sparse-LU preconditioner (see --pc-type)")
     parser.add_argument("--refinements", dest="refinements", type=int, default=0,
                         help="with --disk RES: refine that mesh this many times, new boundary vertices on the circle "
                              "(generate_mesh_gmsh.py:26-36: disk_L); the refined mesh carries its hierarchy, and from PGX_UMG_MIN "
@@ -38,6 +38,10 @@ if __name__ == "__main__":
     parser.add_argument("--alpha-max", "-a", dest="alpha_max", type=float, default=1e5, help="Maximum alpha")
     parser.add_argument("--tol", "-t", dest="tol_exit", type=float, default=1e-6,
                         help="Tolerance for exiting Newton iteration")
+    parser.add_argument("--pc-type", dest="pc_type", choices=["auto", "pgx_mg", "pgx_lu"], default="auto",
+                        help="preconditioner: auto (the default; on a general mesh without a hierarchy - a file read with -f, --disk "
+                             "without --refinements - the sparse LU), pgx_mg (on such a mesh of 2 000 vertices or more the multilevel "
+                             "cycle over a hierarchy built from the stiffness matrix; below, the single-level smoother), pgx_lu")
     args = parser.parse_args()
     if args.filename is not None:
         from proximalgalerkin_amd.io import read_mesh
@@ -50,7 +54,7 @@ if __name__ == "__main__":
                fem.create_rectangle(((-1.0, -1.0), (1.0, 1.0)), (args.N, args.N)))
     sol, newton_steps = solve_problem(msh, args.polynomial_order, args.maximum_number_of_outer_loop_iterations,
                                       args.alpha_scheme, args.alpha_max, args.tol_exit,
-                                      output_dir=Path.cwd() / "output")
+                                      output_dir=Path.cwd() / "output", pc_type=None if args.pc_type == "auto" else args.pc_type)
     print(f"total Newton steps: {newton_steps}")
     # fields for ParaView (the reference writes u and psi with VTXWriter, obstacle_pg.py:239-243)
     from proximalgalerkin_amd.io import write_vtu

@@ -70,8 +70,9 @@ typedef struct {
   const int32_t* cells;   /* [n_cells][3], vertex ids */
   /* >0 only for the right-diagonal structured triangulation with vertex v = j*(nx+1)+i and cells
    * (2q, 2q+1) = [v0,v1,v3],[v0,v2,v3] of square q = j*nx+i (dolfinx create_rectangle default).
-   * Enables the geometric multigrid preconditioner; 0 = general mesh: sparse LU or single-level smoother, and the
-   * multilevel cycle once pgx_set_hierarchy has attached the hierarchy of a refined mesh. */
+   * Enables the geometric multigrid preconditioner; 0 = general mesh.  A general mesh runs the multilevel cycle over a hierarchy
+   * that pgx_set_hierarchy attaches (a refined mesh brings its own) or that pgx_build_hierarchy builds from the stiffness matrix
+   * (any mesh, e.g. one read from a file); without either call it has the sparse LU and the single-level smoother. */
   int32_t structured_nx;
   int32_t structured_ny;
   /* degree 2 only (NULL / 0 for degree 1): dofs per field are [vertices | one per edge]; row c lists the 3
@@ -264,7 +265,35 @@ int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, int in_form
  * sparse-LU rescue of structured P2 after PGX_P2_FALLBACK_ITS iterations, and the LU below.  The coarsest level runs PGX_UMG_COARSE_SWEEPS (60)
  * smoother sweeps, in one launch where it fits the LDS of one workgroup (PGX_UMG_COARSE_LDS=0: as separate launches). */
 int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32_t* n_coarse, const int32_t* const* parents);
-/* Test hooks of that hierarchy, in the style of pgx_mg_level_export / pgx_vcycle_apply (whose preconditions and behaviour they leave
+/* ---- General meshes WITHOUT a refinement hierarchy: the hierarchy built from the matrix (csrc/pgx_amg.hip) ----
+ * A sibling of pgx_set_hierarchy for a mesh that has no `parents` arrays - one read from a file, an unrefined gmsh mesh.  Per transfer,
+ * from the unconstrained stiffness matrix K of the level and its Dirichlet mask:
+ *   strength    j is strong for i where a_ij < 0 and -a_ij >= theta max_k (-a_ik); the graph is symmetrised
+ *   C/F split   greedy maximal independent set over strong edges between vertices of one kind (Dirichlet - Dirichlet, interior -
+ *               interior), Dirichlet vertices first, each kind by ascending index; coarse vertices keep their order
+ *   P           direct interpolation (a Dirichlet row from Dirichlet C vertices only), one Jacobi step P <- P - diag(K)^-1 K P on the
+ *               interior F rows, entries below trunc x the row's largest magnitude dropped and the row rescaled to its sum
+ *   stopping    at <= min_coarse vertices, or before a step that would keep more than max_keep of the vertices
+ * theta < 0, trunc < 0, min_coarse <= 0, max_keep <= 0 take the defaults 0.01, 0.2, 60, 0.8; trunc must be > 0 (PGX_EINVAL otherwise).  The split and all patterns are host work;
+ * the values of P, the Galerkin products P^T K P, P^T M P (here, once) and P^T D P (every Jacobian fill), restriction and prolongation are
+ * fp64 gather kernels without atomics, bitwise reproducible.  The levels, the smoother, the coarsest level, the solver selection (PGX_UMG,
+ * PGX_UMG_MIN, PGX_UMG_MIN_P2, PGX_UMG_COARSE_SWEEPS, PGX_UMG_COARSE_LDS) and the role under a degree-2 handle are those of
+ * pgx_set_hierarchy above.  *n_levels (may be NULL): levels built, >= 2.  seconds (may be NULL): [0] the host pass, [1] device work
+ * and copies.
+ * Call order as pgx_set_hierarchy: after create, before the first Jacobian fill; one hierarchy per handle, attached or built (PGX_ESTATE
+ * otherwise).  PGX_EINVAL, with a message and nothing launched or changed: a structured, sharded or LU-distributed handle; a parameter
+ * out of range; a mesh of no more than min_coarse vertices, or one whose first step keeps more than max_keep of them. */
+int pgx_build_hierarchy(pgx_handle* h, double theta, double trunc, int32_t min_coarse, double max_keep, int32_t* n_levels, double* seconds);
+/* 1 where a front end should call pgx_build_hierarchy (with the defaults) by itself for a handle that is to run with snes option
+ * pc_type: a general, single, not LU-distributed handle without a hierarchy and before its first fill, pc_type 1 (the multigrid
+ * preconditioner asked for), from PGX_UMG_BUILD_MIN (2 000) vertices up - below, the single-level smoother such a handle always ran is
+ * kept.  pc_type 0 (auto) keeps the sparse LU on such meshes: 0. */
+int pgx_build_hierarchy_default(const pgx_handle* h, int pc_type);
+/* Test hook: transfer t of a built hierarchy (level t + 1 -> level t) as CSR; every array may be NULL.  PGX_ESTATE without a built
+ * hierarchy, PGX_EINVAL: no such transfer.  numpy twin: tests/amg_reference.py. */
+int pgx_umg_transfer_export(pgx_handle* h, int t, int32_t* n_fine, int32_t* n_coarse, int32_t* nnz, int32_t* rowptr, int32_t* col, double* val);
+
+/* Test hooks of that hierarchy (attached or built), in the style of pgx_mg_level_export / pgx_vcycle_apply (whose preconditions and behaviour they leave
  * alone; numpy twin: tests/umg_reference.py).  Both need an attached hierarchy (PGX_UMG on), a filled Jacobian and the sparse LU not
  * active: PGX_ESTATE otherwise, nothing launched.
  * Level `level` (0 = the handle's own block CSR): *n vertices, *nnz entries, the CSR pattern, the stored unconstrained K, M, D values

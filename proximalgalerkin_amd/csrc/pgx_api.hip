@@ -1062,6 +1062,7 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_UMG")) h->umg_enable = atoi(e);
   if (const char* e = pgx_tune("PGX_UMG_MIN")) h->umg_min = atoi(e);
   if (const char* e = pgx_tune("PGX_UMG_MIN_P2")) h->umg_min_p2 = atoi(e);
+  if (const char* e = pgx_tune("PGX_UMG_BUILD_MIN")) h->umg_build_min = atoi(e);
   if (const char* e = pgx_tune("PGX_P2_PATCH_WIDE")) h->patch_wide = atoi(e);
   if (const char* e = pgx_tune("PGX_UMG_COARSE_SWEEPS")) h->umg_coarse_sweeps = std::max(1, atoi(e));
   if (const char* e = pgx_tune("PGX_UMG_COARSE_LDS")) h->umg_coarse_lds = atoi(e);
@@ -1582,7 +1583,10 @@ static int jacobian_dev(pgx_handle* h, const double* x, bool have_d = false) {
   for (size_t l = 1; umg_on(h) && !h->umg_idle && l < h->umg.size(); ++l) {
     PhaseTimer t(h, 2);
     const UmgLevel& C = h->umg[l];
-    pgxk_umg_rap(h->st, C.nnz, C.plan_lpe, C.plan_ptr, C.plan_src, h->umg[l - 1].D, C.D);
+    if (C.P_val)  // a built hierarchy (pgx_build_hierarchy): general weights, two gather stages
+      pgxk_amg_rap(h->st, C, h->umg[l - 1].D, C.D);
+    else
+      pgxk_umg_rap(h->st, C.nnz, C.plan_lpe, C.plan_ptr, C.plan_src, h->umg[l - 1].D, C.D);
   }
   h->jac_valid = true;
   h->jac_ever = true;
@@ -1783,9 +1787,15 @@ static void vcycle_umg(pgx_handle* h, int l, const double* bu, const double* bp,
   for (int s = 0; s < nu; ++s) sweep(s == 0);
   pgxk_bspmv(h->st, 1, L.n, L.rowptr, L.colm, L.K, L.M, L.D, h->alpha, cu, cp, bu, bp, 0.0, h->xcd_remap, L.ru, L.rp);
   const UmgLevel& C = h->umg[l + 1];
-  pgxk_umg_resid_restrict(h->st, C.n, C.ch_ptr, C.ch_idx, C.mask, L.ru, L.rp, C.bu, C.bp);
+  if (C.P_val)  // a built hierarchy: the transfers with general weights (pgx_amg.hip)
+    pgxk_amg_resid_restrict(h->st, C, L.ru, L.rp);
+  else
+    pgxk_umg_resid_restrict(h->st, C.n, C.ch_ptr, C.ch_idx, C.mask, L.ru, L.rp, C.bu, C.bp);
   vcycle_umg(h, l + 1, C.bu, C.bp, C.xu, C.xp, nu, omega);
-  pgxk_umg_prolong_add(h->st, L.n, C.parents, C.xu, C.xp, (double*)cu, (double*)cp);
+  if (C.P_val)
+    pgxk_amg_prolong_add(h->st, L.n, C, (double*)cu, (double*)cp);
+  else
+    pgxk_umg_prolong_add(h->st, L.n, C.parents, C.xu, C.xp, (double*)cu, (double*)cp);
   for (int s = 0; s < nu; ++s) sweep(0);
 }
 
@@ -2788,13 +2798,6 @@ extern "C" int pgx_vcycle_apply(pgx_handle* h, int level, int nu, double omega, 
 // entry index), and per coarse vertex its child list (P^T as CSR, children in ascending order: the vertex itself first).  Then K and
 // M of every coarse level, once; D follows on every Jacobian fill (jacobian_dev).
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-static int umg_upload(pgx_handle* h, T** dst, const std::vector<T>& src) {
-  DALLOC(*dst, src.size());
-  if (!src.empty()) HIPCHK(hipMemcpyAsync(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, h->st));
-  return PGX_OK;
-}
-
 extern "C" int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32_t* n_coarse, const int32_t* const* parents) {
   NEED(h);
   if (!h->umg.empty()) {
@@ -2847,24 +2850,9 @@ extern "C" int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32
     }
   }
   std::vector<UmgLevel> lv(n_transfers + 1);
-  {  // level 0 = the handle's P1 block CSR on its vertices; under a degree-2 handle Dv is T^T D_P2 T, refreshed by every fill
-    UmgLevel& L0 = lv[0];
-    L0.n = h->n;
-    L0.nnz = h->nnz;
-    L0.rowptr = h->rowptr;
-    L0.colm = h->colm;
-    L0.K = h->Kv;
-    L0.M = h->Mv;
-    L0.D = h->Dv;
-    L0.mask = h->mask;
-    L0.xu2 = h->tmp_u;
-    L0.xp2 = h->tmp_p;
-    L0.ru = h->res_u;
-    L0.rp = h->res_p;
-    L0.h_rowptr = h->h_rowptr;
-    L0.h_col = h->h_col;
-    L0.h_mask.resize(h->n);
-    HIPCHK(hipMemcpy(L0.h_mask.data(), h->mask, h->n, hipMemcpyDeviceToHost));
+  {
+    const int rc = umg_level0(h, lv[0]);
+    if (rc) return rc;
   }
   for (int t = 0; t < n_transfers; ++t) {
     const UmgLevel& F = lv[t];
@@ -2956,17 +2944,14 @@ extern "C" int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32
   }
   HIPCHK(hipStreamSynchronize(h->st));
   HIPCHK(hipGetLastError());
-  // the coarsest level in one launch: only where this handle's device accepts the kernel's LDS limit (set per device, here)
-  h->umg_coarse_fits = pgxk_umg_coarse_prepare(lv.back().n, lv.back().nnz);
-  h->umg = std::move(lv);
-  h->jac_valid = false;
+  umg_install(h, std::move(lv));
   return PGX_OK;
 }
 
 // Test hooks of that hierarchy (include/pgx.h): copies of what a level stores, and one cycle through the functions the solver calls.
 static int umg_hook_ready(pgx_handle* h, const char* who) {
   if (!h->jac_valid || !umg_on(h) || h->lu_active) {
-    h->err = std::string(who) + " needs a handle with an attached hierarchy (pgx_set_hierarchy, PGX_UMG on), a filled Jacobian and the sparse LU not active";
+    h->err = std::string(who) + " needs a handle with an attached or built hierarchy (pgx_set_hierarchy, pgx_build_hierarchy; PGX_UMG on), a filled Jacobian and the sparse LU not active";
     return PGX_ESTATE;
   }
   return PGX_OK;

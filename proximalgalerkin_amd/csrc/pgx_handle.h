@@ -50,7 +50,21 @@ struct UmgLevel {
   double *bu = nullptr, *bp = nullptr, *xu = nullptr, *xp = nullptr, *xu2 = nullptr, *xp2 = nullptr, *ru = nullptr, *rp = nullptr;
   std::vector<int32_t> h_rowptr, h_col;
   std::vector<uint8_t> h_mask;
+  // transfer of a BUILT hierarchy (pgx_build_hierarchy; kernels: pgx_amg.hip) instead of `parents`: P as CSR over the n_f fine rows
+  // with general weights (P_val != nullptr marks such a level); the child lists above carry the P entry of every child in ch_q.
+  // Galerkin product in two gather stages: T = A P (nnz_t entries; per entry the pairs fine entry t_a, P entry t_p), then P^T T (per
+  // entry of this level the pairs P entry g_p, T entry g_t).  The plans hold indices only, the weights are read from P_val.
+  int nnz_p = 0, nnz_t = 0;
+  int32_t *P_ptr = nullptr, *P_col = nullptr, *ch_q = nullptr;
+  int32_t *t_ptr = nullptr, *t_a = nullptr, *t_p = nullptr, *g_ptr = nullptr, *g_p = nullptr, *g_t = nullptr;
+  double *P_val = nullptr, *T = nullptr;
+  std::vector<int32_t> h_P_ptr, h_P_col;
 };
+// defaults of pgx_build_hierarchy ("Built hierarchies": the variants measured on the numpy twin)
+#define PGX_AMG_THETA 0.01
+#define PGX_AMG_TRUNC 0.2
+#define PGX_AMG_MIN_COARSE 60
+#define PGX_AMG_MAX_KEEP 0.8
 
 struct pgx_handle {
   int device = 0;
@@ -189,6 +203,12 @@ struct pgx_handle {
   int umg_min_p2 = 20000;      // PGX_UMG_MIN_P2: the same for a degree-2 handle (the patch cycle over this hierarchy first, the sparse LU as
                                // its rescue).  Handle creation plus all solves of a settings-B run: 0.18 against 0.44 s at 20 381 vertices,
                                // the smallest size measured, 0.39 / 1.24 s at 81 017, 1.32 / 4.29 s at 323 057 (profiles/p2_umg_disk_scaling.json)
+  int umg_build_min = 2000;    // PGX_UMG_BUILD_MIN: a handle WITHOUT a hierarchy asked for the multigrid preconditioner (pc_type 1) builds
+                               // one from this many vertices up (pgx_build_hierarchy_default).  Below, the single-level smoother such a
+                               // handle always ran still converges (469 vertices: tests/golden/umg_d34_parent.npz).  That smoother needs
+                               // twice the cycle's Krylov iterations at 1 319 vertices, runs into the iteration cap at 20 381 and
+                               // fails to converge from 81 017
+                               // (profiles/umg_disk_scaling.json).  Not a measured crossover
   int umg_coarse_sweeps = 60;  // PGX_UMG_COARSE_SWEEPS
   int umg_coarse_lds = 1;      // PGX_UMG_COARSE_LDS=0: the coarsest level as repeated k_bspmv<2> launches although it fits one workgroup's LDS
   bool umg_coarse_fits = false;  // the coarsest level fits k_umg_coarse and this handle's device took its LDS limit (pgx_set_hierarchy)
@@ -268,6 +288,43 @@ static int dalloc(pgx_handle* h, T** p, size_t count) {
     if (rc_) return rc_;                         \
   } while (0)
 
+// a host vector into device memory the handle owns (the hierarchies of general meshes: pgx_set_hierarchy, pgx_build_hierarchy)
+template <typename T>
+static int umg_upload(pgx_handle* h, T** dst, const std::vector<T>& src) {
+  DALLOC(*dst, src.size());
+  if (!src.empty()) HIPCHK(hipMemcpyAsync(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, h->st));
+  return PGX_OK;
+}
+
+// Level 0 of a general-mesh hierarchy, attached or built: the handle's P1 block CSR on its vertices and its level-0 scratch; under a
+// degree-2 handle Dv is T^T D_P2 T, refreshed by every fill.
+static inline int umg_level0(pgx_handle* h, UmgLevel& L0) {
+  L0.n = h->n;
+  L0.nnz = h->nnz;
+  L0.rowptr = h->rowptr;
+  L0.colm = h->colm;
+  L0.K = h->Kv;
+  L0.M = h->Mv;
+  L0.D = h->Dv;
+  L0.mask = h->mask;
+  L0.xu2 = h->tmp_u;
+  L0.xp2 = h->tmp_p;
+  L0.ru = h->res_u;
+  L0.rp = h->res_p;
+  L0.h_rowptr = h->h_rowptr;
+  L0.h_col = h->h_col;
+  L0.h_mask.resize(h->n);
+  HIPCHK(hipMemcpy(L0.h_mask.data(), h->mask, h->n, hipMemcpyDeviceToHost));
+  return PGX_OK;
+}
+// The finished levels become the handle's hierarchy.  The coarsest level in one launch: only where this handle's device accepts the
+// kernel's LDS limit (set per device, here).
+static inline void umg_install(pgx_handle* h, std::vector<UmgLevel>&& lv) {
+  h->umg_coarse_fits = pgxk_umg_coarse_prepare(lv.back().n, lv.back().nnz);
+  h->umg = std::move(lv);
+  h->jac_valid = false;
+}
+
 struct PhaseTimer {
   pgx_handle* h;
   int slot;
@@ -300,6 +357,11 @@ void spmv_dev(pgx_handle* h, const double* x, double* y);                      /
 void gather_owned(pgx_handle* h, const double* loc, double* cmp);              // sharded: local vector -> owned-compact
 int allreduce_dev(pgx_handle* h, double* dev, size_t n);                       // sharded: sum over the ranks, on the stream
 bool f32_cycle_ok(const pgx_handle* h, int l, int nu);                         // level l enters the single-precision cycle
+
+// ---- pgx_amg.hip: the transfers of a built hierarchy (general weights), onto level C from the level above it ----
+void pgxk_amg_rap(hipStream_t st, const UmgLevel& C, const double* src, double* dst);  // dst = P^T (src) P through C.T
+void pgxk_amg_resid_restrict(hipStream_t st, const UmgLevel& C, const double* ru, const double* rp);  // (C.bu, C.bp) = P^T (ru, rp)
+void pgxk_amg_prolong_add(hipStream_t st, int n_f, const UmgLevel& C, double* xu, double* xp);         // (xu, xp) += P (C.xu, C.xp)
 
 // ---- pgx_krylov.hip ----
 int fgmres(pgx_handle* h, const double* b, double* x, const pgx_snes_opts* o, int* its_out, double* relres, double bnorm_known = -1.0,

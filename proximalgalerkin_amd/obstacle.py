@@ -37,8 +37,12 @@ COLUMNS = ["Energy", "Complementarity", "Feasibility", "Dual Feasibility", "Newt
 
 
 def setup_problem(msh: fem.Mesh, polynomial_order: int = 1, petsc_options: dict | None = None, device: int = 0,
-                  phi=phi_set, lu_comm=None, quadrature_degree: int = 6, quadrature_scheme: str | None = None):
+                  phi=phi_set, lu_comm=None, quadrature_degree: int = 6, quadrature_scheme: str | None = None,
+                  pc_type: str | None = None):
     """Everything obstacle_pg.py does before the loop (:66-152). Returns (problem, sol, sol_k, alpha).
+    pc_type: with petsc_options None, the preconditioner of the reference's option set instead of its "lu" (the automatic choice):
+    "pgx_mg" asks for the multigrid cycle - on a general mesh without a hierarchy, of 2 000 vertices or more, over one built from the
+    matrix - "pgx_lu" for the sparse LU.
     quadrature_degree: 6 is the reference's (:106); 1 selects the vertex rule (mass lumping), with which the system is the
     finite-difference one of obstacle_finite_difference.jl (tests/test_gpu_fd_pin.py).  quadrature_scheme names a table of
     tables/quadrature.json explicitly ("tri_deg6_12_b": the second admissible 12-point degree-6 rule)."""
@@ -69,6 +73,8 @@ def setup_problem(msh: fem.Mesh, polynomial_order: int = 1, petsc_options: dict 
             "snes_rtol": 1e-6,
             "snes_max_it": 100,
         }
+        if pc_type is not None:
+            petsc_options["pc_type"] = pc_type
     problem = NonlinearProblem(F, u=sol, bcs=[bcs], J=J, petsc_options=petsc_options,
                                petsc_options_prefix="obstacle_", device=device, lu_comm=lu_comm)  # :140-142
     return problem, sol, sol_k, alpha
@@ -132,9 +138,10 @@ def run_outer_loop(problem, sol, sol_k, alpha, maximum_number_of_outer_loop_iter
 
 
 def solve_problem(msh, polynomial_order, maximum_number_of_outer_loop_iterations, alpha_scheme, alpha_max, tol_exit,
-                  output_dir: Path | None = None, device_resident=True, verbose=True, return_history=False, device=0):
-    """Reference signature (obstacle_pg.py:53-60) with the XDMF file name replaced by a Mesh."""
-    problem, sol, sol_k, alpha = setup_problem(msh, polynomial_order, device=device)
+                  output_dir: Path | None = None, device_resident=True, verbose=True, return_history=False, device=0,
+                  pc_type: str | None = None):
+    """Reference signature (obstacle_pg.py:53-60) with the XDMF file name replaced by a Mesh; pc_type as in setup_problem."""
+    problem, sol, sol_k, alpha = setup_problem(msh, polynomial_order, device=device, pc_type=pc_type)
     t0 = time.perf_counter()
     hist = run_outer_loop(problem, sol, sol_k, alpha, maximum_number_of_outer_loop_iterations, alpha_scheme,
                           alpha_max, tol_exit, device_resident, verbose)

@@ -225,11 +225,23 @@ class NonlinearProblem:
         self._h = h
         self.ndofs = V.num_dofs
         # a refined general mesh (fem.refine) hands its nested P1 hierarchy to the handle: FGMRES can then precondition with the
-        # multilevel cycle (degree 1) or with the two-level patch cycle over it (degree 2; include/pgx.h: pgx_set_hierarchy).  Meshes
-        # without one - files, structured grids - are solved as before
+        # multilevel cycle (degree 1) or with the two-level patch cycle over it (degree 2; include/pgx.h: pgx_set_hierarchy).  A
+        # general mesh without one - read from a file, an unrefined gmsh mesh - gets a hierarchy built from its stiffness matrix where
+        # the options ask for the multigrid preconditioner ("pgx_mg") and the mesh is large enough for it to pay
+        # (pgx_build_hierarchy_default); structured grids have their own
         hier = getattr(mesh, "hierarchy", None)
+        self._umg_levels = 0
         if hier and V.degree in (1, 2) and part is None and lu_comm is None and not mesh.structured:
             self.set_hierarchy(hier)
+        elif V.degree in (1, 2) and lib.pgx_build_hierarchy_default(self._h, int(self._opts.pc_type)):
+            try:
+                self.build_hierarchy()
+            except _lib.PgxError as e:
+                if getattr(e, "code", 0) != -1:  # not PGX_EINVAL, i.e. anything but a refusal: no half-made handle is left behind
+                    self.close()
+                    raise
+                # refused with nothing changed (e.g. a matrix whose first step keeps too many vertices): the handle runs the
+                # single-level smoother it ran before this call existed
         F.sol.x._binding = (self, "state")
         F.sol_k.x._binding = (self, "prev")
         F.sol.x._dev_valid = F.sol_k.x._dev_valid = False
@@ -428,6 +440,32 @@ class NonlinearProblem:
         self._check_code(self._lib.pgx_set_hierarchy(self._h, len(par), _lib.iptr(nc), ptrs), "pgx_set_hierarchy")
         self._umg_levels = len(par) + 1
 
+    def build_hierarchy(self, theta=None, trunc=None, min_coarse=None, max_keep=None):
+        """Build the multigrid hierarchy of a general mesh that has none from the stiffness matrix (include/pgx.h: pgx_build_hierarchy;
+        None: the library's defaults).  Before the first Jacobian fill, once, instead of set_hierarchy.  Returns the number of levels;
+        build_seconds holds (host pass, device work and copies)."""
+        nl, sec = C.c_int32(0), np.zeros(2)
+        self._check_code(self._lib.pgx_build_hierarchy(self._h, -1.0 if theta is None else float(theta), -1.0 if trunc is None else float(trunc),
+                                                       0 if min_coarse is None else int(min_coarse),
+                                                       0.0 if max_keep is None else float(max_keep), C.byref(nl), _lib.dptr(sec)),
+                         "pgx_build_hierarchy")
+        self._umg_levels, self.build_seconds = int(nl.value), (float(sec[0]), float(sec[1]))
+        return self._umg_levels
+
+    def umg_transfer_export(self, t):
+        """Transfer t of a built hierarchy, level t + 1 -> level t, as a scipy CSR matrix (include/pgx.h: pgx_umg_transfer_export; a
+        test hook)."""
+        import scipy.sparse as sp
+
+        nf, nc, nnz = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        lib = self._lib
+        self._check_code(lib.pgx_umg_transfer_export(self._h, int(t), C.byref(nf), C.byref(nc), C.byref(nnz), None, None, None),
+                         "pgx_umg_transfer_export")
+        rowptr, col, val = np.empty(nf.value + 1, dtype=np.int32), np.empty(nnz.value, dtype=np.int32), np.empty(nnz.value)
+        self._check_code(lib.pgx_umg_transfer_export(self._h, int(t), None, None, None, _lib.iptr(rowptr), _lib.iptr(col), _lib.dptr(val)),
+                         "pgx_umg_transfer_export")
+        return sp.csr_matrix((val, col, rowptr), shape=(nf.value, nc.value))
+
     def umg_level_export(self, level):
         """What level `level` of the general-mesh hierarchy stores after the last assemble_jacobian (include/pgx.h:
         pgx_umg_level_export; a test hook): dict(n, rowptr, col, K, M, D, mask)."""
@@ -444,7 +482,8 @@ class NonlinearProblem:
         return dict(n=n.value, rowptr=rowptr, col=col, K=K, M=M, D=D, mask=mask.astype(bool))
 
     def umg_levels(self):
-        """Number of levels pgx_umg_level_export serves: the transfers handed to set_hierarchy, plus one.  Raises as that hook does
+        """Number of levels pgx_umg_level_export serves: the transfers handed to set_hierarchy, plus one, or what build_hierarchy
+        built.  Raises as that hook does
         where it would not serve level 0 (no hierarchy, no filled Jacobian)."""
         n = C.c_int32(0)
         self._check_code(self._lib.pgx_umg_level_export(self._h, 0, C.byref(n), None, None, None, None, None, None, None),

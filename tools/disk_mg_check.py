@@ -3,6 +3,7 @@
 
     python3 tools/disk_mg_check.py [--levels 3 4 5 6] [--modes mg single lu] [--trace-level 5] [--out profiles/umg_disk_scaling.json]
     python3 tools/disk_mg_check.py --degree 2 [--levels 3 4 5] [--modes mg lu auto]          (-> profiles/p2_umg_disk_scaling.json)
+    python3 tools/disk_mg_check.py --built [--levels 3 4]                                     (-> profiles/amg_disk_scaling.json)
 
 For every L: create_disk(0.1, refinements=L) - the construction of generate_mesh_gmsh.py's disk_L - solved with settings B
 (double_exponential, alpha_max 100, tol 1e-4) under "pgx_mg" (the cycle), "pgx_mg" with PGX_UMG=0 (the single-level smoother) and
@@ -20,7 +21,15 @@ the Krylov iteration cap on the large meshes) is recorded with its message.  Nee
 LU, "auto" pc_type auto forced onto the cycle at every size (PGX_UMG_MIN_P2=0): the cycle first, the sparse LU for a Newton solve in
 which it stagnates.  Recorded in addition: create_seconds (the handle, pgx_set_hierarchy included), fallbacks (Newton solves rescued
 by the LU) and nw (wide stars).  setup_and_solve_seconds - handle creation plus every solve, rescues included - of "auto" against
-"lu" is what PGX_UMG_MIN_P2's default is taken from."""
+"lu" is what PGX_UMG_MIN_P2's default is taken from.
+
+--built: the hierarchy built from the matrix (pgx_build_hierarchy) on meshes that carry none.  Per L three meshes: "attached" - the
+refined disk with its hierarchy, the comparator; "renumbered" - the same mesh with its vertices renumbered by a fixed random permutation
+and the hierarchy stripped; "unrefined" - create_disk(h / 2^L), a mesh of about as many vertices that no refinement produced.  The last
+two run "built" ("pgx_mg"; the constructor builds the hierarchy, PGX_UMG_BUILD_MIN=0) and "lu".  Recorded in addition:
+build_hierarchy_seconds = (host pass, device work and copies) of pgx_build_hierarchy and the vertices per built level.  Each mode
+is warmed by ONE untimed run on the first mesh it meets (code objects loaded), not once per mesh; one timed run per entry.  The section
+"twin" of the output file is kept as it is (CPU figures of tests/amg_reference.py)."""
 import argparse
 import contextlib
 import csv
@@ -41,7 +50,7 @@ ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 BASE = {"ksp_type": "preonly", "ksp_error_if_not_converged": True, "snes_error_if_not_converged": True, "snes_linesearch_type": "none",
         "snes_rtol": 1e-6, "snes_max_it": 100}
-MODES = {"mg": ("pgx_mg", {}), "single": ("pgx_mg", {"PGX_UMG": 0}), "lu": ("pgx_lu", {}), "auto": ("lu", {"PGX_UMG_MIN_P2": 0})}
+MODES = {"built": ("pgx_mg", {"PGX_UMG_BUILD_MIN": 0}), "mg": ("pgx_mg", {}), "single": ("pgx_mg", {"PGX_UMG": 0}), "lu": ("pgx_lu", {}), "auto": ("lu", {"PGX_UMG_MIN_P2": 0})}
 
 
 @contextlib.contextmanager
@@ -86,6 +95,8 @@ def solve(msh, mode, monitor_file=None, degree=1):
         problem, sol, sol_k, alpha = setup_problem(msh, degree, petsc_options=opts)
         t_create = time.perf_counter() - t_create
         extra = {}
+        if getattr(problem, "build_seconds", None):  # the constructor built the hierarchy (pgx_build_hierarchy)
+            extra = dict(build_hierarchy_seconds=[round(v, 4) for v in problem.build_seconds])
         try:
             lin, ms, inner = [], [], problem.solve
 
@@ -100,9 +111,12 @@ def solve(msh, mode, monitor_file=None, degree=1):
             with (c_stdout_to(monitor_file) if monitor_file else contextlib.nullcontext()):
                 hist = run_outer_loop(problem, sol, sol_k, alpha, 500, "double_exponential", 1e2, 1e-4)
             u = sol.x.array[: sol.function_space.block_size].copy()
+            if "build_hierarchy_seconds" in extra:
+                problem.assemble_jacobian()
+                extra["built_levels"] = [problem.umg_level_export(l)["n"] for l in range(problem.umg_levels())]
             if degree == 2:
                 problem.assemble_jacobian()
-                extra = dict(fallbacks=problem.p2_cycle_info()["fallbacks"], nw=int(len(problem.p2_wide_export()[0])))
+                extra.update(fallbacks=problem.p2_cycle_info()["fallbacks"], nw=int(len(problem.p2_wide_export()[0])))
         finally:
             problem.close()
     finally:
@@ -153,8 +167,55 @@ def kernel_times(trace_dir):
                  us_max=round(float(np.max(v)), 2)) for (k, g), v in sorted(acc.items(), key=lambda kv: (kv[0][0], -kv[0][1]))]
 
 
+def main_built(a):
+    from proximalgalerkin_amd import fem
+    from tests.amg_reference import permuted as renumbered  # fixed random permutation of the vertex numbers, hierarchy stripped
+
+    path = pathlib.Path(a.out or str(ROOT / "profiles" / "amg_disk_scaling.json"))
+    out = json.loads(path.read_text()) if path.exists() else {}
+    out.update(h=a.h, settings="B: double_exponential, alpha_max 100, tol 1e-4; V(6,6), omega 0.75, 60 coarse sweeps; one timed run per entry; "
+               "each mode is run once untimed on the first mesh it meets, not once per mesh, so a first-solve figure still carries what is "
+               "first-use per mesh size", device={})
+    warm = set()
+    for L in a.levels:
+        refined = fem.create_disk(a.h, refinements=L)
+        meshes = {"attached": (refined, ["mg"]), "renumbered": (renumbered(refined), ["built", "lu"]),
+                  "unrefined": (fem.create_disk(a.h / 2 ** L), ["built", "lu"])}
+        rec = {}
+        for tag, (msh, modes) in meshes.items():
+            rec[tag] = dict(vertices=int(msh.num_vertices))
+            u_ref = {}
+            for mode in modes:
+                if mode == "lu" and L > a.lu_max_level:
+                    rec[tag][mode] = "not run at this size"
+                    continue
+                try:
+                    if mode not in warm:
+                        solve(msh, mode)
+                        warm.add(mode)
+                    t0 = time.perf_counter()
+                    r, u_ref[mode] = solve(msh, mode)
+                    r["setup_and_solve_seconds"] = round(time.perf_counter() - t0, 2)
+                    if mode != "lu":
+                        with tempfile.TemporaryDirectory() as tmp:
+                            r.update(solve(msh, mode, os.path.join(tmp, "monitor.txt"))[0])
+                        r["krylov_per_newton_step_mean"] = round(float(np.mean(r["krylov_per_newton_step"])), 2)
+                    rec[tag][mode] = r
+                    print(f"L={L} {tag} {msh.num_vertices} {mode}: Newton {r['newton']}, Krylov per Newton step mean {r.get('krylov_per_newton_step_mean')}, "
+                          f"ms per LVPP solve without the first {r['ms_per_lvpp_solve_mean_without_first']}, build {r.get('build_hierarchy_seconds')} s, "
+                          f"levels {r.get('built_levels')}", flush=True)
+                except Exception as e:
+                    rec[tag][mode] = f"failed: {type(e).__name__}: {e}"
+                    print(f"L={L} {tag} {mode}: {rec[tag][mode]}", flush=True)
+            if "lu" in u_ref and "built" in u_ref:
+                rec[tag]["rel_l2_u_built_vs_lu"] = float(np.linalg.norm(u_ref["built"] - u_ref["lu"]) / np.linalg.norm(u_ref["lu"]))
+        out["device"][str(L)] = rec
+        path.write_text(json.dumps(out, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--built", action="store_true", help="meshes without a hierarchy: the hierarchy built from the matrix (-> profiles/amg_disk_scaling.json)")
     ap.add_argument("--levels", type=int, nargs="+", default=[3, 4, 5, 6])
     ap.add_argument("--degree", type=int, default=1, choices=[1, 2])
     ap.add_argument("--modes", nargs="+", default=None, choices=sorted(MODES), help="default: mg single lu; degree 2: mg lu auto")
@@ -166,6 +227,10 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/umg_disk_scaling.json; degree 2: profiles/p2_umg_disk_scaling.json")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.built:
+        if a.degree != 1 or a.trace_level is not None:
+            ap.error("--built runs degree 1 without a kernel trace")
+        return main_built(a)
     a.modes = a.modes or (["mg", "single", "lu"] if a.degree == 1 else ["mg", "lu", "auto"])
     a.out = a.out or str(ROOT / "profiles" / ("umg_disk_scaling.json" if a.degree == 1 else "p2_umg_disk_scaling.json"))
     if a.degree == 2 and (a.trace_level is not None or "single" in a.modes):
