@@ -284,6 +284,18 @@ int pgx_set_hierarchy(pgx_handle* h, int32_t n_transfers, const int32_t* n_coars
  * otherwise).  PGX_EINVAL, with a message and nothing launched or changed: a structured, sharded or LU-distributed handle; a parameter
  * out of range; a mesh of no more than min_coarse vertices, or one whose first step keeps more than max_keep of them. */
 int pgx_build_hierarchy(pgx_handle* h, double theta, double trunc, int32_t min_coarse, double max_keep, int32_t* n_levels, double* seconds);
+/* Where the split and the patterns of pgx_build_hierarchy are computed: on the device (csrc/pgx_amg_build.hip; the default), or, with
+ * the tuning key PGX_AMG_BUILD=0 (read when the handle is created), in the serial host pass that did it before.  Both build bitwise the
+ * same hierarchy - split, numbering, patterns, the order inside every plan row, hence P, K, M, D of every level - and refuse the same
+ * inputs with the same messages (a mesh with a row without its diagonal AND a plan beyond int32 gets the first of these from the
+ * device pass, whichever row order meets first from the host pass); what the text above calls host work is device work on the default
+ * path, where seconds[1] is the time the host waited for the device or copied (the reads that end the split and size the arrays, the
+ * downloads of the mirrors) and seconds[0] everything else it did: launches, allocating and freeing device memory, bookkeeping.  The device split runs as launches that each decide every vertex whose lower-numbered strong
+ * neighbours are decided, until a counter read every 16 launches shows none left (PGX_AMG_SPLIT_BATCH, for tests, lowers the 16).
+ * pgx_amg_build_info: *mode = 1 device pass, 0 host pass; *n_transfers = levels - 1; split_launches[t] = launches of the split of
+ * transfer t (device pass: >= 1 and <= the vertices of level t; host pass: 0).  Every pointer may be NULL.  PGX_ESTATE on a handle
+ * without a built hierarchy. */
+int pgx_amg_build_info(pgx_handle* h, int32_t* mode, int32_t* n_transfers, int32_t* split_launches);
 /* 1 where a front end should call pgx_build_hierarchy (with the defaults) by itself for a handle that is to run with snes option
  * pc_type: a general, single, not LU-distributed handle without a hierarchy and before its first fill, pc_type 1 (the multigrid
  * preconditioner asked for), from PGX_UMG_BUILD_MIN (2 000) vertices up - below, the single-level smoother such a handle always ran is

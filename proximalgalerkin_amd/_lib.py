@@ -373,6 +373,7 @@ SYMBOLS = [
     ("pgx_set_hierarchy", C.c_int, [_H, C.c_int32, c_int32_p, C.POINTER(c_int32_p)]),
     ("pgx_build_hierarchy", C.c_int, [_H, C.c_double, C.c_double, C.c_int32, C.c_double, c_int32_p, c_double_p]),
     ("pgx_build_hierarchy_default", C.c_int, [_H, C.c_int]),
+    ("pgx_amg_build_info", C.c_int, [_H, c_int32_p, c_int32_p, c_int32_p]),
     ("pgx_umg_transfer_export", C.c_int, [_H, C.c_int, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_double_p]),
     ("pgx_umg_level_export", C.c_int,
      [_H, C.c_int, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_uint8)]),

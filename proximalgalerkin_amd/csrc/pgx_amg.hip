@@ -1,9 +1,10 @@
 // Multigrid on general P1 meshes that come without a refinement hierarchy (include/pgx.h: pgx_build_hierarchy; DESIGN.md section 3,
 // "Built hierarchies").  The hierarchy is built from the handle's own stiffness matrix: per transfer a coarse/fine split on the
 // strength graph and a CSR prolongation P with general weights (direct interpolation, one Jacobi step on the interior F rows,
-// truncation).  The split and every pattern are host work at setup, as in pgx_set_hierarchy; the levels are the block-CSR levels of
-// pgx_umg.hip and run its cycle (k_bspmv smoother and residual, k_umg_coarse).  This file holds the host pass and what the general
-// weights need on the device:
+// truncation).  The split and every pattern are computed on the device by default (pgx_amg_build.hip); the host pass below, which did
+// that work before, stays as the comparator behind the tuning key PGX_AMG_BUILD=0 and builds bitwise the same hierarchy.  The levels
+// are the block-CSR levels of pgx_umg.hip and run its cycle (k_bspmv smoother and residual, k_umg_coarse).  This file holds the host
+// pass and what the general weights need on the device:
 //   k_amg_direct          values of the direct interpolation from the fine K
 //   k_amg_pvalues         the Jacobi step on the interior F rows, truncation and rescale; other rows copy the direct values
 //   k_amg_gather2         dst[e] = sum over the plan row of e of a[ia] * b[ib]: both stages of the Galerkin product, T = A P entry by
@@ -154,6 +155,15 @@ void pgxk_amg_prolong_add(hipStream_t st, int n_f, const UmgLevel& C, double* xu
   hipLaunchKernelGGL(k_amg_prolong_add, amg_grid(n_f), dim3(PGX_BLOCK), 0, st, n_f, C.P_ptr, C.P_col, C.P_val, C.xu, C.xp, xu, xp);
 }
 
+void pgxk_amg_direct(hipStream_t st, int n, const int32_t* ptr, const int32_t* src, const double* K, double* val) {
+  hipLaunchKernelGGL(k_amg_direct, amg_grid(n), dim3(PGX_BLOCK), 0, st, n, ptr, src, K, val);
+}
+
+void pgxk_amg_pvalues(hipStream_t st, int n, const int32_t* fptr, const int32_t* own, const int32_t* pptr, const int32_t* pa, const int32_t* pb,
+                      const int32_t* diag, const double* K, const double* p0, double trunc, double* val) {
+  hipLaunchKernelGGL(k_amg_pvalues, amg_grid(n), dim3(PGX_BLOCK), 0, st, n, fptr, own, pptr, pa, pb, diag, K, p0, trunc, val);
+}
+
 // ---- host pass -----------------------------------------------------------------------------------------------------------------
 namespace {
 struct DevTmp {  // device scratch of the setup, released when the transfer is done
@@ -228,6 +238,7 @@ extern "C" int pgx_build_hierarchy(pgx_handle* h, double theta, double trunc, in
     h->err = "pgx_build_hierarchy: the mesh has no more than min_coarse vertices, there is nothing to coarsen";
     return PGX_EINVAL;
   }
+  if (h->amg_build) return pgx_amg_build_device(h, theta, trunc, min_coarse, max_keep, n_levels, seconds);  // pgx_amg_build.hip
   double t_host = 0.0, t_dev = 0.0;
   std::vector<UmgLevel> lv(1);
   {
@@ -466,11 +477,25 @@ extern "C" int pgx_build_hierarchy(pgx_handle* h, double theta, double trunc, in
     return PGX_EINVAL;
   }
   umg_install(h, std::move(lv));
+  h->amg_mode = 0;
+  h->amg_split.assign(h->umg.size() - 1, 0);  // the host's split is one serial sweep, no launches
   if (n_levels) *n_levels = (int32_t)h->umg.size();
   if (seconds) {
     seconds[0] = t_host;
     seconds[1] = t_dev;
   }
+  return PGX_OK;
+}
+
+extern "C" int pgx_amg_build_info(pgx_handle* h, int32_t* mode, int32_t* n_transfers, int32_t* split_launches) {
+  NEED(h);
+  if (h->amg_mode < 0 || h->umg.size() < 2) {
+    h->err = "pgx_amg_build_info needs a handle with a built hierarchy (pgx_build_hierarchy)";
+    return PGX_ESTATE;
+  }
+  if (mode) *mode = h->amg_mode;
+  if (n_transfers) *n_transfers = (int32_t)h->amg_split.size();
+  if (split_launches) memcpy(split_launches, h->amg_split.data(), sizeof(int32_t) * h->amg_split.size());
   return PGX_OK;
 }
 

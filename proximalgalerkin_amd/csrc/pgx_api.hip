@@ -1063,6 +1063,8 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_UMG_MIN")) h->umg_min = atoi(e);
   if (const char* e = pgx_tune("PGX_UMG_MIN_P2")) h->umg_min_p2 = atoi(e);
   if (const char* e = pgx_tune("PGX_UMG_BUILD_MIN")) h->umg_build_min = atoi(e);
+  if (const char* e = pgx_tune("PGX_AMG_BUILD")) h->amg_build = atoi(e);
+  if (const char* e = pgx_tune("PGX_AMG_SPLIT_BATCH")) h->amg_split_batch = std::max(1, atoi(e));
   if (const char* e = pgx_tune("PGX_P2_PATCH_WIDE")) h->patch_wide = atoi(e);
   if (const char* e = pgx_tune("PGX_UMG_COARSE_SWEEPS")) h->umg_coarse_sweeps = std::max(1, atoi(e));
   if (const char* e = pgx_tune("PGX_UMG_COARSE_LDS")) h->umg_coarse_lds = atoi(e);

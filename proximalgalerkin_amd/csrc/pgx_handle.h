@@ -209,6 +209,13 @@ struct pgx_handle {
                                // twice the cycle's Krylov iterations at 1 319 vertices, runs into the iteration cap at 20 381 and
                                // fails to converge from 81 017
                                // (profiles/umg_disk_scaling.json).  Not a measured crossover
+  int amg_build = 1;           // PGX_AMG_BUILD=0: pgx_build_hierarchy computes split and patterns in its host pass (pgx_amg.hip) instead of on
+                               // the device (pgx_amg_build.hip); bitwise the same hierarchy (tests/test_gpu_amg_device.py)
+  int amg_split_batch = 16;    // split launches of the device pass between two reads of its counter of decided vertices.  A mesh in its
+                               // generator's order needs hundreds of launches at 300 000 vertices, so the host
+                               // does not read after each.  PGX_AMG_SPLIT_BATCH lowers it FOR TESTS (1: a read after every launch)
+  int amg_mode = -1;           // which of the two built this handle's hierarchy (-1: none built); pgx_amg_build_info
+  std::vector<int32_t> amg_split;  // split launches per transfer of the device pass (0 each for the host pass)
   int umg_coarse_sweeps = 60;  // PGX_UMG_COARSE_SWEEPS
   int umg_coarse_lds = 1;      // PGX_UMG_COARSE_LDS=0: the coarsest level as repeated k_bspmv<2> launches although it fits one workgroup's LDS
   bool umg_coarse_fits = false;  // the coarsest level fits k_umg_coarse and this handle's device took its LDS limit (pgx_set_hierarchy)
@@ -359,6 +366,11 @@ int allreduce_dev(pgx_handle* h, double* dev, size_t n);                       /
 bool f32_cycle_ok(const pgx_handle* h, int l, int nu);                         // level l enters the single-precision cycle
 
 // ---- pgx_amg.hip: the transfers of a built hierarchy (general weights), onto level C from the level above it ----
+void pgxk_amg_direct(hipStream_t st, int n, const int32_t* ptr, const int32_t* src, const double* K, double* val);  // direct weights
+void pgxk_amg_pvalues(hipStream_t st, int n, const int32_t* fptr, const int32_t* own, const int32_t* pptr, const int32_t* pa, const int32_t* pb,
+                      const int32_t* diag, const double* K, const double* p0, double trunc, double* val);  // Jacobi step + truncation
+// pgx_amg_build.hip: the device pass of pgx_build_hierarchy, arguments checked and defaulted
+int pgx_amg_build_device(pgx_handle* h, double theta, double trunc, int32_t min_coarse, double max_keep, int32_t* n_levels, double* seconds);
 void pgxk_amg_rap(hipStream_t st, const UmgLevel& C, const double* src, double* dst);  // dst = P^T (src) P through C.T
 void pgxk_amg_resid_restrict(hipStream_t st, const UmgLevel& C, const double* ru, const double* rp);  // (C.bu, C.bp) = P^T (ru, rp)
 void pgxk_amg_prolong_add(hipStream_t st, int n_f, const UmgLevel& C, double* xu, double* xp);         // (xu, xp) += P (C.xu, C.xp)

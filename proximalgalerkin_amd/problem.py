@@ -452,6 +452,15 @@ class NonlinearProblem:
         self._umg_levels, self.build_seconds = int(nl.value), (float(sec[0]), float(sec[1]))
         return self._umg_levels
 
+    def build_info(self):
+        """How the built hierarchy came about (include/pgx.h: pgx_amg_build_info): dict(mode="device" | "host", split_launches=[per
+        transfer the launches its C/F split took; 0 for the host pass]).  Raises without a built hierarchy."""
+        mode, nt = C.c_int32(0), C.c_int32(0)
+        self._check_code(self._lib.pgx_amg_build_info(self._h, C.byref(mode), C.byref(nt), None), "pgx_amg_build_info")
+        launches = np.zeros(max(nt.value, 1), dtype=np.int32)
+        self._check_code(self._lib.pgx_amg_build_info(self._h, None, None, _lib.iptr(launches)), "pgx_amg_build_info")
+        return dict(mode="device" if mode.value == 1 else "host", split_launches=[int(v) for v in launches[: nt.value]])
+
     def umg_transfer_export(self, t):
         """Transfer t of a built hierarchy, level t + 1 -> level t, as a scipy CSR matrix (include/pgx.h: pgx_umg_transfer_export; a
         test hook)."""

@@ -3,7 +3,7 @@
 
     python3 tools/disk_mg_check.py [--levels 3 4 5 6] [--modes mg single lu] [--trace-level 5] [--out profiles/umg_disk_scaling.json]
     python3 tools/disk_mg_check.py --degree 2 [--levels 3 4 5] [--modes mg lu auto]          (-> profiles/p2_umg_disk_scaling.json)
-    python3 tools/disk_mg_check.py --built [--levels 3 4]                                     (-> profiles/amg_disk_scaling.json)
+    python3 tools/disk_mg_check.py --built [--levels 3 4] [--build {host,device}]             (-> profiles/amg_disk_scaling.json)
 
 For every L: create_disk(0.1, refinements=L) - the construction of generate_mesh_gmsh.py's disk_L - solved with settings B
 (double_exponential, alpha_max 100, tol 1e-4) under "pgx_mg" (the cycle), "pgx_mg" with PGX_UMG=0 (the single-level smoother) and
@@ -29,7 +29,11 @@ and the hierarchy stripped; "unrefined" - create_disk(h / 2^L), a mesh of about 
 two run "built" ("pgx_mg"; the constructor builds the hierarchy, PGX_UMG_BUILD_MIN=0) and "lu".  Recorded in addition:
 build_hierarchy_seconds = (host pass, device work and copies) of pgx_build_hierarchy and the vertices per built level.  Each mode
 is warmed by ONE untimed run on the first mesh it meets (code objects loaded), not once per mesh; one timed run per entry.  The section
-"twin" of the output file is kept as it is (CPU figures of tests/amg_reference.py)."""
+"twin" of the output file is kept as it is (CPU figures of tests/amg_reference.py).  --build host / device pins the pass that computes
+the split and the patterns (tuning key PGX_AMG_BUILD = 0 / 1; without the option no key is set and the library's default, the device
+pass, runs) and files the results under "build_host" / "build_device" instead of "device", so that two runs into one --out file
+(profiles/amg_device_build.json) hold both passes side by side; build_pass and split_launches (pgx_amg_build_info) are recorded
+either way."""
 import argparse
 import contextlib
 import csv
@@ -96,7 +100,9 @@ def solve(msh, mode, monitor_file=None, degree=1):
         t_create = time.perf_counter() - t_create
         extra = {}
         if getattr(problem, "build_seconds", None):  # the constructor built the hierarchy (pgx_build_hierarchy)
-            extra = dict(build_hierarchy_seconds=[round(v, 4) for v in problem.build_seconds])
+            info = problem.build_info()
+            extra = dict(build_hierarchy_seconds=[round(v, 4) for v in problem.build_seconds], build_pass=info["mode"],
+                         split_launches=info["split_launches"])
         try:
             lin, ms, inner = [], [], problem.solve
 
@@ -175,7 +181,11 @@ def main_built(a):
     out = json.loads(path.read_text()) if path.exists() else {}
     out.update(h=a.h, settings="B: double_exponential, alpha_max 100, tol 1e-4; V(6,6), omega 0.75, 60 coarse sweeps; one timed run per entry; "
                "each mode is run once untimed on the first mesh it meets, not once per mesh, so a first-solve figure still carries what is "
-               "first-use per mesh size", device={})
+               "first-use per mesh size")
+    section = "device" if a.build is None else f"build_{a.build}"
+    out[section] = {}
+    if a.build is not None:
+        MODES["built"] = ("pgx_mg", dict(MODES["built"][1], PGX_AMG_BUILD=1 if a.build == "device" else 0))
     warm = set()
     for L in a.levels:
         refined = fem.create_disk(a.h, refinements=L)
@@ -203,19 +213,22 @@ def main_built(a):
                     rec[tag][mode] = r
                     print(f"L={L} {tag} {msh.num_vertices} {mode}: Newton {r['newton']}, Krylov per Newton step mean {r.get('krylov_per_newton_step_mean')}, "
                           f"ms per LVPP solve without the first {r['ms_per_lvpp_solve_mean_without_first']}, build {r.get('build_hierarchy_seconds')} s, "
-                          f"levels {r.get('built_levels')}", flush=True)
+                          f"levels {r.get('built_levels')}, {r.get('build_pass')} pass, split launches {r.get('split_launches')}, "
+                          f"creation plus all solves {r['setup_and_solve_seconds']} s", flush=True)
                 except Exception as e:
                     rec[tag][mode] = f"failed: {type(e).__name__}: {e}"
                     print(f"L={L} {tag} {mode}: {rec[tag][mode]}", flush=True)
             if "lu" in u_ref and "built" in u_ref:
                 rec[tag]["rel_l2_u_built_vs_lu"] = float(np.linalg.norm(u_ref["built"] - u_ref["lu"]) / np.linalg.norm(u_ref["lu"]))
-        out["device"][str(L)] = rec
+        out[section][str(L)] = rec
         path.write_text(json.dumps(out, indent=1) + "\n")
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--built", action="store_true", help="meshes without a hierarchy: the hierarchy built from the matrix (-> profiles/amg_disk_scaling.json)")
+    ap.add_argument("--build", choices=["host", "device"], default=None,
+                    help="with --built: the pass of pgx_build_hierarchy (PGX_AMG_BUILD); results under build_host / build_device")
     ap.add_argument("--levels", type=int, nargs="+", default=[3, 4, 5, 6])
     ap.add_argument("--degree", type=int, default=1, choices=[1, 2])
     ap.add_argument("--modes", nargs="+", default=None, choices=sorted(MODES), help="default: mg single lu; degree 2: mg lu auto")
@@ -231,6 +244,8 @@ def main():
         if a.degree != 1 or a.trace_level is not None:
             ap.error("--built runs degree 1 without a kernel trace")
         return main_built(a)
+    if a.build is not None:
+        ap.error("--build goes with --built")
     a.modes = a.modes or (["mg", "single", "lu"] if a.degree == 1 else ["mg", "lu", "auto"])
     a.out = a.out or str(ROOT / "profiles" / ("umg_disk_scaling.json" if a.degree == 1 else "p2_umg_disk_scaling.json"))
     if a.degree == 2 and (a.trace_level is not None or "single" in a.modes):
