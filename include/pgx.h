@@ -378,6 +378,20 @@ int pgx_observables(pgx_handle* h, double out[6]);
  * otherwise).  Changes no state a solve reads. */
 int pgx_reduce_selfcheck(pgx_handle* h, int nv, int64_t len, int basis_f32, int reps, uint64_t seed, int64_t* mismatches);
 
+/* Entry evaluations of pgx_newton_solve since the handle was created (or the last reset): out[0] in full, out[1] reduced to the first
+ * residual row.  A solve of a single degree-1 handle on a uniform structured mesh that starts at the iterate where the converged solve
+ * before it ended - only the proximal centre and alpha changed in between, the LVPP loop's case - takes F_psi and D(psi) over from that
+ * solve's last evaluation and computes F_u only (tuning key PGX_RESID_REUSE, default 1; 0: always in full).  Any other call on the handle
+ * in between, apart from pgx_get_state, pgx_get_prev, pgx_set_prev, pgx_advance_prev, pgx_set_alpha, pgx_observables and the profile
+ * calls, makes the next entry evaluation a full one.  Same bits either way. */
+int pgx_resid_reuse_counts(pgx_handle* h, int64_t out[2], int reset);
+/* Test hook of the above, to be called where the next pgx_newton_solve would reduce its entry evaluation (PGX_EINVAL otherwise): runs
+ * that evaluation reduced, then in full, at the current sol, sol_k and alpha, and counts differing words.  out[0] entries of F_u that
+ * differ between the two; out[1] entries of F_psi, out[2] 8-byte words of the stored D(psi) copies (level-0 stencil forms, CSR rows)
+ * that the reduced evaluation changed; out[3], out[4] the same two counts for the held values against the full evaluation's;
+ * out[5] the number of vertices.  0 in out[0 .. 5) is the only right answer.  The next entry evaluation is a full one. */
+int pgx_resid_reuse_selfcheck(pgx_handle* h, int64_t out[6]);
+
 /* Accumulated device-time per phase since the last reset, ms (HIP events; only when enabled):
  * [0] residual [1] jacobian fill [2] mg setup [3] spmv (outer Krylov) [4] v-cycle [5] orthogonalisation
  * [6] observables [7] total newton_solve wall */

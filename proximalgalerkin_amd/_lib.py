@@ -389,6 +389,8 @@ SYMBOLS = [
      [_H, C.POINTER(pgx_snes_opts), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("pgx_observables", C.c_int, [_H, c_double_p]),
     ("pgx_reduce_selfcheck", C.c_int, [_H, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_uint64, c_int64_p]),
+    ("pgx_resid_reuse_counts", C.c_int, [_H, c_int64_p, C.c_int]),
+    ("pgx_resid_reuse_selfcheck", C.c_int, [_H, c_int64_p]),
     ("pgx_profile_enable", C.c_int, [_H, C.c_int]),
     ("pgx_profile_get", C.c_int, [_H, c_double_p, C.c_int]),
     # sharded path

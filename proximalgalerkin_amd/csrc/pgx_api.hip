@@ -1030,6 +1030,7 @@ static int create_impl(const pgx_mesh* m, const pgx_problem* p, int device, cons
   if (const char* e = pgx_tune("PGX_SPMV_DICT")) h->spmv_dict = atoi(e);
   if (const char* e = pgx_tune("PGX_SPMV_STENCIL")) h->spmv_stencil = atoi(e);
   if (const char* e = pgx_tune("PGX_RESID_GRID")) h->resid_grid = atoi(e);
+  if (const char* e = pgx_tune("PGX_RESID_REUSE")) h->resid_reuse = atoi(e);
   if (const char* e = pgx_tune("PGX_D_DIRECT")) h->d_direct = atoi(e);
   if (const char* e = pgx_tune("PGX_RAP_LDS_MIN")) h->rap_lds_min = atoi(e);
   if (const char* e = pgx_tune("PGX_K6_MAX")) h->k6_max = atoi(e);
@@ -1433,22 +1434,22 @@ extern "C" int pgx_set_state(pgx_handle* h, const double* x) {
   return copy_in(h, h->x, x);
 }
 extern "C" int pgx_get_state(pgx_handle* h, double* x) {
-  NEED(h);
+  NEED_KEEP(h);
   if (!x) return PGX_EINVAL;
   return copy_out(h, x, h->x);
 }
 extern "C" int pgx_set_prev(pgx_handle* h, const double* x) {
-  NEED(h);
+  NEED_KEEP(h);
   if (!x) return PGX_EINVAL;
   return copy_in(h, h->xk, x);
 }
 extern "C" int pgx_get_prev(pgx_handle* h, double* x) {
-  NEED(h);
+  NEED_KEEP(h);
   if (!x) return PGX_EINVAL;
   return copy_out(h, x, h->xk);
 }
 extern "C" int pgx_advance_prev(pgx_handle* h) {
-  NEED(h);
+  NEED_KEEP(h);
   pgxk_scale_copy(h->st, 2 * (size_t)h->nd, 1.0, h->x, h->xk);  // a streaming kernel: the runtime's D2D blit ran these 67 MB at 0.5 TB/s
   HIPCHK(hipStreamSynchronize(h->st));
   return PGX_OK;
@@ -1496,7 +1497,19 @@ static bool d_direct_on(const pgx_handle* h) {
          sizeof(dsten_t) == 8 && !h->lev[0].Dh32;
 }
 
-static void residual_dev(pgx_handle* h, const double* x, double* F, int with_d = 0) {
+// the residual (and D(psi)) of this handle goes through k_resid_fill_grid / its frame kernel
+static bool resid_grid_on(const pgx_handle* h) {
+  return h->degree == 1 && h->resid_grid && h->structured && !h->lev.empty() && h->lev[0].uniform;
+}
+
+// PGX_RESID_REUSE applies: single handle on the grid path with the default (single-precision) multigrid; sharded handles, replicas of a
+// distributed LU and the fp64 variant keep the full evaluation
+static bool resid_reuse_on(const pgx_handle* h) {
+  return h->resid_reuse && resid_grid_on(h) && !h->dist.on && !h->lu_comm && h->mg_f32;
+}
+
+// fu_only (grid path only, pgx_handle::fresh says when): F[nd ..) and the D copies are at this x already - F[0 .. nd) alone
+static void residual_dev(pgx_handle* h, const double* x, double* F, int with_d = 0, bool fu_only = false) {
   PhaseTimer t(h, 0);
   if (h->degree == 2) {
     pgxk_residual_p2_cells(h->st, h->nc, h->nd, h->cdofs, h->coords, h->mask, h->gbc, x, h->xk, h->alpha, h->f, h->q2,
@@ -1505,12 +1518,13 @@ static void residual_dev(pgx_handle* h, const double* x, double* F, int with_d =
     return;
   }
   // row-parallel, atomic-free, bitwise reproducible; with_d: also fills D(psi) at the same x (Newton driver)
-  if (h->resid_grid && h->structured && !h->lev.empty() && h->lev[0].uniform) {  // uniform structured mesh: LDS-staged element blocks
+  if (resid_grid_on(h)) {  // uniform structured mesh: LDS-staged element blocks
     // with_d == 2 (the Newton loop of a handle whose operator apply is matrix-free and whose preconditioner is the multigrid
     // cycle): the interior rows of D go to the stencil only - their CSR form (56 B per vertex, 235 MB at 2048^2) has no reader
     // until the next pgx_jacobian_fill / pgx_csr_export, which refill it (jac_valid is dropped at the end of the solve)
     pgxk_resid_fill_grid(h->st, with_d ? 1 : 0, h->lev[0], h->fill_lds, h->rowptr, h->v2c_ptr, h->v2c_ent, h->v2c_pos, h->cells,
-                         h->coords, h->mask, h->gbc, h->bphi, x, h->xk, h->alpha, h->f, h->q, F, h->Dv, with_d, d_direct_on(h), h->colm);
+                         h->coords, h->mask, h->gbc, h->bphi, x, h->xk, h->alpha, h->f, h->q, F, h->Dv, with_d, d_direct_on(h), h->colm,
+                         fu_only ? 1 : 0);
     h->dh_interior = with_d != 0;  // the interior rows of the finest D stencil are in place (consumed by jacobian_dev(have_d))
     h->d0_direct = with_d != 0 && d_direct_on(h);  // ... and its frame rows, Dd4 and Dq with them
     if (with_d == 2) h->dv_lean = true;
@@ -1531,7 +1545,7 @@ static int jacobian_dev(pgx_handle* h, const double* x, bool have_d = false) {
       // Galerkin coarse block T^T D_P2 T == D in the P1 basis with the P2 psi (same quadrature), for the P1 hierarchy
       pgxk_fill_rows_p1_Dp2(h->st, h->n, h->fill_lds, h->rowptr, h->v2c_ptr, h->v2c_ent, h->v2c_pos, h->cdofs, h->coords,
                             x + h->nd, h->q2, h->Dv, h->geoq);
-    } else if (h->resid_grid && h->structured && !h->lev.empty() && h->lev[0].uniform) {
+    } else if (resid_grid_on(h)) {
       // uniform structured mesh: D(psi) comes from the same element kernel the Newton driver uses (its residual output goes to
       // scratch), so pgx_jacobian_fill + pgx_csr_export put THAT kernel under the entry-wise oracle comparison of the parity tests
       pgxk_resid_fill_grid(h->st, 1, h->lev[0], h->fill_lds, h->rowptr, h->v2c_ptr, h->v2c_ent, h->v2c_pos, h->cells, h->coords,
@@ -3284,7 +3298,7 @@ extern "C" int pgx_spmv_select(pgx_handle* h, int kind, int* active) {
 }
 
 extern "C" int pgx_observables(pgx_handle* h, double out[6]) {
-  NEED(h);
+  NEED_KEEP(h);
   if (!out) return PGX_EINVAL;
   {
     PhaseTimer t(h, 6);
@@ -3330,6 +3344,75 @@ extern "C" int pgx_observables(pgx_handle* h, double out[6]) {
   return PGX_OK;
 }
 
+extern "C" int pgx_resid_reuse_counts(pgx_handle* h, int64_t out[2], int reset) {
+  if (!h || !out) return PGX_EINVAL;
+  out[0] = h->entry_full;
+  out[1] = h->entry_reduced;
+  if (reset) h->entry_full = h->entry_reduced = 0;
+  return PGX_OK;
+}
+
+// Test hook of PGX_RESID_REUSE: evaluates the entry residual of the next pgx_newton_solve both ways, at the current x, x_k and alpha,
+// and compares bytes on the host.  Needs a valid stamp (PGX_EINVAL otherwise) and leaves it dropped.
+extern "C" int pgx_resid_reuse_selfcheck(pgx_handle* h, int64_t out[6]) {
+  if (!h) return PGX_EINVAL;
+  const pgx_handle::ResidFresh fr = h->fresh;
+  NEED(h);
+  if (!out) return PGX_EINVAL;
+  if (!(resid_reuse_on(h) && fr.valid && fr.dh_interior == h->dh_interior && fr.d0_direct == h->d0_direct && fr.dv_lean == h->dv_lean)) {
+    h->err = "pgx_resid_reuse_selfcheck: no valid stamp (call it after a converged pgx_newton_solve of a handle PGX_RESID_REUSE applies to)";
+    return PGX_EINVAL;
+  }
+  const GridLevel& L = h->lev[0];
+  const size_t n = (size_t)h->n;
+  // the buffers the stamp speaks of: F_psi, Dh, Dd4, Dq, the CSR rows
+  struct Buf {
+    const void* dev;
+    size_t bytes;
+  };
+  const Buf bufs[5] = {{h->F + n, n * sizeof(double)},
+                       {L.Dh, 4 * n * sizeof(dsten_t)},
+                       {L.Dd4, L.Dd4 ? n * sizeof(double4) : 0},
+                       {L.Dq, (L.f32 && L.Dq) ? n * (L.dbf16 ? sizeof(uint2) : sizeof(float4)) : 0},
+                       {h->Dv, h->Dv ? (size_t)h->nnz * sizeof(double) : 0}};
+  using Snap = std::vector<std::vector<unsigned char>>;
+  auto snapshot = [&](Snap& s) -> int {
+    s.resize(5);
+    for (int k = 0; k < 5; ++k) {
+      s[k].resize(bufs[k].bytes);
+      if (bufs[k].bytes) HIPCHK(hipMemcpyAsync(s[k].data(), bufs[k].dev, bufs[k].bytes, hipMemcpyDeviceToHost, h->st));
+    }
+    HIPCHK(hipStreamSynchronize(h->st));
+    return PGX_OK;
+  };
+  auto differing = [](const std::vector<unsigned char>& a, const std::vector<unsigned char>& b, size_t word) {
+    int64_t c = 0;
+    for (size_t i = 0; i < a.size(); i += word) c += memcmp(a.data() + i, b.data() + i, word) != 0;
+    return c;
+  };
+  Snap held, after_reduced, after_full;
+  std::vector<double> fu_reduced(n), fu_full(n);
+  int rc = snapshot(held);
+  if (rc) return rc;
+  residual_dev(h, h->x, h->F, fr.with_d, true);
+  HIPCHK(hipMemcpyAsync(fu_reduced.data(), h->F, n * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  if ((rc = snapshot(after_reduced))) return rc;
+  residual_dev(h, h->x, h->F, fr.with_d, false);
+  HIPCHK(hipMemcpyAsync(fu_full.data(), h->F, n * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  if ((rc = snapshot(after_full))) return rc;
+  HIPCHK(hipGetLastError());
+  out[0] = 0;  // entries of F_u that differ between the two evaluations
+  for (size_t i = 0; i < n; ++i) out[0] += memcmp(&fu_reduced[i], &fu_full[i], sizeof(double)) != 0;
+  out[1] = differing(held[0], after_reduced[0], sizeof(double));  // entries of F_psi the reduced evaluation changed
+  out[2] = 0;  // 8-byte words of the D copies it changed
+  for (int k = 1; k < 5; ++k) out[2] += differing(held[k], after_reduced[k], 8);
+  out[3] = differing(held[0], after_full[0], sizeof(double));  // entries of F_psi in which the held values are not the full evaluation's
+  out[4] = 0;  // the same for the D copies
+  for (int k = 1; k < 5; ++k) out[4] += differing(held[k], after_full[k], 8);
+  out[5] = (int64_t)n;
+  return PGX_OK;
+}
+
 extern "C" int pgx_profile_enable(pgx_handle* h, int on) {
   if (!h) return PGX_EINVAL;
   h->prof = on != 0;
@@ -3348,7 +3431,7 @@ extern "C" int pgx_profile_get(pgx_handle* h, double ms[8], int reset) {
 // options of obstacle_pg.py:128-139; "copy back only if converged" of lvpp/problem.py:121-123.
 // ------------------------------------------------------------------------------------------------
 extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* reason, int* its_out, int* lin_out) {
-  NEED(h);
+  NEED_KEEP(h);
   if (!opts || !reason) return PGX_EINVAL;
   pgx_snes_opts optv = *opts;
   // auto: chosen so that the final primal field stays within 1e-10 of the LU oracle on EVERY case measured
@@ -3411,8 +3494,16 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
   };
   // matrix-free operator + multigrid preconditioner: nobody reads the CSR form of D inside this solve (see residual_dev)
   const int with_d = (!use_lu && !mg_first && h->degree == 1 && h->structured && h->spmv_stencil == 1 && h->lean_d) ? 2 : 1;
+  // entry evaluation: where the solve before ended at this x in this mode and nothing touched its results since (pgx_handle::fresh),
+  // F_psi and D(psi) are in place and only F_u is evaluated.  The stamp is dropped here and set again at the end of a converged solve,
+  // so every other way out - diverged, out of iterations, an early `return rc` - leaves it dropped
+  const bool reuse_ok = resid_reuse_on(h) && !use_lu;
+  const bool fu_only = reuse_ok && h->fresh.valid && h->fresh.with_d == with_d && h->fresh.dh_interior == h->dh_interior &&
+                       h->fresh.d0_direct == h->d0_direct && h->fresh.dv_lean == h->dv_lean;
+  h->fresh.valid = false;
+  ++(fu_only ? h->entry_reduced : h->entry_full);
   pgxk_scale_copy(h->st, n2, 1.0, h->x, h->xw);
-  residual_dev(h, h->xw, h->F, with_d);
+  residual_dev(h, h->xw, h->F, with_d, fu_only);
   if ((rc = replica_check(h, h->F, n2, "the residual"))) return rc;
   if (dist) {
     gather_owned(h, h->F, h->rhs);
@@ -3533,6 +3624,8 @@ extern "C" int pgx_newton_solve(pgx_handle* h, const pgx_snes_opts* opts, int* r
   if (h->dh_interior || h->dv_lean) h->jac_valid = false;
   HIPCHK(hipStreamSynchronize(h->st));
   HIPCHK(hipGetLastError());  // a failed kernel launch anywhere in the solve must not pass silently
+  // converged: x is the iterate of the last residual_dev, whose F_psi and D copies the next solve's entry evaluation can take over
+  if (rsn > 0 && reuse_ok && h->dh_interior) h->fresh = {true, with_d, h->dh_interior, h->d0_direct, h->dv_lean};
   if (h->prof) h->ms[7] += scope.stop();
   *reason = rsn;
   if (its_out) *its_out = its;

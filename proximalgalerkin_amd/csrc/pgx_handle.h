@@ -252,6 +252,23 @@ struct pgx_handle {
   int f32_rr_max = 300000;   // PGX_F32_RR_MAX (measured, us per V-cycle from that level: 257^2 and below -2 each, 513^2 +3, 1025^2 +5, 2049^2 +12): levels with at most this many vertices fuse the residual + restriction into the last
                              // pre-smoothing launch (pgx_mg32.hip, RR mode)
   int resid_grid = 1;      // uniform structured P1: residual + D(psi) through k_resid_fill_grid (PGX_RESID_GRID=0: general kernel)
+  // PGX_RESID_REUSE (default 1; 0: every entry evaluation in full, the launches before it).  A proximal step starts where the last
+  // one ended: sol_k <- sol, another alpha, pgx_newton_solve again from sol.  Of the entry evaluation only F_u = alpha K u +
+  // M (psi - psi_k) - alpha f load depends on what changed; F_psi and D(psi) depend on x alone, and the last evaluation of the solve
+  // before left them in device memory.  valid says exactly that: F[nd .. 2 nd), lev[0].Dh (interior and frame), lev[0].Dd4 / Dq and,
+  // with_d == 1, the CSR rows Dv hold the values at x, written by residual_dev(x, F, with_d) on the grid path, and dh_interior,
+  // d0_direct, dv_lean are as that call left them.  (PGX_D_DIRECT=0: the interior of Dh and the CSR rows hold them; jacobian_dev
+  // derives the frame of Dh, Dd4 and Dq from those, as after a full evaluation.)  Set in ONE place, the end of a converged
+  // pgx_newton_solve.  Cleared by NEED():
+  // every entry of the library that takes the handle drops it before it does anything, except the few that cannot write one of
+  // those buffers or x (NEED_KEEP) - a missed reuse costs one exp pass, a stale one is a silent wrong answer.
+  int resid_reuse = 1;
+  struct ResidFresh {
+    bool valid = false;
+    int with_d = 0;
+    bool dh_interior = false, d0_direct = false, dv_lean = false;
+  } fresh;
+  int64_t entry_full = 0, entry_reduced = 0;  // entry evaluations of pgx_newton_solve, in full / F_u only (pgx_resid_reuse_counts)
   int spmv_stencil = 1;    // structured P1: the outer-Krylov operator apply through the level-0 stencil kernels (matrix-free)
   bool lu_active = false;  // the current Newton solve preconditions with the factorisation
   bool check_replicas = false;  // PGX_CHECK_REPLICAS=1: assert that the replicas' residuals are bitwise identical
@@ -353,9 +370,15 @@ struct PhaseTimer {
   }
 };
 
-#define NEED(hh)          \
+// NEED_KEEP: for the entries that leave pgx_handle::fresh standing - they write neither x, F, a D copy of level 0 nor anything F_psi
+// or D(psi) are computed from (pgx_get_state, pgx_get_prev, pgx_set_prev, pgx_advance_prev, pgx_observables; pgx_newton_solve
+// consumes it itself).  Every other entry takes NEED
+#define NEED_KEEP(hh)          \
   if (!(hh)) return PGX_EINVAL; \
   hipSetDevice((hh)->device)
+#define NEED(hh)  \
+  NEED_KEEP(hh);  \
+  (hh)->fresh.valid = false
 
 #pragma GCC visibility push(hidden)
 // ---- pgx_api.hip, for the Krylov driver ----

@@ -344,11 +344,13 @@ void pgxk_resid_fill_grid(hipStream_t st, int write_d, const GridLevel& L, size_
                           const int32_t* v2c_ptr, const int32_t* v2c_ent, const int32_t* v2c_pos, const int32_t* cells,
                           const double* coords, const uint8_t* mask, const double* gbc, const double* bphi, const double* x,
                           const double* xk, double alpha, double f, QuadTab q, double* F, double* Dout, int write_sh,
-                          int direct = 0, const int32_t* colm = nullptr);
+                          int direct = 0, const int32_t* colm = nullptr, int fu_only = 0);
 // write_sh: 0 = CSR rows only; 1 = CSR rows + the half-stencil L.Dh of the interior; 2 = half-stencil only (interior CSR rows NOT written)
 // direct != 0 (PGX_D_DIRECT): the frame goes through the compact k_resid_fill_frame (one thread per frame vertex), and with write_d
 // and write_sh both kernels also store L.Dh of the frame and the copies L.Dd4 / L.Dq (where allocated) of every vertex: nothing of
 // level 0 is left for pgxk_csr_to_stencil_h, pgxk_f_pack_d and pgxk_pack_d4.  colm: the CSR columns (the frame's Dh slots).
+// fu_only != 0: F[n ..) and every D copy of the interior already hold the values at this x (the caller knows: pgx_handle::ResidFresh) -
+// the interior launch writes F[0 .. n) only, without the exp pass; the frame launch is the one above, unchanged.
 // CGS2, second projection fused with the normalisation: v = (w' - V h2) * scale
 void pgxk_multiaxpy_scale(hipStream_t st, size_t len, int nv, const double* V, size_t ldv, const double* h,
                           double scale, double* w);

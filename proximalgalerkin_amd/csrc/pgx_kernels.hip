@@ -524,15 +524,15 @@ __global__ void __launch_bounds__(PGX_BLOCK) k_resid_fill_p1(int n, const int32_
 // ------------------------------------------------------------------------------------------------
 #define PGX_RF_TX 32
 #define PGX_RF_TY 12
-template <bool WRITE_D>
+template <bool WRITE_D, bool FU_ONLY = false>
 __global__ void __launch_bounds__(PGX_RF_TX * PGX_RF_TY) k_resid_fill_grid(
     int nx, int ny, int n, const int32_t* __restrict__ rowptr, const double* __restrict__ coords, const uint8_t* __restrict__ mask,
     const double* __restrict__ gbc, const double* __restrict__ bphi, const double* __restrict__ x, const double* __restrict__ xk,
     double alpha, double f, QuadTab q, StConst sc, double* __restrict__ F, double* __restrict__ Dout,
     dsten_t* __restrict__ Sh, double4* __restrict__ Dd4, void* __restrict__ Dq, int dbf16) {
   constexpr int TX = PGX_RF_TX, TY = PGX_RF_TY, IW = TX + 2, IH = TY + 2, SW = TX + 1, SH = TY + 1;
-  __shared__ double iu[IH * IW], ip[IH * IW], idp[IH * IW];
-  __shared__ double E[2 * SW * SH][6];  // [2 * square + triangle][00, 11, 22, 01, 02, 12]
+  __shared__ double iu[IH * IW], ip[FU_ONLY ? 1 : IH * IW], idp[IH * IW];
+  __shared__ double E[FU_ONLY ? 1 : 2 * SW * SH][6];  // [2 * square + triangle][00, 11, 22, 01, 02, 12]
   const int sx = nx + 1;
   const int ntx = (nx - 1 + TX - 1) / TX;
   const int i1 = 1 + ((int)blockIdx.x % ntx) * TX, j1 = 1 + ((int)blockIdx.x / ntx) * TY;  // first vertex of the tile
@@ -547,10 +547,29 @@ __global__ void __launch_bounds__(PGX_RF_TX * PGX_RF_TY) k_resid_fill_grid(
       dp = p - xk[n + v];
     }
     iu[t] = u;
-    ip[t] = p;
+    if (!FU_ONLY) ip[t] = p;
     idp[t] = dp;
   }
   __syncthreads();
+  if (FU_ONLY) {
+    // F_psi and every copy of D(psi) at this x are in place (pgx_handle::ResidFresh): only the first residual row, which alone
+    // depends on alpha and x_k - no phase A, no E.  The statements are those of the full form below, so that the bits are too
+    const int li = tid % TX, lj = tid / TX, gi = i1 + li, gj = j1 + lj;
+    if (gi >= nx || gj >= ny) return;
+    const int v = gj * sx + gi;
+    const double adet = fabs((coords[2] - coords[0]) * (coords[2 * sx + 1] - coords[1]));
+    const int o = (lj + 1) * IW + li + 1;
+    const int off[7] = {0, 1, -1, IW, -IW, IW + 1, -IW - 1};
+    double Ku = 0.0, Mdp = 0.0;
+#pragma unroll
+    for (int t = 0; t < 7; ++t) {
+      Ku += sc.K[t] * iu[o + off[t]];
+      Mdp += sc.M[t] * idp[o + off[t]];
+    }
+    const double load = adet * 2.0 * (q.mref[0] + q.mref[1] + q.mref[2]);
+    F[v] = mask[v] ? x[v] - gbc[v] : alpha * Ku + Mdp - alpha * f * load;
+    return;
+  }
   for (int t = tid; t < 2 * SW * SH; t += TX * TY) {
     const int sq = t >> 1, a = sq % SW, b = sq / SW;
     double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -761,7 +780,7 @@ void pgxk_resid_fill_grid(hipStream_t st, int write_d, const GridLevel& L, size_
                           const int32_t* v2c_ptr, const int32_t* v2c_ent, const int32_t* v2c_pos, const int32_t* cells,
                           const double* coords, const uint8_t* mask, const double* gbc, const double* bphi, const double* x,
                           const double* xk, double alpha, double f, QuadTab q, double* F, double* Dout, int write_sh, int direct,
-                          const int32_t* colm) {
+                          const int32_t* colm, int fu_only) {
   const int n = L.n, sx = L.nx + 1;
   // direct: the stencil copies of level 0 leave with the values (frame and interior); needs the CSR columns for the frame's slots
   const bool copies = direct && write_d && write_sh && colm;
@@ -788,7 +807,12 @@ void pgxk_resid_fill_grid(hipStream_t st, int write_d, const GridLevel& L, size_
   if (L.nx < 2 || L.ny < 2) return;
   const int ntx = (L.nx - 1 + PGX_RF_TX - 1) / PGX_RF_TX, nty = (L.ny - 1 + PGX_RF_TY - 1) / PGX_RF_TY;
   const StConst sc = make_stconst(L);
-  if (write_d)
+  // fu_only: F_psi and the D copies of the interior already hold the values at this x - the interior kernel without its exp pass.
+  // The frame above ran in full: 2 (nx + ny) vertices, and it rewrites the bits that are there
+  if (fu_only)
+    hipLaunchKernelGGL((k_resid_fill_grid<false, true>), dim3(ntx * nty), dim3(PGX_RF_TX * PGX_RF_TY), 0, st, L.nx, L.ny, n, rowptr,
+                       coords, mask, gbc, bphi, x, xk, alpha, f, q, sc, F, nullptr, nullptr, nullptr, nullptr, 0);
+  else if (write_d)
     hipLaunchKernelGGL(k_resid_fill_grid<true>, dim3(ntx * nty), dim3(PGX_RF_TX * PGX_RF_TY), 0, st, L.nx, L.ny, n, rowptr, coords,
                        mask, gbc, bphi, x, xk, alpha, f, q, sc, F, write_sh == 2 ? nullptr : Dout, write_sh ? L.Dh : nullptr, Dd4, Dq,
                        L.dbf16);

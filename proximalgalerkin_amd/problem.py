@@ -584,6 +584,20 @@ class NonlinearProblem:
                                                                       int(seed), C.byref(bad)), "pgx_reduce_selfcheck")
         return bad.value
 
+    def resid_reuse_counts(self, reset=False):
+        """(full, reduced): entry evaluations of the Newton solves of this handle so far (include/pgx.h: pgx_resid_reuse_counts)."""
+        out = (C.c_int64 * 2)()
+        _lib.check(self._lib, self._h, self._lib.pgx_resid_reuse_counts(self._h, out, int(reset)), "pgx_resid_reuse_counts")
+        return int(out[0]), int(out[1])
+
+    def resid_reuse_selfcheck(self):
+        """The next solve's entry evaluation, reduced against full, at the current sol, sol_k and alpha: six counts, the first five of
+        which must be 0 (include/pgx.h: pgx_resid_reuse_selfcheck)."""
+        self._sync_inputs()
+        out = (C.c_int64 * 6)()
+        _lib.check(self._lib, self._h, self._lib.pgx_resid_reuse_selfcheck(self._h, out), "pgx_resid_reuse_selfcheck")
+        return [int(v) for v in out]
+
     def owned_edge_range(self):
         """(offset, count): owned EDGE dofs within each field block of a P2 local vector (include/pgx.h: pgx_owned_edge_range)."""
         off, cnt = C.c_int64(0), C.c_int64(0)
