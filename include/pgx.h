@@ -318,7 +318,7 @@ int pgx_umg_level_export(pgx_handle* h, int level, int32_t* n, int32_t* nnz, int
  * restricted residual is; PGX_EINVAL otherwise. */
 int pgx_umg_cycle_apply(pgx_handle* h, int level, int nu, double omega, const double* b, double* z);
 
-/* ---- Test hooks of the P2 two-level preconditioner (pgx_api.hip: pcycle_p2_patch; pgx_patch.hip): patch_nu additive vertex-star
+/* ---- Test hooks of the P2 two-level preconditioner (pgx_cycle.hip: pcycle_p2_patch; pgx_patch.hip): patch_nu additive vertex-star
  * sweeps | restriction to the P1 hierarchy | one P1 V-cycle | prolongation | patch_nu sweeps.  They replace nothing in the reference
  * (which factorises the P2 Newton matrix as well, obstacle_pg.py:68-70,129-131): they let tests compare what the device stores and
  * computes, stage by stage, with a numpy statement of the same algebra (tests/p2_cycle_reference.py).  Preconditions of all three: a

@@ -1,6 +1,8 @@
-// Internal: the handle behind include/pgx.h and what its two translation units share.  pgx_api.hip holds the plan building, the
-// multigrid hierarchy and its cycles, the Newton driver and the C ABI; pgx_krylov.hip holds FGMRES, the reductions' way to the host
-// and their test hook.  Nothing here is exported from libpgx.so.
+// Internal: the handle behind include/pgx.h and what its five translation units share.  pgx_api.hip holds the tuning table, handle
+// creation, state access, residual, Jacobian, operator apply and the Newton driver; pgx_setup.hip the plan building and the multigrid
+// hierarchies; pgx_cycle.hip the preconditioner: the cycles, the collectives, the patch data and the sparse LU; pgx_hooks.hip the test
+// and measurement hooks; pgx_krylov.hip FGMRES, the reductions' way to the host and their test hook.  Nothing here is exported from
+// libpgx.so.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -381,12 +383,42 @@ struct PhaseTimer {
   (hh)->fresh.valid = false
 
 #pragma GCC visibility push(hidden)
-// ---- pgx_api.hip, for the Krylov driver ----
+// ---- pgx_api.hip ----
+extern thread_local std::string g_create_error;  // what pgx_last_error(nullptr) answers: a failed creation has no handle to ask
+int copy_in(pgx_handle* h, double* dst, const double* src);   // 2 nd doubles host -> device, synchronous
+int copy_out(pgx_handle* h, double* dst, const double* src);  // 2 nd doubles device -> host, synchronous
+bool resid_reuse_on(const pgx_handle* h);                     // PGX_RESID_REUSE applies to this handle
+void residual_dev(pgx_handle* h, const double* x, double* F, int with_d = 0, bool fu_only = false);
+bool p2st_ready(pgx_handle* h);  // the structured P2 apply can run (refreshes its copies of D once per Jacobian)
+void p2st_apply(pgx_handle* h, const double* xu, const double* xp, const double* bu, const double* bp, double* yu, double* yp, bool inner);
+void spmv_dev(pgx_handle* h, const double* x, double* y);  // y = J x
+
+// ---- pgx_setup.hip ----
+int build_plan(pgx_handle* h, const pgx_mesh* m, const std::vector<uint8_t>& hmask);
+int build_plan_p2(pgx_handle* h, const pgx_mesh* m, const std::vector<uint8_t>& hmask);
+int build_km_dictionary(pgx_handle* h);
+int ghost_mul();  // ghost depth multiplier of the sharded path (PGX_GHOST_MUL)
+int build_multigrid(pgx_handle* h);
+int build_multigrid_dist(pgx_handle* h);
+
+// ---- pgx_cycle.hip ----
 int precond(pgx_handle* h, const double* b, double* z, int nu, double omega);  // z = M^-1 b: one cycle, or the sparse LU
-void spmv_dev(pgx_handle* h, const double* x, double* y);                      // y = J x
-void gather_owned(pgx_handle* h, const double* loc, double* cmp);              // sharded: local vector -> owned-compact
-int allreduce_dev(pgx_handle* h, double* dev, size_t n);                       // sharded: sum over the ranks, on the stream
-bool f32_cycle_ok(const pgx_handle* h, int l, int nu);                         // level l enters the single-precision cycle
+void level_apply(pgx_handle* h, int l, int mode, const double* xu, const double* xp, const double* bu, const double* bp, double omega,
+                 int first, double* yu, double* yp);  // one stencil (or, level 0 of a general mesh, block-CSR) launch on level l
+void vcycle(pgx_handle* h, int l, const double* bu, const double* bp, double* outu, double* outp, int nu, double omega);
+const float2* vcycle_f(pgx_handle* h, int l, const double* bu, const double* bp, double* outu, double* outp, int nu, double omega);
+void vcycle_umg(pgx_handle* h, int l, const double* bu, const double* bp, double* outu, double* outp, int nu, double omega);
+bool f32_cycle_ok(const pgx_handle* h, int l, int nu);             // level l enters the single-precision cycle
+int halo_solution(pgx_handle* h, double* fu, double* fp);          // sharded: ghost entries of a solution-space pair from their owners
+int allreduce_dev(pgx_handle* h, double* dev, size_t n);           // sharded: sum over the ranks, on the stream
+void gather_owned(pgx_handle* h, const double* loc, double* cmp);  // sharded: local vector -> owned-compact
+int ensure_patches(pgx_handle* h);                                 // P2 patch data: tables on first use, inverses once per Jacobian
+int p2_cycle_resid_kind(pgx_handle* h);
+void p2_cycle_resid(pgx_handle* h, int kind, const double* xu, const double* xp, const double* bu, const double* bp);
+void p2_cycle_patch(pgx_handle* h, const double* ru, const double* rp, double* xu, double* xp);
+int ensure_lu(pgx_handle* h);  // symbolic phase of the sparse LU, once per handle
+int lu_factor(pgx_handle* h);  // numeric factorisation of the current Jacobian
+int replica_check(pgx_handle* h, const double* dev, size_t n, const char* what);  // PGX_CHECK_REPLICAS
 
 // ---- pgx_amg.hip: the transfers of a built hierarchy (general weights), onto level C from the level above it ----
 void pgxk_amg_direct(hipStream_t st, int n, const int32_t* ptr, const int32_t* src, const double* K, double* val);  // direct weights

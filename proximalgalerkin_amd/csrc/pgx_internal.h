@@ -1,5 +1,6 @@
-// Internal declarations shared by pgx_kernels.hip (device code + launch wrappers), pgx_api.hip (host-side plan building,
-// Newton / multigrid drivers, C ABI) and pgx_krylov.hip (FGMRES and the reductions' read-back).  gfx950 only.
+// Internal declarations shared by pgx_kernels.hip (device code + launch wrappers) and the host side: pgx_api.hip (handle, Newton
+// driver, C ABI), pgx_setup.hip (plan building, hierarchies), pgx_cycle.hip (multigrid drivers), pgx_hooks.hip (test hooks) and
+// pgx_krylov.hip (FGMRES and the reductions' read-back).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

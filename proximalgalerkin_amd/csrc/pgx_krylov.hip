@@ -1,5 +1,5 @@
 // The Krylov driver of libpgx.so: how a reduced scalar reaches the host (one routine, three routes), the 2-norm, FGMRES on one basis
-// type, and the test hook that runs those same pieces.  The preconditioner, the operator and the collectives stay in pgx_api.hip.
+// type, and the test hook that runs those same pieces.  The operator is in pgx_api.hip, the preconditioner and the collectives in pgx_cycle.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>

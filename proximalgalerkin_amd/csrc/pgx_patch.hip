@@ -2,7 +2,7 @@
 //
 // Reference: the reference solves the P2 systems of `obstacle_pg.py -p 2` exactly (/root/reference/examples/01_obstacle_problem/
 // obstacle_pg.py:68-70,129-131,288).  Here they are solved by FGMRES with a two-level cycle: a smoother on the P2 level + the P1
-// hierarchy as coarse space (pgx_api.hip: pcycle_p2).  The collective point-Jacobi smoother of rounds 1-2 is not robust there: on
+// hierarchy as coarse space (pgx_cycle.hip: pcycle_p2).  The collective point-Jacobi smoother of rounds 1-2 is not robust there: on
 // the late proximal steps e^psi spans tens of orders of magnitude inside one element and the Krylov counts grow with N (30-90 at
 // 64^2-128^2, hundreds at 256^2).  The remedy (prototype: oracle/p2_patch_proto.py, 8-18 iterations at 16^2 ... 256^2 on the same
 // systems) is an ADDITIVE VERTEX-STAR SCHWARZ smoother: for every mesh vertex the dofs (u, psi) on the vertex and on the edges that

@@ -1,4 +1,4 @@
-"""numpy statement of the P2 two-level preconditioner (csrc/pgx_api.hip: pcycle_p2_patch; csrc/pgx_patch.hip).  Test infrastructure:
+"""numpy statement of the P2 two-level preconditioner (csrc/pgx_cycle.hip: pcycle_p2_patch; csrc/pgx_patch.hip).  Test infrastructure:
 the algebra of oracle/p2_patch_proto.py, built only from what the library exports (the scalar blocks K, M, D of pgx_csr_export,
 alpha, the Dirichlet set) plus the edges of the oracle's ObstacleLagrange:
 
@@ -57,7 +57,7 @@ def patch_slots(NN):
 
 
 def dict_values(v):
-    """What build_km_dictionary (csrc/pgx_api.hip) keeps of the entries v of K or M: each rounded to a grid of 2^-40 of the power of
+    """What build_km_dictionary (csrc/pgx_setup.hip) keeps of the entries v of K or M: each rounded to a grid of 2^-40 of the power of
     two at or below the largest |entry| (exact arithmetic, a function of the entry alone)."""
     v = np.asarray(v, dtype=np.float64)
     t = 2.0 ** (np.floor(np.log2(np.abs(v).max())) - 40)

@@ -1,5 +1,5 @@
 """numpy statement of the P2 two-level cycle over the hierarchy of a refined general mesh (include/pgx.h: pgx_set_hierarchy on a
-degree-2 handle; csrc/pgx_api.hip: pcycle_p2_patch -> vcycle_umg; csrc/pgx_patch.hip: the wide stars).  TEST INFRASTRUCTURE ONLY.
+degree-2 handle; csrc/pgx_cycle.hip: pcycle_p2_patch -> vcycle_umg; csrc/pgx_patch.hip: the wide stars).  TEST INFRASTRUCTURE ONLY.
 
   P2UmgReference   tests/p2_cycle_reference.P2CycleReference with its coarse step replaced by one cycle of
                    tests/umg_reference.UmgReference on (K1, M1, D1) = T^T (K, M, D) T, the vertex mask and the mesh's `parents`

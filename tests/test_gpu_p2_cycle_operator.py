@@ -1,4 +1,4 @@
-"""The P2 two-level preconditioner (csrc/pgx_api.hip: pcycle_p2_patch; csrc/pgx_patch.hip) as an OPERATOR, stage by stage, against
+"""The P2 two-level preconditioner (csrc/pgx_cycle.hip: pcycle_p2_patch; csrc/pgx_patch.hip) as an OPERATOR, stage by stage, against
 tests/p2_cycle_reference.py.
 
 No assertion on a solve can see this code go wrong: FGMRES runs on the exact fp64 operator, a worse preconditioner costs Krylov

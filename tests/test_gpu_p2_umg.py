@@ -1,5 +1,5 @@
 """Degree 2 on refined general meshes: the two-level patch cycle over the block-CSR hierarchy (include/pgx.h: pgx_set_hierarchy on a
-degree-2 handle; csrc/pgx_api.hip: pcycle_p2_patch -> vcycle_umg) and the wide stars of degree 8 ... 15 (csrc/pgx_patch.hip:
+degree-2 handle; csrc/pgx_cycle.hip: pcycle_p2_patch -> vcycle_umg) and the wide stars of degree 8 ... 15 (csrc/pgx_patch.hip:
 k_patch_invert_wide, k_patch_apply_wide), against tests/p2_umg_reference.py.
 
 Meshes (tests/p2_umg_reference.build_mesh): D34 469 vertices, degree <= 6, 7 slots; D5 227, one vertex of degree 7, 8 slots; W4 =

@@ -1,4 +1,4 @@
-"""numpy twin of the P1 multigrid V-cycle (csrc/pgx_api.hip: vcycle, vcycle_f) on an nx x ny right-diagonal grid.  Test infrastructure:
+"""numpy twin of the P1 multigrid V-cycle (csrc/pgx_cycle.hip: vcycle, vcycle_f) on an nx x ny right-diagonal grid.  Test infrastructure:
 the algebra of oracle/krylov_proto.py: CollectiveMG, stated for rectangles and built only from what the library exports (the scalar
 blocks K, M, D of pgx_csr_export, alpha, the Dirichlet set):
 
@@ -66,7 +66,7 @@ def half_stencil(S, nx, ny):
 
 
 def coarse_shapes(nx, ny, min_nx=4):
-    """Cells per side of every level: halved while both counts are even and above min_nx (csrc/pgx_api.hip: build_multigrid)."""
+    """Cells per side of every level: halved while both counts are even and above min_nx (csrc/pgx_setup.hip: build_multigrid)."""
     shapes = [(nx, ny)]
     while nx % 2 == 0 and ny % 2 == 0 and nx > min_nx and ny > min_nx:
         nx, ny = nx // 2, ny // 2
