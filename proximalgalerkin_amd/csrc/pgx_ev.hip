@@ -504,22 +504,8 @@ static int ev_create_impl(pgx_ev_handle* h, const pgx_ev_problem* pr) {
     xy[2 * (size_t)v] = pr->x0 + (v % Lx) * hx / p, xy[2 * (size_t)v + 1] = pr->y0 + (v / Lx) * hy / p;
   }
   MXHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix Am{};
-  Am.n = ntot;
-  Am.rowptr = rowptr.data();
-  Am.col = col.data();
-  Am.n_nodes = n;
-  Am.node_of_dof = nod.data();
-  Am.dim = 2;
-  Am.node_coords = xy.data();
-  Am.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) Am.leaf_nodes = atoi(e);
-  int rc = pgx_nd_create(&Am, h->device, (void*)h->st, &h->lu);
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, n, nod.data(), 2, xy.data());
+  if (rc) return rc;
   // the Jacobian with its Dirichlet rows AND columns replaced is symmetric (indefinite) as assembled: L D L^T in LU clothing (pgx_nd.h)
   pgx_nd_set_symmetric(h->lu, 1);
   MXALLOC(h->tab, 1);

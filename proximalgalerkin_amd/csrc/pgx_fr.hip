@@ -15,13 +15,11 @@
 #include "../../include/pgx_fr.h"
 #include "pgx_mixed.h"
 #include "pgx_scatter.h"
+#include "pgx_tri.h"
 
 #define FR_MAXQ 16
 #define FR_MAXPTS 64
-struct FrQuad {
-  double N[FR_MAXQ][3], w[FR_MAXQ];
-  int nq;
-};
+using FrQuad = TriQuad<FR_MAXQ>;
 struct FrPar {
   double G, Gc, l, eps, reps;
 };
@@ -54,25 +52,6 @@ struct pgx_fr_handle : MixedBase {
 
 extern "C" const char* pgx_fr_last_error(const pgx_fr_handle* h) { return h ? h->err.c_str() : g_fr_error.c_str(); }
 
-struct FrGeom {
-  double G[3][2];  // physical P1 gradients
-  double adet;
-};
-__device__ inline FrGeom fr_geom(const double* __restrict__ coords, const int32_t* __restrict__ cv) {
-  FrGeom g;
-  double X[3][2];
-  for (int a = 0; a < 3; ++a) X[a][0] = coords[2 * (size_t)cv[a]], X[a][1] = coords[2 * (size_t)cv[a] + 1];
-  const double j00 = X[1][0] - X[0][0], j10 = X[1][1] - X[0][1];
-  const double j01 = X[2][0] - X[0][0], j11 = X[2][1] - X[0][1];
-  const double det = j00 * j11 - j01 * j10;
-  const double i00 = j11 / det, i01 = -j01 / det, i10 = -j10 / det, i11 = j00 / det;
-  g.G[1][0] = i00, g.G[1][1] = i01;
-  g.G[2][0] = i10, g.G[2][1] = i11;
-  g.G[0][0] = -(i00 + i10), g.G[0][1] = -(i01 + i11);
-  g.adet = fabs(det);
-  return g;
-}
-__device__ inline double fr_me(double area, int a, int b) { return area / 12.0 * (a == b ? 2.0 : 1.0); }
 // logistic function and its derivative sigma (1 - sigma) from t = exp(-|p|) <= 1: finite for every finite p
 __device__ inline void fr_sigma(double p, double* s, double* ds) {
   const double t = exp(-fabs(p)), r = 1.0 / (1.0 + t);
@@ -86,7 +65,7 @@ struct FrCell {
   double Ms[3];   // int (1 - c) phi_a
   double g2, Iw;  // |grad u|^2, int w(c)
 };
-__device__ inline FrCell fr_cell(const FrGeom& g, double area, const double u[3], const double c[3], double eps) {
+__device__ inline FrCell fr_cell(const TriGeom& g, double area, const double u[3], const double c[3], double eps) {
   FrCell k;
   double gu[2] = {0, 0};
   for (int a = 0; a < 3; ++a) gu[0] += u[a] * g.G[a][0], gu[1] += u[a] * g.G[a][1];
@@ -95,7 +74,7 @@ __device__ inline FrCell fr_cell(const FrGeom& g, double area, const double u[3]
   for (int a = 0; a < 3; ++a) {
     k.ga[a] = gu[0] * g.G[a][0] + gu[1] * g.G[a][1];
     k.Ms[a] = 0.0;
-    for (int b = 0; b < 3; ++b) k.Ms[a] += fr_me(area, a, b) * (1.0 - c[b]);
+    for (int b = 0; b < 3; ++b) k.Ms[a] += tri_me(area, a, b) * (1.0 - c[b]);
     Iss += (1.0 - c[a]) * k.Ms[a];
   }
   k.Iw = (1.0 - eps) * Iss + eps * area;  // w(c) = (1 - eps) (1 - c)^2 + eps (:119)
@@ -110,7 +89,7 @@ __global__ __launch_bounds__(128) void k_fr_residual(int nc, int nv, const int32
   const int cell = blockIdx.x * blockDim.x + threadIdx.x;
   if (cell >= nc) return;
   const int32_t* cv = cells + 3 * (size_t)cell;
-  const FrGeom g = fr_geom(coords, cv);
+  const TriGeom g = tri_geom(coords, cv);
   double u[3], c[3], p[3], dp[3], cp[3], lift[3];
   for (int a = 0; a < 3; ++a) {
     const size_t v = cv[a];
@@ -128,14 +107,14 @@ __global__ __launch_bounds__(128) void k_fr_residual(int nc, int nv, const int32
   double Rv[3], Rd[3], Rp[3];
   for (int a = 0; a < 3; ++a) {
     double mc = 0, mdp = 0;
-    for (int b = 0; b < 3; ++b) mc += fr_me(area, a, b) * c[b], mdp += fr_me(area, a, b) * dp[b];
+    for (int b = 0; b < 3; ++b) mc += tri_me(area, a, b) * c[b], mdp += tri_me(area, a, b) * dp[b];
     Rv[a] = alpha * P.G * k.Iw * k.ga[a];                                                             // :119, :125
     Rd[a] = alpha * (0.5 * P.G * dwf * k.g2 * k.Ms[a] + P.Gc / P.l * mc +
                      P.Gc * P.l * area * (gc[0] * g.G[a][0] + gc[1] * g.G[a][1])) + mdp;               // :119-121, :125-127
     Rp[a] = mc;                                                                                        // :128
     for (int b = 0; b < 3; ++b) {  // lifting: element columns of J_reg of the Dirichlet vertices times (g - x_b)
       const double gab = g.G[a][0] * g.G[b][0] + g.G[a][1] * g.G[b][1];
-      Rv[a] += (alpha * P.G * k.Iw * gab + P.reps * fr_me(area, a, b)) * lift[b];
+      Rv[a] += (alpha * P.G * k.Iw * gab + P.reps * tri_me(area, a, b)) * lift[b];
       Rd[a] += alpha * P.G * dwf * k.ga[b] * k.Ms[a] * lift[b];
     }
   }
@@ -164,11 +143,11 @@ __global__ __launch_bounds__(128) void k_fr_const(int nc, const int32_t* __restr
                                                   double* __restrict__ stash) {
   const int cell = blockIdx.x * blockDim.x + threadIdx.x;
   if (cell >= nc) return;
-  const FrGeom g = fr_geom(coords, cells + 3 * (size_t)cell);
+  const TriGeom g = tri_geom(coords, cells + 3 * (size_t)cell);
   const double area = 0.5 * g.adet;
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) {
-      stash[(size_t)(a * 3 + b) * nc + cell] = fr_me(area, a, b);
+      stash[(size_t)(a * 3 + b) * nc + cell] = tri_me(area, a, b);
       stash[(size_t)(9 + a * 3 + b) * nc + cell] = area * (g.G[a][0] * g.G[b][0] + g.G[a][1] * g.G[b][1]);
     }
 }
@@ -191,7 +170,7 @@ __global__ __launch_bounds__(128) void k_fr_jac(int nc, int nv, const int32_t* _
   const int cell = blockIdx.x * blockDim.x + threadIdx.x;
   if (cell >= nc) return;
   const int32_t* cv = cells + 3 * (size_t)cell;
-  const FrGeom g = fr_geom(coords, cv);
+  const TriGeom g = tri_geom(coords, cv);
   double u[3], c[3], p[3], cp[3];
   for (int a = 0; a < 3; ++a) {
     const size_t v = cv[a];
@@ -206,7 +185,7 @@ __global__ __launch_bounds__(128) void k_fr_jac(int nc, int nv, const int32_t* _
       stash[(size_t)(a * 3 + b) * nc + cell] = alpha * P.G * k.Iw * gab;
       stash[(size_t)(9 + a * 3 + b) * nc + cell] = alpha * P.G * dwf * k.ga[a] * k.Ms[b];
       stash[(size_t)(18 + a * 3 + b) * nc + cell] = alpha * P.G * dwf * k.ga[b] * k.Ms[a];
-      stash[(size_t)(27 + a * 3 + b) * nc + cell] = alpha * P.G * (1.0 - P.eps) * k.g2 * fr_me(area, a, b);  // 1/2 G w'' |grad u|^2 M
+      stash[(size_t)(27 + a * 3 + b) * nc + cell] = alpha * P.G * (1.0 - P.eps) * k.g2 * tri_me(area, a, b);  // 1/2 G w'' |grad u|^2 M
     }
   double D[6] = {0, 0, 0, 0, 0, 0};  // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
   for (int q = 0; q < Q.nq; ++q) {
@@ -232,13 +211,13 @@ __global__ __launch_bounds__(256) void k_fr_l2(int nc, int nv, const int32_t* __
   double s = 0.0;
   for (int cell = blockIdx.x * 256 + threadIdx.x; cell < nc; cell += MX_RED * 256) {
     const int32_t* cv = cells + 3 * (size_t)cell;
-    const FrGeom g = fr_geom(coords, cv);
+    const TriGeom g = tri_geom(coords, cv);
     const double area = 0.5 * g.adet;
     for (int blk = b0; blk < b1; ++blk) {
       double d[3];
       for (int a = 0; a < 3; ++a) d[a] = x[(size_t)blk * nv + cv[a]] - y[(size_t)blk * nv + cv[a]];
       for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) s += fr_me(area, a, b) * d[a] * d[b];
+        for (int b = 0; b < 3; ++b) s += tri_me(area, a, b) * d[a] * d[b];
     }
   }
   sh[threadIdx.x] = s;
@@ -297,16 +276,11 @@ static int fr_create_impl(pgx_fr_handle* h, const pgx_mesh* m, const pgx_fr_prob
   const int64_t ntot = 3 * (int64_t)nv;
   h->nv = nv, h->nc = nc, h->ntot = ntot;
   h->P = FrPar{p->G, p->Gc, p->l, p->eps, p->reps};
-  h->Q.nq = p->nq;
-  for (int q = 0; q < p->nq; ++q) {
-    const double X = p->qpts[2 * q], Y = p->qpts[2 * q + 1];
-    h->Q.N[q][0] = 1.0 - X - Y, h->Q.N[q][1] = X, h->Q.N[q][2] = Y, h->Q.w[q] = p->qwts[q];
+  h->Q.fill(p->qpts, p->qwts, p->nq);
+  if (const char* e = check_cells(m->cells, 3, nc, nv)) {
+    h->err = e;
+    return PGX_EINVAL;
   }
-  for (size_t k = 0; k < 3 * (size_t)nc; ++k)
-    if (m->cells[k] < 0 || m->cells[k] >= nv) {
-      h->err = "cell vertex out of range";
-      return PGX_EINVAL;
-    }
   for (int c = 0; c < nc; ++c) {
     const int32_t* cv = m->cells + 3 * (size_t)c;
     const double* X0 = m->coords + 2 * (size_t)cv[0];
@@ -335,32 +309,8 @@ static int fr_create_impl(pgx_fr_handle* h, const pgx_mesh* m, const pgx_fr_prob
     }
   }
   // scalar P1 pattern (vertex adjacency incl. self), then 3 x 3 blocks
-  std::vector<int64_t> vptr(nv + 1, 0);
-  for (size_t k = 0; k < 3 * (size_t)nc; ++k) vptr[m->cells[k] + 1]++;
-  for (int v = 0; v < nv; ++v) vptr[v + 1] += vptr[v];
-  std::vector<int32_t> vcell(vptr[nv]);
-  {
-    std::vector<int64_t> fill(vptr.begin(), vptr.end() - 1);
-    for (int c = 0; c < nc; ++c)
-      for (int a = 0; a < 3; ++a) vcell[fill[m->cells[3 * (size_t)c + a]]++] = c;
-  }
-  std::vector<int32_t> sptr(nv + 1, 0), scol;
-  {
-    std::vector<std::vector<int32_t>> rows(nv);
-    mx_par_for(nv, [&](int64_t a, int64_t b) {
-      for (int64_t v = a; v < b; ++v) {
-        auto& r = rows[v];
-        r.push_back((int32_t)v);  // a vertex of no cell keeps its diagonal
-        for (int64_t q = vptr[v]; q < vptr[v + 1]; ++q)
-          for (int k = 0; k < 3; ++k) r.push_back(m->cells[3 * (size_t)vcell[q] + k]);
-        std::sort(r.begin(), r.end());
-        r.erase(std::unique(r.begin(), r.end()), r.end());
-      }
-    });
-    for (int v = 0; v < nv; ++v) sptr[v + 1] = sptr[v] + (int32_t)rows[v].size();
-    scol.resize(sptr[nv]);
-    for (int v = 0; v < nv; ++v) std::copy(rows[v].begin(), rows[v].end(), scol.begin() + sptr[v]);
-  }
+  std::vector<int32_t> sptr, scol;
+  p1_adjacency(nv, nc, m->cells, true, sptr, scol);  // true: a vertex of no cell keeps its diagonal, its rows are not empty
   const int64_t nnz_s = sptr[nv];
   if (9 * nnz_s > 0x7fffffff || 45 * (int64_t)nc > 0x7fffffff) {
     h->err = "mixed matrix exceeds int32 nnz";
@@ -432,22 +382,8 @@ static int fr_create_impl(pgx_fr_handle* h, const pgx_mesh* m, const pgx_fr_prob
   std::vector<int32_t> nod(ntot);
   for (int v = 0; v < nv; ++v) nod[v] = nod[(size_t)nv + v] = nod[2 * (size_t)nv + v] = v;
   MXHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix A{};
-  A.n = ntot;
-  A.rowptr = rowptr.data();
-  A.col = col.data();
-  A.n_nodes = nv;
-  A.node_of_dof = nod.data();
-  A.dim = 2;
-  A.node_coords = m->coords;
-  A.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) A.leaf_nodes = atoi(e);
-  int rc = pgx_nd_create(&A, h->device, (void*)h->st, &h->lu);
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, nv, nod.data(), 2, m->coords);
+  if (rc) return rc;
   // J_reg with its Dirichlet rows AND columns replaced is symmetric (indefinite) as assembled: L D L^T in LU clothing (pgx_nd.h)
   pgx_nd_set_symmetric(h->lu, 1);
   MXALLOC(h->coords, 2 * (size_t)nv);
@@ -456,19 +392,15 @@ static int fr_create_impl(pgx_fr_handle* h, const pgx_mesh* m, const pgx_fr_prob
   MXALLOC(h->zprev, ntot);
   MXALLOC(h->stash, 45 * (size_t)nc);
   MXALLOC(h->Sc, 2 * nnz_s);
-  MXALLOC(h->rowptr, ntot + 1);
-  MXALLOC(h->col, tot);
   MXALLOC(h->kind, tot);
   MXALLOC(h->src, tot);
   MXALLOC(h->Jc, tot);
-  MXALLOC(h->Jv, tot);
   MXALLOC(h->d_pts, 2 * FR_MAXPTS);
   if ((rc = mx_alloc_state(h))) return rc;
+  if ((rc = mx_upload_pattern(h))) return rc;
   MXHIP(hipMemcpy(h->coords, m->coords, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->cells, m->cells, sizeof(int32_t) * 3 * (size_t)nc, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->sign, hsign.data(), nv, hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->rowptr, rowptr.data(), sizeof(int32_t) * (ntot + 1), hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->col, col.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->kind, kind.data(), tot, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->src, src.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   MXHIP(hipMemsetAsync(h->zprev, 0, sizeof(double) * ntot, h->st));
@@ -483,23 +415,10 @@ static int fr_create_impl(pgx_fr_handle* h, const pgx_mesh* m, const pgx_fr_prob
       return PGX_ENOMEM;
     }
   }
-  {  // scalar M and K, once, deterministic: the table is temporary, the stash is the handle's
-    std::vector<void*> tmp;
-    PgxScatter sc_c;
-    std::string e1 = pgx_scatter_build(d18.data(), (int64_t)18 * nc, 2 * nnz_s, tmp, &sc_c);
-    hipError_t e = hipErrorOutOfMemory;
-    if (e1.empty()) {
-      hipLaunchKernelGGL(k_fr_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cells, h->coords, h->stash);
-      pgx_scatter_run(h->st, sc_c, h->stash, 1.0, 0, h->Sc);
-      e = hipStreamSynchronize(h->st);
-    }
-    for (void* q : tmp) hipFree(q);
-    if (e != hipSuccess) {
-      h->err = std::string("constant Jacobian blocks: ") + (e1.empty() ? hipGetErrorString(e) : e1.c_str());
-      return PGX_EHIP;
-    }
-  }
-  return PGX_OK;
+  // scalar M and K, once: the stash is the handle's
+  return mx_scatter_once(h, d18.data(), 18, nc, 2 * nnz_s, h->stash, [&](double* stash) {
+    hipLaunchKernelGGL(k_fr_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cells, h->coords, stash);
+  }, h->Sc, 0);
 }
 
 extern "C" int pgx_fr_create(const pgx_mesh* m, const pgx_fr_problem* p, int device, pgx_fr_handle** out) {

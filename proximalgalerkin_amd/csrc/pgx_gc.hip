@@ -306,6 +306,7 @@ __global__ __launch_bounds__(256) void k_gc_l2(int nc, const int32_t* __restrict
 // element sizes: triangles P8 / P7 have 45 / 36 local nodes, quadrilaterals Q8 / Q7 81 / 64 (pgx_gc.h: affine cells of either shape)
 #define GCG_MAXU 81
 #define GCG_MAXP 64
+static_assert(GCG_MAXU + 2 * GCG_MAXP <= PAT_MAX_ENTITY_DOFS, "the mixed dofs of a cell must fit the pattern builder's buffer");
 #define GCG_TRIU 45
 #define GCG_TRIP 36
 struct GcgArgs {
@@ -594,88 +595,14 @@ static int gc_create_impl(pgx_gc_handle* h, const pgx_mesh* m, const pgx_gc_prob
     for (int a = 0; a < 6; ++a) md[a] = cd[6 * (size_t)c + a];
     for (int b = 0; b < 3; ++b) md[6 + b] = n2 + cd[6 * (size_t)c + b], md[9 + b] = n2 + nv + cd[6 * (size_t)c + b];
   };
-  // dof -> cells
-  std::vector<int64_t> dptr(ntot + 1, 0);
-  for (int c = 0; c < nc; ++c) {
-    int32_t md[12];
-    mixed(c, md);
-    for (int a = 0; a < 12; ++a) dptr[md[a] + 1]++;
-  }
-  for (int64_t i = 0; i < ntot; ++i) dptr[i + 1] += dptr[i];
-  std::vector<int32_t> dcell(dptr[ntot]);
-  {
-    std::vector<int64_t> fill(dptr.begin(), dptr.end() - 1);
-    for (int c = 0; c < nc; ++c) {
-      int32_t md[12];
-      mixed(c, md);
-      for (int a = 0; a < 12; ++a) dcell[fill[md[a]]++] = c;
-    }
-  }
   // pattern: row r couples to every mixed dof of its cells
   std::vector<int32_t>& rowptr = h->h_rowptr;
   std::vector<int32_t>& col = h->h_col;
-  rowptr.assign(ntot + 1, 0);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    std::vector<int32_t> tmp;
-    for (int64_t r = a; r < b; ++r) {
-      tmp.clear();
-      for (int64_t q = dptr[r]; q < dptr[r + 1]; ++q) {
-        int32_t md[12];
-        mixed(dcell[q], md);
-        tmp.insert(tmp.end(), md, md + 12);
-      }
-      std::sort(tmp.begin(), tmp.end());
-      rowptr[r + 1] = (int32_t)(std::unique(tmp.begin(), tmp.end()) - tmp.begin());
-    }
-  });
-  int64_t tot = 0;
-  for (int64_t r = 0; r < ntot; ++r) {
-    tot += rowptr[r + 1];
-    if (tot > 0x7fffffff) {
-      h->err = "mixed matrix exceeds int32 nnz";
-      return PGX_EINVAL;
-    }
-    rowptr[r + 1] = (int32_t)tot;
-  }
-  h->nnz = tot;
-  col.resize(tot);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    std::vector<int32_t> tmp;
-    for (int64_t r = a; r < b; ++r) {
-      tmp.clear();
-      for (int64_t q = dptr[r]; q < dptr[r + 1]; ++q) {
-        int32_t md[12];
-        mixed(dcell[q], md);
-        tmp.insert(tmp.end(), md, md + 12);
-      }
-      std::sort(tmp.begin(), tmp.end());
-      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-      std::copy(tmp.begin(), tmp.end(), col.begin() + rowptr[r]);
-    }
-  });
-  auto find = [&](int32_t r, int32_t c) -> int32_t {
-    const int32_t* b = col.data() + rowptr[r];
-    const int32_t* e = col.data() + rowptr[r + 1];
-    return (int32_t)(std::lower_bound(b, e, c) - col.data());
-  };
-  // slot kinds
-  std::vector<uint8_t> kind(tot);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    for (int64_t r = a; r < b; ++r)
-      for (int32_t k = rowptr[r]; k < rowptr[r + 1]; ++k) {
-        const int32_t c = col[k];
-        uint8_t t;
-        if (r < n2 && c < n2)
-          t = (hmask[r] || hmask[c]) ? ((r == c && hmask[r]) ? 3 : 4) : 0;
-        else if (r < n2)
-          t = hmask[r] ? 4 : 1;
-        else if (c < n2)
-          t = hmask[c] ? 4 : 1;
-        else
-          t = 2;
-        kind[k] = t;
-      }
-  });
+  const PatFind find = pattern_from_entities(ntot, nc, [&](int64_t c, int32_t* md) { return mixed((int)c, md), 12; }, rowptr, col, h->err);
+  if (!find) return PGX_EINVAL;
+  const int64_t tot = h->nnz = rowptr[ntot];
+  std::vector<uint8_t> kind;
+  saddle_kinds(ntot, n2, hmask, rowptr, col, kind);
   // destination tables
   std::vector<int32_t> d108((size_t)nc * 108), d36((size_t)nc * 36), d12((size_t)nc * 12);
   mx_par_for(nc, [&](int64_t a0, int64_t b0) {
@@ -718,22 +645,8 @@ static int gc_create_impl(pgx_gc_handle* h, const pgx_mesh* m, const pgx_gc_prob
   for (int v = 0; v < nv; ++v) nod[n2 + v] = nod[(size_t)n2 + nv + v] = v;
   // device
   GCHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix A{};
-  A.n = ntot;
-  A.rowptr = rowptr.data();
-  A.col = col.data();
-  A.n_nodes = n2;
-  A.node_of_dof = nod.data();
-  A.dim = 2;
-  A.node_coords = xy.data();
-  A.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) A.leaf_nodes = atoi(e);
-  int rc = comm ? pgx_nd_create_dist(&A, comm, h->device, (void*)h->st, &h->lu) : pgx_nd_create(&A, h->device, (void*)h->st, &h->lu);
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, n2, nod.data(), 2, xy.data(), comm);
+  if (rc) return rc;
   // the Newton matrix [[alpha K, G^T], [G, -N(psi)]] is symmetric (indefinite): L D L^T in LU clothing, half the flops (pgx_nd.h)
   pgx_nd_set_symmetric(h->lu, 1);
   GCALLOC(h->coords, 2 * (size_t)nv);
@@ -742,24 +655,17 @@ static int gc_create_impl(pgx_gc_handle* h, const pgx_mesh* m, const pgx_gc_prob
   GCALLOC(h->gbc, n2);
   GCALLOC(h->phi, n2);
   GCALLOC(h->f, n2);
-  GCALLOC(h->rowptr, ntot + 1);
-  GCALLOC(h->col, tot);
   GCALLOC(h->kind, tot);
   GCALLOC(h->stash, (size_t)36 * nc);
   GCALLOC(h->Jc, tot);
-  GCALLOC(h->Jv, tot);
-  {
-    int rcs = mx_alloc_state(h);
-    if (rcs) return rcs;
-  }
+  if ((rc = mx_alloc_state(h))) return rc;
+  if ((rc = mx_upload_pattern(h))) return rc;
   GCHIP(hipMemcpy(h->coords, m->coords, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->cdofs, cd, sizeof(int32_t) * 6 * (size_t)nc, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->mask, hmask.data(), n2, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->gbc, hg.data(), sizeof(double) * n2, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->phi, p->phi_dofs, sizeof(double) * n2, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->f, p->f_dofs, sizeof(double) * n2, hipMemcpyHostToDevice));
-  GCHIP(hipMemcpy(h->rowptr, rowptr.data(), sizeof(int32_t) * (ntot + 1), hipMemcpyHostToDevice));
-  GCHIP(hipMemcpy(h->col, col.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->kind, kind.data(), tot, hipMemcpyHostToDevice));
   {
     std::string e1 = pgx_scatter_build(d12.data(), (int64_t)12 * nc, ntot, h->allocs, &h->sc_res);
@@ -769,27 +675,11 @@ static int gc_create_impl(pgx_gc_handle* h, const pgx_mesh* m, const pgx_gc_prob
       return PGX_ENOMEM;
     }
   }
-  // constant blocks, once: park 108 entries per cell, sum per CSR position; the table and the stash are temporary
+  // constant blocks, once: park 108 entries per cell, sum per CSR position
   GCHIP(hipMemsetAsync(h->Jc, 0, sizeof(double) * tot, h->st));
-  {
-    std::vector<void*> tmp;
-    PgxScatter sc_c;
-    std::string e1 = pgx_scatter_build(d108.data(), (int64_t)108 * nc, tot, tmp, &sc_c);
-    double* st108 = nullptr;
-    hipError_t e = e1.empty() ? hipMalloc((void**)&st108, sizeof(double) * 108 * (size_t)nc) : hipErrorOutOfMemory;
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_gc_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cdofs, h->coords, h->Q, st108);
-      pgx_scatter_run(h->st, sc_c, st108, 1.0, 0, h->Jc);
-      e = hipStreamSynchronize(h->st);
-    }
-    if (st108) hipFree(st108);
-    for (void* q : tmp) hipFree(q);
-    if (e != hipSuccess) {
-      h->err = std::string("constant Jacobian blocks: ") + (e1.empty() ? hipGetErrorString(e) : e1.c_str());
-      return PGX_EHIP;
-    }
-  }
-  return PGX_OK;
+  return mx_scatter_once(h, d108.data(), 108, nc, tot, nullptr, [&](double* stash) {
+    hipLaunchKernelGGL(k_gc_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cdofs, h->coords, h->Q, stash);
+  }, h->Jc, 0);
 }
 
 static GcgArgs gcg_args(const pgx_gc_handle* h) {
@@ -822,11 +712,10 @@ static int gcg_create_impl(pgx_gc_handle* h, const pgx_gc_spaces* sp, const pgx_
       h->err = "latent cell dof out of range";
       return PGX_EINVAL;
     }
-  for (size_t k = 0; k < 3 * (size_t)nc; ++k)
-    if (sp->cells[k] < 0 || sp->cells[k] >= nvert) {
-      h->err = "cell vertex out of range";
-      return PGX_EINVAL;
-    }
+  if (const char* e = check_cells(sp->cells, 3, nc, nvert)) {
+    h->err = e;
+    return PGX_EINVAL;
+  }
   std::vector<uint8_t> hmask(n2, 0);
   std::vector<double> hg(n2, 0.0);
   for (int k = 0; k < p->n_bc; ++k) {
@@ -842,83 +731,13 @@ static int gcg_create_impl(pgx_gc_handle* h, const pgx_gc_spaces* sp, const pgx_
     for (int a = 0; a < NU; ++a) md[a] = cdu[(size_t)NU * c + a];
     for (int b = 0; b < NP; ++b) md[NU + b] = n2 + cdp[(size_t)NP * c + b], md[NU + NP + b] = n2 + nv + cdp[(size_t)NP * c + b];
   };
-  std::vector<int64_t> dptr(ntot + 1, 0);
-  {
-    std::vector<int32_t> md(ND);
-    for (int c = 0; c < nc; ++c) {
-      mixed(c, md.data());
-      for (int a = 0; a < ND; ++a) dptr[md[a] + 1]++;
-    }
-  }
-  for (int64_t i = 0; i < ntot; ++i) dptr[i + 1] += dptr[i];
-  std::vector<int32_t> dcell(dptr[ntot]);
-  {
-    std::vector<int64_t> fill(dptr.begin(), dptr.end() - 1);
-    std::vector<int32_t> md(ND);
-    for (int c = 0; c < nc; ++c) {
-      mixed(c, md.data());
-      for (int a = 0; a < ND; ++a) dcell[fill[md[a]]++] = c;
-    }
-  }
   std::vector<int32_t>& rowptr = h->h_rowptr;
   std::vector<int32_t>& col = h->h_col;
-  rowptr.assign(ntot + 1, 0);
-  auto gather_row = [&](int64_t r, std::vector<int32_t>& tmp, std::vector<int32_t>& md) {
-    tmp.clear();
-    for (int64_t q = dptr[r]; q < dptr[r + 1]; ++q) {
-      mixed(dcell[q], md.data());
-      tmp.insert(tmp.end(), md.begin(), md.end());
-    }
-    std::sort(tmp.begin(), tmp.end());
-    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-  };
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    std::vector<int32_t> tmp, md(ND);
-    for (int64_t r = a; r < b; ++r) {
-      gather_row(r, tmp, md);
-      rowptr[r + 1] = (int32_t)tmp.size();
-    }
-  });
-  int64_t tot = 0;
-  for (int64_t r = 0; r < ntot; ++r) {
-    tot += rowptr[r + 1];
-    if (tot > 0x7fffffff) {
-      h->err = "mixed matrix exceeds int32 nnz";
-      return PGX_EINVAL;
-    }
-    rowptr[r + 1] = (int32_t)tot;
-  }
-  h->nnz = tot;
-  col.resize(tot);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    std::vector<int32_t> tmp, md(ND);
-    for (int64_t r = a; r < b; ++r) {
-      gather_row(r, tmp, md);
-      std::copy(tmp.begin(), tmp.end(), col.begin() + rowptr[r]);
-    }
-  });
-  auto find = [&](int32_t r, int32_t c) -> int32_t {
-    const int32_t* b = col.data() + rowptr[r];
-    const int32_t* e = col.data() + rowptr[r + 1];
-    return (int32_t)(std::lower_bound(b, e, c) - col.data());
-  };
-  std::vector<uint8_t> kind(tot);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    for (int64_t r = a; r < b; ++r)
-      for (int32_t k = rowptr[r]; k < rowptr[r + 1]; ++k) {
-        const int32_t c = col[k];
-        uint8_t t;
-        if (r < n2 && c < n2)
-          t = (hmask[r] || hmask[c]) ? ((r == c && hmask[r]) ? 3 : 4) : 0;
-        else if (r < n2)
-          t = hmask[r] ? 4 : 1;
-        else if (c < n2)
-          t = hmask[c] ? 4 : 1;
-        else
-          t = 2;
-        kind[k] = t;
-      }
-  });
+  const PatFind find = pattern_from_entities(ntot, nc, [&](int64_t c, int32_t* md) { return mixed((int)c, md), ND; }, rowptr, col, h->err);
+  if (!find) return PGX_EINVAL;
+  const int64_t tot = h->nnz = rowptr[ntot];
+  std::vector<uint8_t> kind;
+  saddle_kinds(ntot, n2, hmask, rowptr, col, kind);
   const size_t nsc = (size_t)NU * NU + 4 * (size_t)NP * NU, nsn = 4 * (size_t)NP * NP;
   if ((double)(nsc + nsn + ND) * nc * 12.0 > 96e9) {
     h->err = "mesh too large for the one-pass assembly at this degree";
@@ -955,22 +774,8 @@ static int gcg_create_impl(pgx_gc_handle* h, const pgx_gc_spaces* sp, const pgx_
   for (int i = 0; i < n2; ++i) nod[i] = i;
   for (int v = 0; v < nv; ++v) nod[n2 + v] = nod[(size_t)n2 + nv + v] = n2 + v;
   GCHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix Am{};
-  Am.n = ntot;
-  Am.rowptr = rowptr.data();
-  Am.col = col.data();
-  Am.n_nodes = n2 + nv;
-  Am.node_of_dof = nod.data();
-  Am.dim = 2;
-  Am.node_coords = xy.data();
-  Am.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) Am.leaf_nodes = atoi(e);
-  int rc = comm ? pgx_nd_create_dist(&Am, comm, h->device, (void*)h->st, &h->lu) : pgx_nd_create(&Am, h->device, (void*)h->st, &h->lu);
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, n2 + nv, nod.data(), 2, xy.data(), comm);
+  if (rc) return rc;
   pgx_nd_set_symmetric(h->lu, 1);  // (symmetric Newton matrix, as above)
   const int nq = p->nq;
   GCALLOC(h->coords, 2 * (size_t)nvert);
@@ -984,16 +789,11 @@ static int gcg_create_impl(pgx_gc_handle* h, const pgx_gc_spaces* sp, const pgx_
   GCALLOC(h->gbc, n2);
   GCALLOC(h->phi, n2);
   GCALLOC(h->f, n2);
-  GCALLOC(h->rowptr, ntot + 1);
-  GCALLOC(h->col, tot);
   GCALLOC(h->kind, tot);
   GCALLOC(h->stash, std::max(nsn, (size_t)ND) * nc);
   GCALLOC(h->Jc, tot);
-  GCALLOC(h->Jv, tot);
-  {
-    int rcs = mx_alloc_state(h);
-    if (rcs) return rcs;
-  }
+  if ((rc = mx_alloc_state(h))) return rc;
+  if ((rc = mx_upload_pattern(h))) return rc;
   GCHIP(hipMemcpy(h->coords, sp->coords, sizeof(double) * 2 * nvert, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->cells3, sp->cells, sizeof(int32_t) * 3 * (size_t)nc, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->cdofs, cdu, sizeof(int32_t) * (size_t)NU * nc, hipMemcpyHostToDevice));
@@ -1005,8 +805,6 @@ static int gcg_create_impl(pgx_gc_handle* h, const pgx_gc_spaces* sp, const pgx_
   GCHIP(hipMemcpy(h->gbc, hg.data(), sizeof(double) * n2, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->phi, p->phi_dofs, sizeof(double) * n2, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->f, p->f_dofs, sizeof(double) * n2, hipMemcpyHostToDevice));
-  GCHIP(hipMemcpy(h->rowptr, rowptr.data(), sizeof(int32_t) * (ntot + 1), hipMemcpyHostToDevice));
-  GCHIP(hipMemcpy(h->col, col.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   GCHIP(hipMemcpy(h->kind, kind.data(), tot, hipMemcpyHostToDevice));
   {
     std::string e1 = pgx_scatter_build(dR.data(), (int64_t)ND * nc, ntot, h->allocs, &h->sc_res);
@@ -1017,25 +815,9 @@ static int gcg_create_impl(pgx_gc_handle* h, const pgx_gc_spaces* sp, const pgx_
     }
   }
   GCHIP(hipMemsetAsync(h->Jc, 0, sizeof(double) * tot, h->st));
-  {
-    std::vector<void*> tmp;
-    PgxScatter sc_c;
-    std::string e1 = pgx_scatter_build(dC.data(), (int64_t)nsc * nc, tot, tmp, &sc_c);
-    double* stc = nullptr;
-    hipError_t e = e1.empty() ? hipMalloc((void**)&stc, sizeof(double) * nsc * nc) : hipErrorOutOfMemory;
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_gcg_const, dim3((nc + 63) / 64), dim3(64), 0, h->st, gcg_args(h), stc);
-      pgx_scatter_run(h->st, sc_c, stc, 1.0, 0, h->Jc);
-      e = hipStreamSynchronize(h->st);
-    }
-    if (stc) hipFree(stc);
-    for (void* q : tmp) hipFree(q);
-    if (e != hipSuccess) {
-      h->err = std::string("constant Jacobian blocks: ") + (e1.empty() ? hipGetErrorString(e) : e1.c_str());
-      return PGX_EHIP;
-    }
-  }
-  return PGX_OK;
+  return mx_scatter_once(h, dC.data(), (int64_t)nsc, nc, tot, nullptr, [&](double* stash) {
+    hipLaunchKernelGGL(k_gcg_const, dim3((nc + 63) / 64), dim3(64), 0, h->st, gcg_args(h), stash);
+  }, h->Jc, 0);
 }
 
 extern "C" int pgx_gc_create_general(const pgx_gc_spaces* sp, const pgx_gc_problem* p, int device, pgx_gc_handle** out) {

@@ -214,22 +214,8 @@ static int ic_create_impl(pgx_ic_handle* h, const pgx_ic_problem* p) {
     xy[2 * (size_t)v] = p->x[v];
   }
   MXHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix A{};
-  A.n = ntot;
-  A.rowptr = rowptr.data();
-  A.col = col.data();
-  A.n_nodes = nv;
-  A.node_of_dof = nod.data();
-  A.dim = 2;
-  A.node_coords = xy.data();
-  A.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) A.leaf_nodes = atoi(e);
-  int rc = pgx_nd_create(&A, h->device, (void*)h->st, &h->lu);
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, nv, nod.data(), 2, xy.data());
+  if (rc) return rc;
   const size_t nqc = (size_t)nc * p->nq;
   MXALLOC(h->xc, nv);
   MXALLOC(h->mask, nv);

@@ -2,7 +2,10 @@
 // pgx_ic.hip, pgx_mp.hip): the handle base with its mixed CSR Newton matrix on the device and state vectors, the allocation / error / timing
 // helpers, and the prototypes of the shared driver in pgx_mixed.hip - fixed-shape reductions, the SNES-mirroring Newton drivers
 // (newtonls with linesearch none / bt / l2), their linear solve = sparse LU (pgx_nd) + iterative refinement on the exact
-// operator, and the C entry points every family forwards to.  A family keeps only its assembly kernels and its create path.
+// operator, and the C entry points every family forwards to.  The create paths share their steps too: the host pattern builders
+// (pgx_pattern.h), the sparse-LU setup mx_lu_create, the pattern upload mx_upload_pattern and the one-off constant-block pass
+// mx_scatter_once; the P1-triangle families share their device geometry and quadrature table (pgx_tri.h).  A family keeps only
+// its assembly kernels, its block layout and destination tables, and the order of these steps in its create path.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +21,7 @@
 #include "../../include/pgx.h"
 #include "../../include/pgx_nd.h"
 #include "pgx_comm.h"
+#include "pgx_pattern.h"
 #include "pgx_scope.h"
 
 struct MixedBase {
@@ -131,6 +135,16 @@ struct MxTimer {
 #pragma GCC visibility push(hidden)
 void mx_par_for(int64_t n, const std::function<void(int64_t, int64_t)>& fn);  // host threads over [0, n) in chunks
 int mx_alloc_state(MixedBase* h);  // state vectors, reduction scratch, events; the stream must exist
+// The sparse LU of the pattern h->h_rowptr / h->h_col on the handle's stream (which must exist): nested dissection over n_nodes
+// nodes with coordinates node_coords[n_nodes][dim], node_of_dof[ntot]; distributed over comm if given.  Sets h->lu, or h->err.
+// Symmetry (pgx_nd_set_symmetric) and the row flip lu_flip_from are the family's, after the call.
+int mx_lu_create(MixedBase* h, int32_t n_nodes, const int32_t* node_of_dof, int dim, const double* node_coords, pgx_comm* comm = nullptr);
+int mx_upload_pattern(MixedBase* h);  // h->rowptr, h->col <- h->h_rowptr, h->h_col; h->Jv allocated [nnz], not cleared
+// Constant blocks, once, deterministic: launch(stash) parks n_slots values per entity slot-major, table[slot * n_entities + entity]
+// names their destinations among n_dest (< 0: dropped), dst receives the sums (accumulate: is added to).  The scatter table is
+// temporary, and so is the stash unless the caller lends one.  Synchronises the stream.
+int mx_scatter_once(MixedBase* h, const int32_t* table, int64_t n_slots, int64_t n_entities, int64_t n_dest, double* stash_or_null,
+                    const std::function<void(double*)>& launch, double* dst, int accumulate);
 int mx_in(MixedBase* h, double* dst, const double* src, int64_t len = 0);  // host -> device, len = 0: ntot
 int mx_norm(MixedBase* h, const double* v, double* out, int64_t len = 0);   // 2-norm (rank 0's value on every rank)
 void mx_axpby(MixedBase* h, double a, const double* x, double b, double* y, int64_t len = 0);  // y = a x + b y on the stream

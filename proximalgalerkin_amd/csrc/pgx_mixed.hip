@@ -6,6 +6,7 @@
 // examples/06_gradient_constraints/gradient_constraint_dolfinx.py:116-131 and examples/02_signorini/
 // signorini_dolfinx.py:271-291,331-335; callback contract src/lvpp/problem.py:54-77,114-124.
 #include "pgx_mixed.h"
+#include "pgx_scatter.h"
 
 // y = A x (ABS: y = |A| |x|), 16 lanes per row
 template <bool ABS>
@@ -78,18 +79,7 @@ static __global__ void k_mx_axpby(int64_t len, double a, const double* __restric
   if (i < len) y[i] = a * x[i] + (b == 0.0 ? 0.0 : b * y[i]);
 }
 
-void mx_par_for(int64_t n, const std::function<void(int64_t, int64_t)>& fn) {
-  unsigned T = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (n < 20000) T = 1;
-  std::vector<std::thread> th;
-  const int64_t chunk = (n + T - 1) / T;
-  for (unsigned t = 0; t < T; ++t) {
-    const int64_t a = t * chunk, b = std::min<int64_t>(n, a + chunk);
-    if (a >= b) break;
-    th.emplace_back([=, &fn] { fn(a, b); });
-  }
-  for (auto& t : th) t.join();
-}
+void mx_par_for(int64_t n, const std::function<void(int64_t, int64_t)>& fn) { pat_par_for(n, fn); }
 
 // d_out[0] <- rank 0's value on every rank (no-op on a single handle)
 static int mx_sync_scalar(MixedBase* h) {
@@ -168,6 +158,56 @@ int mx_alloc_state(MixedBase* h) {
   if (const char* e = pgx_tune("PGX_LAZY_LU")) h->lazy_lu = atoi(e);
   if (const char* e = pgx_tune("PGX_LAZY_BUDGET")) h->lazy_budget = std::max(1, atoi(e));
   if (const char* e = pgx_tune("PGX_MX_REFINE_ETA")) h->refine_eta = atof(e);
+  return PGX_OK;
+}
+
+int mx_lu_create(MixedBase* h, int32_t n_nodes, const int32_t* node_of_dof, int dim, const double* node_coords, pgx_comm* comm) {
+  pgx_nd_matrix A{};
+  A.n = h->ntot;
+  A.rowptr = h->h_rowptr.data();
+  A.col = h->h_col.data();
+  A.n_nodes = n_nodes;
+  A.node_of_dof = node_of_dof;
+  A.dim = dim;
+  A.node_coords = node_coords;
+  A.leaf_nodes = 0;
+  if (const char* e = pgx_tune("PGX_ND_LEAF")) A.leaf_nodes = atoi(e);
+  const int rc = comm ? pgx_nd_create_dist(&A, comm, h->device, (void*)h->st, &h->lu) : pgx_nd_create(&A, h->device, (void*)h->st, &h->lu);
+  if (rc) {
+    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
+    h->lu = nullptr;
+  }
+  return rc;
+}
+
+int mx_upload_pattern(MixedBase* h) {
+  MXALLOC(h->rowptr, h->ntot + 1);
+  MXALLOC(h->col, h->nnz);
+  MXALLOC(h->Jv, h->nnz);
+  MXHIP(hipMemcpy(h->rowptr, h->h_rowptr.data(), sizeof(int32_t) * (h->ntot + 1), hipMemcpyHostToDevice));
+  MXHIP(hipMemcpy(h->col, h->h_col.data(), sizeof(int32_t) * h->nnz, hipMemcpyHostToDevice));
+  return PGX_OK;
+}
+
+int mx_scatter_once(MixedBase* h, const int32_t* table, int64_t n_slots, int64_t n_entities, int64_t n_dest, double* stash_or_null,
+                    const std::function<void(double*)>& launch, double* dst, int accumulate) {
+  std::vector<void*> tmp;
+  PgxScatter sc;
+  const std::string e1 = pgx_scatter_build(table, n_slots * n_entities, n_dest, tmp, &sc);
+  double *own = nullptr, *stash = stash_or_null;
+  hipError_t e = !e1.empty() ? hipErrorOutOfMemory : stash ? hipSuccess : hipMalloc((void**)&own, sizeof(double) * (size_t)(n_slots * n_entities));
+  if (e == hipSuccess) {
+    if (!stash) stash = own;
+    launch(stash);
+    pgx_scatter_run(h->st, sc, stash, 1.0, accumulate, dst);
+    e = hipStreamSynchronize(h->st);
+  }
+  if (own) hipFree(own);
+  for (void* q : tmp) hipFree(q);
+  if (e != hipSuccess) {
+    h->err = std::string("constant Jacobian blocks: ") + (e1.empty() ? hipGetErrorString(e) : e1.c_str());
+    return PGX_EHIP;
+  }
   return PGX_OK;
 }
 

@@ -12,13 +12,11 @@
 #include "../../include/pgx_mp.h"
 #include "pgx_mixed.h"
 #include "pgx_scatter.h"
+#include "pgx_tri.h"
 
 #define MP_MAXQ 16
 #define MP_NS 4
-struct MpQuad {
-  double N[MP_MAXQ][3], w[MP_MAXQ];
-  int nq;
-};
+using MpQuad = TriQuad<MP_MAXQ>;
 
 static thread_local std::string g_mp_error;
 
@@ -45,23 +43,12 @@ struct pgx_mp_handle : MixedBase {
 
 extern "C" const char* pgx_mp_last_error(const pgx_mp_handle* h) { return h ? h->err.c_str() : g_mp_error.c_str(); }
 
-struct MpGeom {
-  double G[3][2];  // physical P1 gradients
-  double adet;
+struct MpGeom : TriGeom {
   double epsh2;  // epsilon^2 = (2 h)^2, h = 2 Circumradius (:53-54)
 };
 __device__ inline MpGeom mp_geom(const double* __restrict__ coords, const int32_t* __restrict__ cv) {
-  MpGeom g;
   double X[3][2];
-  for (int a = 0; a < 3; ++a) X[a][0] = coords[2 * (size_t)cv[a]], X[a][1] = coords[2 * (size_t)cv[a] + 1];
-  const double j00 = X[1][0] - X[0][0], j10 = X[1][1] - X[0][1];
-  const double j01 = X[2][0] - X[0][0], j11 = X[2][1] - X[0][1];
-  const double det = j00 * j11 - j01 * j10;
-  const double i00 = j11 / det, i01 = -j01 / det, i10 = -j10 / det, i11 = j00 / det;
-  g.G[1][0] = i00, g.G[1][1] = i01;
-  g.G[2][0] = i10, g.G[2][1] = i11;
-  g.G[0][0] = -(i00 + i10), g.G[0][1] = -(i01 + i11);
-  g.adet = fabs(det);
+  MpGeom g{tri_geom(coords, cv, X), 0.0};
   double e[3];
   for (int k = 0; k < 3; ++k) {
     const double dx = X[(k + 1) % 3][0] - X[(k + 2) % 3][0], dy = X[(k + 1) % 3][1] - X[(k + 2) % 3][1];
@@ -71,7 +58,6 @@ __device__ inline MpGeom mp_geom(const double* __restrict__ coords, const int32_
   g.epsh2 = (4.0 * R) * (4.0 * R);
   return g;
 }
-__device__ inline double mp_me(double area, int a, int b) { return area / 12.0 * (a == b ? 2.0 : 1.0); }
 // softmax of the species at one quadrature point, shifted by the maximum: finite for every finite psi
 __device__ inline void mp_softmax(const double p[3][MP_NS], const double N[3], double S[MP_NS]) {
   double pq[MP_NS], mx = -INFINITY;
@@ -110,7 +96,7 @@ __global__ __launch_bounds__(128) void k_mp_residual(int nc, int nv, const int32
     for (int m = 0; m < MP_NS; ++m) {
       double mu = 0, mdu = 0, mz = 0, mp = 0, mdp = 0, kz = 0, ku = 0;
       for (int b = 0; b < 3; ++b) {
-        const double me = mp_me(area, a, b);
+        const double me = tri_me(area, a, b);
         mu += me * u[b][m], mdu += me * du[b][m], mz += me * z[b][m], mp += me * p[b][m], mdp += me * dp[b][m];
         kz += Ke[a][b] * z[b][m], ku += Ke[a][b] * u[b][m];
       }
@@ -143,7 +129,7 @@ __global__ __launch_bounds__(128) void k_mp_const(int nc, const int32_t* __restr
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) {
       const double k = area * (g.G[a][0] * g.G[b][0] + g.G[a][1] * g.G[b][1]);
-      stash[(size_t)(a * 3 + b) * nc + c] = mp_me(area, a, b);
+      stash[(size_t)(a * 3 + b) * nc + c] = tri_me(area, a, b);
       stash[(size_t)(9 + a * 3 + b) * nc + c] = k;
       stash[(size_t)(18 + a * 3 + b) * nc + c] = g.epsh2 * k;
     }
@@ -185,7 +171,7 @@ __global__ __launch_bounds__(128) void k_mp_jac_w(int nc, int nv, const int32_t*
     for (int m = 0; m < MP_NS; ++m)
       for (int k = 0; k < MP_NS; ++k) J[m][k] -= wd * ((m == k ? S[m] : 0.0) - S[m] * S[k]);
   }
-  const double em = eps * mp_me(0.5 * g.adet, a, b);
+  const double em = eps * tri_me(0.5 * g.adet, a, b);
   for (int m = 0; m < MP_NS; ++m)
     for (int k = 0; k < MP_NS; ++k)
       stash[(size_t)((a * MP_NS + m) * 12 + b * MP_NS + k) * nc + c] = m == k ? J[m][k] - em : J[m][k];
@@ -215,7 +201,7 @@ __global__ __launch_bounds__(256) void k_mp_l2(int nc, const int32_t* __restrict
       double d[3];
       for (int a = 0; a < 3; ++a) d[a] = x[(size_t)MP_NS * cv[a] + m] - xk[(size_t)MP_NS * cv[a] + m];
       for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) s += mp_me(area, a, b) * d[a] * d[b];
+        for (int b = 0; b < 3; ++b) s += tri_me(area, a, b) * d[a] * d[b];
     }
   }
   sh[threadIdx.x] = s;
@@ -275,16 +261,11 @@ static int mp_create_impl(pgx_mp_handle* h, const pgx_mesh* m, const pgx_mp_prob
   const int64_t nb = (int64_t)MP_NS * nv, ntot = 3 * nb;
   h->nv = nv, h->nc = nc, h->ntot = ntot;
   h->tau = p->tau, h->eps = p->eps;
-  h->Q.nq = p->nq;
-  for (int q = 0; q < p->nq; ++q) {
-    const double X = p->qpts[2 * q], Y = p->qpts[2 * q + 1];
-    h->Q.N[q][0] = 1.0 - X - Y, h->Q.N[q][1] = X, h->Q.N[q][2] = Y, h->Q.w[q] = p->qwts[q];
+  h->Q.fill(p->qpts, p->qwts, p->nq);
+  if (const char* e = check_cells(m->cells, 3, nc, nv)) {
+    h->err = e;
+    return PGX_EINVAL;
   }
-  for (size_t k = 0; k < 3 * (size_t)nc; ++k)
-    if (m->cells[k] < 0 || m->cells[k] >= nv) {
-      h->err = "cell vertex out of range";
-      return PGX_EINVAL;
-    }
   std::vector<double> hwv(nv, 0.0);
   for (int c = 0; c < nc; ++c) {
     const int32_t* cv = m->cells + 3 * (size_t)c;
@@ -299,31 +280,8 @@ static int mp_create_impl(pgx_mp_handle* h, const pgx_mesh* m, const pgx_mp_prob
     for (int a = 0; a < 3; ++a) hwv[cv[a]] += 0.5 * std::fabs(det) / 3.0;
   }
   // scalar P1 pattern (vertex adjacency incl. self)
-  std::vector<int64_t> vptr(nv + 1, 0);
-  for (size_t k = 0; k < 3 * (size_t)nc; ++k) vptr[m->cells[k] + 1]++;
-  for (int v = 0; v < nv; ++v) vptr[v + 1] += vptr[v];
-  std::vector<int32_t> vcell(vptr[nv]);
-  {
-    std::vector<int64_t> fill(vptr.begin(), vptr.end() - 1);
-    for (int c = 0; c < nc; ++c)
-      for (int a = 0; a < 3; ++a) vcell[fill[m->cells[3 * (size_t)c + a]]++] = c;
-  }
-  std::vector<int32_t> sptr(nv + 1, 0), scol;
-  {
-    std::vector<std::vector<int32_t>> rows(nv);
-    mx_par_for(nv, [&](int64_t a, int64_t b) {
-      for (int64_t v = a; v < b; ++v) {
-        auto& r = rows[v];
-        for (int64_t q = vptr[v]; q < vptr[v + 1]; ++q)
-          for (int k = 0; k < 3; ++k) r.push_back(m->cells[3 * (size_t)vcell[q] + k]);
-        std::sort(r.begin(), r.end());
-        r.erase(std::unique(r.begin(), r.end()), r.end());
-      }
-    });
-    for (int v = 0; v < nv; ++v) sptr[v + 1] = sptr[v] + (int32_t)rows[v].size();
-    scol.resize(sptr[nv]);
-    for (int v = 0; v < nv; ++v) std::copy(rows[v].begin(), rows[v].end(), scol.begin() + sptr[v]);
-  }
+  std::vector<int32_t> sptr, scol;
+  p1_adjacency(nv, nc, m->cells, false, sptr, scol);  // false, as this family always had it: a vertex of no cell has empty rows
   const int64_t nnz_s = sptr[nv];
   // per vertex pair and species: v and y rows 3 entries (u, z, psi), w rows 2 + 4 (u, z, psi of every species)
   if (48 * nnz_s > 0x7fffffff) {
@@ -396,22 +354,8 @@ static int mp_create_impl(pgx_mp_handle* h, const pgx_mesh* m, const pgx_mp_prob
   std::vector<int32_t> nod(ntot);
   for (int64_t i = 0; i < ntot; ++i) nod[i] = (int32_t)((i % nb) / MP_NS);
   MXHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix A{};
-  A.n = ntot;
-  A.rowptr = rowptr.data();
-  A.col = col.data();
-  A.n_nodes = nv;
-  A.node_of_dof = nod.data();
-  A.dim = 2;
-  A.node_coords = m->coords;
-  A.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) A.leaf_nodes = atoi(e);
-  int rc = pgx_nd_create(&A, h->device, (void*)h->st, &h->lu);
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, nv, nod.data(), 2, m->coords);
+  if (rc) return rc;
   MXALLOC(h->coords, 2 * (size_t)nv);
   MXALLOC(h->cells, 3 * (size_t)nc);
   MXALLOC(h->uprev, nb);
@@ -419,17 +363,13 @@ static int mp_create_impl(pgx_mp_handle* h, const pgx_mesh* m, const pgx_mp_prob
   MXALLOC(h->mass, MP_NS);
   MXALLOC(h->stash, 144 * (size_t)nc);
   MXALLOC(h->Sc, 3 * nnz_s);
-  MXALLOC(h->rowptr, ntot + 1);
-  MXALLOC(h->col, tot);
   MXALLOC(h->kind, tot);
   MXALLOC(h->src, tot);
-  MXALLOC(h->Jv, tot);
   if ((rc = mx_alloc_state(h))) return rc;
+  if ((rc = mx_upload_pattern(h))) return rc;
   MXHIP(hipMemcpy(h->coords, m->coords, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->cells, m->cells, sizeof(int32_t) * 3 * (size_t)nc, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->wv, hwv.data(), sizeof(double) * nv, hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->rowptr, rowptr.data(), sizeof(int32_t) * (ntot + 1), hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->col, col.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->kind, kind.data(), tot, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->src, src.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   MXHIP(hipMemsetAsync(h->uprev, 0, sizeof(double) * nb, h->st));
@@ -443,23 +383,10 @@ static int mp_create_impl(pgx_mp_handle* h, const pgx_mesh* m, const pgx_mp_prob
       return PGX_ENOMEM;
     }
   }
-  {  // scalar M, K, K_eps, once, deterministic: table is temporary, the stash is the handle's
-    std::vector<void*> tmp;
-    PgxScatter sc_c;
-    std::string e1 = pgx_scatter_build(d27.data(), (int64_t)27 * nc, 3 * nnz_s, tmp, &sc_c);
-    hipError_t e = hipErrorOutOfMemory;
-    if (e1.empty()) {
-      hipLaunchKernelGGL(k_mp_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cells, h->coords, h->stash);
-      pgx_scatter_run(h->st, sc_c, h->stash, 1.0, 0, h->Sc);
-      e = hipStreamSynchronize(h->st);
-    }
-    for (void* q : tmp) hipFree(q);
-    if (e != hipSuccess) {
-      h->err = std::string("constant Jacobian blocks: ") + (e1.empty() ? hipGetErrorString(e) : e1.c_str());
-      return PGX_EHIP;
-    }
-  }
-  return PGX_OK;
+  // scalar M, K, K_eps, once: the stash is the handle's
+  return mx_scatter_once(h, d27.data(), 27, nc, 3 * nnz_s, h->stash, [&](double* stash) {
+    hipLaunchKernelGGL(k_mp_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cells, h->coords, stash);
+  }, h->Sc, 0);
 }
 
 extern "C" int pgx_mp_create(const pgx_mesh* m, const pgx_mp_problem* p, int device, pgx_mp_handle** out) {

@@ -9,12 +9,10 @@
 #include "../../include/pgx_qmy.h"
 #include "pgx_mixed.h"
 #include "pgx_scatter.h"
+#include "pgx_tri.h"
 
 #define QM_MAXQ 36
-struct QmQuad {  // kernel argument: the loop index is uniform, so the table is read with scalar loads
-  double N[QM_MAXQ][3], w[QM_MAXQ];
-  int nq;
-};
+using QmQuad = TriQuad<QM_MAXQ>;
 
 static thread_local std::string g_qmy_error;
 
@@ -40,25 +38,6 @@ struct pgx_qmy_handle : MixedBase {
 
 extern "C" const char* pgx_qmy_last_error(const pgx_qmy_handle* h) { return h ? h->err.c_str() : g_qmy_error.c_str(); }
 
-struct QmGeom {
-  double G[3][2];  // physical P1 gradients
-  double adet;
-};
-__device__ inline QmGeom qm_geom(const double* __restrict__ coords, const int32_t* __restrict__ cv) {
-  QmGeom g;
-  double X[3][2];
-  for (int a = 0; a < 3; ++a) X[a][0] = coords[2 * (size_t)cv[a]], X[a][1] = coords[2 * (size_t)cv[a] + 1];
-  const double j00 = X[1][0] - X[0][0], j10 = X[1][1] - X[0][1];
-  const double j01 = X[2][0] - X[0][0], j11 = X[2][1] - X[0][1];
-  const double det = j00 * j11 - j01 * j10;
-  const double i00 = j11 / det, i01 = -j01 / det, i10 = -j10 / det, i11 = j00 / det;
-  g.G[1][0] = i00, g.G[1][1] = i01;
-  g.G[2][0] = i10, g.G[2][1] = i11;
-  g.G[0][0] = -(i00 + i10), g.G[0][1] = -(i01 + i11);
-  g.adet = fabs(det);
-  return g;
-}
-
 // R_u = (grad u, grad v) - (f, v) + gamma (max(0, d), v);  R_T = (grad T, grad R) + (T, R) - (g(s), R)   (MY:77-81)
 __global__ __launch_bounds__(128) void k_qm_residual(int nc, int nv, const int32_t* __restrict__ cells,
                                                      const double* __restrict__ coords, const uint8_t* __restrict__ mask,
@@ -68,7 +47,7 @@ __global__ __launch_bounds__(128) void k_qm_residual(int nc, int nv, const int32
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const int32_t* cv = cells + 3 * (size_t)c;
-  const QmGeom g = qm_geom(coords, cv);
+  const TriGeom g = tri_geom(coords, cv);
   double u[3], T[3], P[3], p[3];
   for (int a = 0; a < 3; ++a) {
     const int v = cv[a];
@@ -120,7 +99,7 @@ __global__ __launch_bounds__(128) void k_qm_const(int nc, const int32_t* __restr
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const int32_t* cv = cells + 3 * (size_t)c;
-  const QmGeom g = qm_geom(coords, cv);
+  const TriGeom g = tri_geom(coords, cv);
   double Ke[3][3], Me[3][3];
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) {
@@ -219,7 +198,7 @@ __global__ __launch_bounds__(256) void k_qm_functionals(int nc, int nv, const in
   double se = 0.0, sp = 0.0;
   for (int c = blockIdx.x * 256 + threadIdx.x; c < nc; c += MX_RED * 256) {
     const int32_t* cv = cells + 3 * (size_t)c;
-    const QmGeom g = qm_geom(coords, cv);
+    const TriGeom g = tri_geom(coords, cv);
     double u[3], T[3], P[3], p[3], gu[2] = {0, 0};
     for (int a = 0; a < 3; ++a) {
       const int v = cv[a];
@@ -258,7 +237,7 @@ __global__ __launch_bounds__(256) void k_qm_cauchy(int nc, const int32_t* __rest
   double s = 0.0;
   for (int c = blockIdx.x * 256 + threadIdx.x; c < nc; c += MX_RED * 256) {
     const int32_t* cv = cells + 3 * (size_t)c;
-    const QmGeom g = qm_geom(coords, cv);
+    const TriGeom g = tri_geom(coords, cv);
     double d[3], gd[2] = {0, 0};
     for (int a = 0; a < 3; ++a) {
       d[a] = mask[cv[a]] ? 0.0 : x[cv[a]] - xk[cv[a]];
@@ -312,16 +291,11 @@ static int qmy_create_impl(pgx_qmy_handle* h, const pgx_mesh* m, const pgx_qmy_p
   const int64_t ntot = 2 * (int64_t)nv;
   h->nv = nv, h->nc = nc, h->ntot = ntot;
   h->f = p->f, h->knee = p->q;
-  h->Q.nq = p->nq;
-  for (int q = 0; q < p->nq; ++q) {
-    const double X = p->qpts[2 * q], Y = p->qpts[2 * q + 1];
-    h->Q.N[q][0] = 1.0 - X - Y, h->Q.N[q][1] = X, h->Q.N[q][2] = Y, h->Q.w[q] = p->qwts[q];
+  h->Q.fill(p->qpts, p->qwts, p->nq);
+  if (const char* e = check_cells(m->cells, 3, nc, nv)) {
+    h->err = e;
+    return PGX_EINVAL;
   }
-  for (size_t k = 0; k < 3 * (size_t)nc; ++k)
-    if (m->cells[k] < 0 || m->cells[k] >= nv) {
-      h->err = "cell vertex out of range";
-      return PGX_EINVAL;
-    }
   std::vector<uint8_t> hmask(nv, 0);
   for (int k = 0; k < p->n_bc; ++k) {
     if (p->bc_dofs[k] < 0 || p->bc_dofs[k] >= nv) {
@@ -331,32 +305,8 @@ static int qmy_create_impl(pgx_qmy_handle* h, const pgx_mesh* m, const pgx_qmy_p
     hmask[p->bc_dofs[k]] = 1;
   }
   // scalar P1 pattern (vertex adjacency incl. self), then 2 x 2 blocks
-  std::vector<int64_t> vptr(nv + 1, 0);
-  for (size_t k = 0; k < 3 * (size_t)nc; ++k) vptr[m->cells[k] + 1]++;
-  for (int v = 0; v < nv; ++v) vptr[v + 1] += vptr[v];
-  std::vector<int32_t> vcell(vptr[nv]);
-  {
-    std::vector<int64_t> fill(vptr.begin(), vptr.end() - 1);
-    for (int c = 0; c < nc; ++c)
-      for (int a = 0; a < 3; ++a) vcell[fill[m->cells[3 * (size_t)c + a]]++] = c;
-  }
-  std::vector<int32_t> sptr(nv + 1, 0), scol;
-  {
-    std::vector<std::vector<int32_t>> rows(nv);
-    mx_par_for(nv, [&](int64_t a, int64_t b) {
-      for (int64_t v = a; v < b; ++v) {
-        auto& r = rows[v];
-        r.push_back((int32_t)v);  // a vertex no cell touches keeps its diagonal
-        for (int64_t q = vptr[v]; q < vptr[v + 1]; ++q)
-          for (int k = 0; k < 3; ++k) r.push_back(m->cells[3 * (size_t)vcell[q] + k]);
-        std::sort(r.begin(), r.end());
-        r.erase(std::unique(r.begin(), r.end()), r.end());
-      }
-    });
-    for (int v = 0; v < nv; ++v) sptr[v + 1] = sptr[v] + (int32_t)rows[v].size();
-    scol.resize(sptr[nv]);
-    for (int v = 0; v < nv; ++v) std::copy(rows[v].begin(), rows[v].end(), scol.begin() + sptr[v]);
-  }
+  std::vector<int32_t> sptr, scol;
+  p1_adjacency(nv, nc, m->cells, true, sptr, scol);  // true: a vertex no cell touches keeps its diagonal, its rows are not empty
   const int64_t nnz_s = sptr[nv];
   if (4 * nnz_s > 0x7fffffff || 36 * (int64_t)nc > 0x7fffffff) {
     h->err = "mixed matrix exceeds int32 indices";
@@ -413,22 +363,8 @@ static int qmy_create_impl(pgx_qmy_handle* h, const pgx_mesh* m, const pgx_qmy_p
   std::vector<int32_t> nod(ntot);
   for (int v = 0; v < nv; ++v) nod[v] = nod[(size_t)nv + v] = v;
   MXHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix A{};
-  A.n = ntot;
-  A.rowptr = rowptr.data();
-  A.col = col.data();
-  A.n_nodes = nv;
-  A.node_of_dof = nod.data();
-  A.dim = 2;
-  A.node_coords = m->coords;
-  A.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) A.leaf_nodes = atoi(e);
-  int rc = pgx_nd_create(&A, h->device, (void*)h->st, &h->lu);  // not symmetric: lu_flip_from stays -1
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, nv, nod.data(), 2, m->coords);  // not symmetric: lu_flip_from stays -1
+  if (rc) return rc;
   MXALLOC(h->coords, 2 * (size_t)nv);
   MXALLOC(h->cells, 3 * (size_t)nc);
   MXALLOC(h->Phi0, nv);
@@ -436,19 +372,15 @@ static int qmy_create_impl(pgx_qmy_handle* h, const pgx_mesh* m, const pgx_qmy_p
   MXALLOC(h->mask, nv);
   MXALLOC(h->stash, 36 * (size_t)nc);
   MXALLOC(h->partials2, 2 * MX_RED);
-  MXALLOC(h->rowptr, ntot + 1);
-  MXALLOC(h->col, tot);
   MXALLOC(h->kind, tot);
   MXALLOC(h->Jc, tot);
-  MXALLOC(h->Jv, tot);
   if ((rc = mx_alloc_state(h))) return rc;
+  if ((rc = mx_upload_pattern(h))) return rc;
   MXHIP(hipMemcpy(h->coords, m->coords, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->cells, m->cells, sizeof(int32_t) * 3 * (size_t)nc, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->Phi0, p->Phi0, sizeof(double) * nv, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->phi, p->phi, sizeof(double) * nv, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->mask, hmask.data(), nv, hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->rowptr, rowptr.data(), sizeof(int32_t) * (ntot + 1), hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->col, col.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->kind, kind.data(), tot, hipMemcpyHostToDevice));
   MXHIP(hipMemsetAsync(h->Jc, 0, sizeof(double) * tot, h->st));
   {
@@ -459,23 +391,10 @@ static int qmy_create_impl(pgx_qmy_handle* h, const pgx_mesh* m, const pgx_qmy_p
       return PGX_ENOMEM;
     }
   }
-  {  // constant blocks, once, deterministic: the table is temporary, the stash is the per-step one (18 of its 36 slots)
-    std::vector<void*> tmp;
-    PgxScatter sc_c;
-    const std::string e1 = pgx_scatter_build(d18.data(), (int64_t)18 * nc, tot, tmp, &sc_c);
-    hipError_t e = e1.empty() ? hipSuccess : hipErrorOutOfMemory;
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_qm_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cells, h->coords, h->Q, h->stash);
-      pgx_scatter_run(h->st, sc_c, h->stash, 1.0, 0, h->Jc);
-      e = hipStreamSynchronize(h->st);
-    }
-    for (void* q : tmp) hipFree(q);
-    if (e != hipSuccess) {
-      h->err = std::string("constant Jacobian blocks: ") + (e1.empty() ? hipGetErrorString(e) : e1.c_str());
-      return PGX_EHIP;
-    }
-  }
-  return PGX_OK;
+  // constant blocks, once: the stash is the per-step one (18 of its 36 slots)
+  return mx_scatter_once(h, d18.data(), 18, nc, tot, h->stash, [&](double* stash) {
+    hipLaunchKernelGGL(k_qm_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cells, h->coords, h->Q, stash);
+  }, h->Jc, 0);
 }
 
 extern "C" int pgx_qmy_create(const pgx_mesh* m, const pgx_qmy_problem* p, int device, pgx_qmy_handle** out) {

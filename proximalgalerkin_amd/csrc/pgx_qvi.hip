@@ -8,12 +8,10 @@
 #include "../../include/pgx_qvi.h"
 #include "pgx_mixed.h"
 #include "pgx_scatter.h"
+#include "pgx_tri.h"
 
 #define QV_MAXQ 16
-struct QvQuad {
-  double N[QV_MAXQ][3], w[QV_MAXQ];
-  int nq;
-};
+using QvQuad = TriQuad<QV_MAXQ>;
 
 static thread_local std::string g_qvi_error;
 
@@ -35,28 +33,9 @@ struct pgx_qvi_handle : MixedBase {
 
 extern "C" const char* pgx_qvi_last_error(const pgx_qvi_handle* h) { return h ? h->err.c_str() : g_qvi_error.c_str(); }
 
-struct QvGeom {
-  double G[3][2];  // physical P1 gradients
-  double adet;
-  double X[3][2];
-};
-__device__ inline QvGeom qv_geom(const double* __restrict__ coords, const int32_t* __restrict__ cv) {
-  QvGeom g;
-  for (int a = 0; a < 3; ++a) g.X[a][0] = coords[2 * (size_t)cv[a]], g.X[a][1] = coords[2 * (size_t)cv[a] + 1];
-  const double j00 = g.X[1][0] - g.X[0][0], j10 = g.X[1][1] - g.X[0][1];
-  const double j01 = g.X[2][0] - g.X[0][0], j11 = g.X[2][1] - g.X[0][1];
-  const double det = j00 * j11 - j01 * j10;
-  const double i00 = j11 / det, i01 = -j01 / det, i10 = -j10 / det, i11 = j00 / det;
-  // G[a][d] = sum_k gref[a][k] inv[k][d], gref = [[-1,-1],[1,0],[0,1]]
-  g.G[1][0] = i00, g.G[1][1] = i01;
-  g.G[2][0] = i10, g.G[2][1] = i11;
-  g.G[0][0] = -(i00 + i10), g.G[0][1] = -(i01 + i11);
-  g.adet = fabs(det);
-  return g;
-}
-__device__ inline void qv_space(const QvGeom& g, const double N[3], double* phi0, double* xi) {
-  const double x = N[0] * g.X[0][0] + N[1] * g.X[1][0] + N[2] * g.X[2][0];
-  const double y = N[0] * g.X[0][1] + N[1] * g.X[1][1] + N[2] * g.X[2][1];
+__device__ inline void qv_space(const double X[3][2], const double N[3], double* phi0, double* xi) {
+  const double x = N[0] * X[0][0] + N[1] * X[1][0] + N[2] * X[2][0];
+  const double y = N[0] * X[0][1] + N[1] * X[1][1] + N[2] * X[2][1];
   *phi0 = 1.0 - 2.0 * fmax(fabs(x - 0.5), fabs(y - 0.5));          // thermoforming_dolfinx.py:58
   *xi = sin(3.14159265358979323846 * x) * sin(3.14159265358979323846 * y);  // :59
 }
@@ -68,7 +47,8 @@ __global__ __launch_bounds__(128) void k_qv_residual(int nc, int nv, const int32
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const int32_t* cv = cells + 3 * (size_t)c;
-  const QvGeom g = qv_geom(coords, cv);
+  double X[3][2];
+  const TriGeom g = tri_geom(coords, cv, X);
   double u[3], T[3], p[3], pk[3];
   for (int a = 0; a < 3; ++a) {
     const int v = cv[a];
@@ -94,7 +74,7 @@ __global__ __launch_bounds__(128) void k_qv_residual(int nc, int nv, const int32
     const double s = exp(-pq);
     const double gv = s < knee ? 1.0 - s / knee : 0.0;
     double phi0, xi;
-    qv_space(g, N, &phi0, &xi);
+    qv_space(X, N, &phi0, &xi);
     const double cu = wd * (pq - pkq - alpha * f), cT = wd * (beta * Tq - gv), cp = wd * (uq + s - phi0 - xi * Tq);
     for (int a = 0; a < 3; ++a) Ru[a] += cu * N[a], RT[a] += cT * N[a], Rp[a] += cp * N[a];
   }
@@ -116,7 +96,8 @@ __global__ __launch_bounds__(128) void k_qv_const(int nc, const int32_t* __restr
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const int32_t* cv = cells + 3 * (size_t)c;
-  const QvGeom g = qv_geom(coords, cv);
+  double X[3][2];
+  const TriGeom g = tri_geom(coords, cv, X);
   double Ke[3][3], Me[3][3], Mx[3][3];
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) {
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(128) void k_qv_const(int nc, const int32_t* __restr
     const double* N = Q.N[q];
     const double wd = Q.w[q] * g.adet;
     double phi0, xi;
-    qv_space(g, N, &phi0, &xi);
+    qv_space(X, N, &phi0, &xi);
     for (int a = 0; a < 3; ++a)
       for (int b = 0; b < 3; ++b) Me[a][b] += wd * N[a] * N[b], Mx[a][b] += wd * xi * N[a] * N[b];
   }
@@ -159,7 +140,7 @@ __global__ __launch_bounds__(128) void k_qv_jac_psi(int nc, int nv, const int32_
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const int32_t* cv = cells + 3 * (size_t)c;
-  const QvGeom g = qv_geom(coords, cv);
+  const TriGeom g = tri_geom(coords, cv);
   const double p0 = x[2 * nv + cv[0]], p1 = x[2 * nv + cv[1]], p2 = x[2 * nv + cv[2]];
   double Ce[3][3], De[3][3];
   for (int a = 0; a < 3; ++a)
@@ -193,7 +174,7 @@ __global__ __launch_bounds__(256) void k_qv_h1(int nc, const int32_t* __restrict
   double s = 0.0;
   for (int c = blockIdx.x * 256 + threadIdx.x; c < nc; c += MX_RED * 256) {
     const int32_t* cv = cells + 3 * (size_t)c;
-    const QvGeom g = qv_geom(coords, cv);
+    const TriGeom g = tri_geom(coords, cv);
     double d[3], gd[2] = {0, 0};
     for (int a = 0; a < 3; ++a) {
       d[a] = x[cv[a]] - xk[cv[a]];
@@ -243,16 +224,11 @@ static int qvi_create_impl(pgx_qvi_handle* h, const pgx_mesh* m, const pgx_qvi_p
   const int64_t ntot = 3 * (int64_t)nv;
   h->nv = nv, h->nc = nc, h->ntot = ntot;
   h->beta = p->beta, h->f = p->f, h->knee = p->knee, h->eps_mod = p->eps_mod;
-  h->Q.nq = p->nq;
-  for (int q = 0; q < p->nq; ++q) {
-    const double X = p->qpts[2 * q], Y = p->qpts[2 * q + 1];
-    h->Q.N[q][0] = 1.0 - X - Y, h->Q.N[q][1] = X, h->Q.N[q][2] = Y, h->Q.w[q] = p->qwts[q];
+  h->Q.fill(p->qpts, p->qwts, p->nq);
+  if (const char* e = check_cells(m->cells, 3, nc, nv)) {
+    h->err = e;
+    return PGX_EINVAL;
   }
-  for (size_t k = 0; k < 3 * (size_t)nc; ++k)
-    if (m->cells[k] < 0 || m->cells[k] >= nv) {
-      h->err = "cell vertex out of range";
-      return PGX_EINVAL;
-    }
   std::vector<uint8_t> hmask(nv, 0);
   for (int k = 0; k < p->n_bc; ++k) {
     if (p->bc_dofs[k] < 0 || p->bc_dofs[k] >= nv) {
@@ -262,31 +238,8 @@ static int qvi_create_impl(pgx_qvi_handle* h, const pgx_mesh* m, const pgx_qvi_p
     hmask[p->bc_dofs[k]] = 1;
   }
   // scalar P1 pattern (vertex adjacency incl. self), then 3 x 3 blocks
-  std::vector<int64_t> vptr(nv + 1, 0);
-  for (size_t k = 0; k < 3 * (size_t)nc; ++k) vptr[m->cells[k] + 1]++;
-  for (int v = 0; v < nv; ++v) vptr[v + 1] += vptr[v];
-  std::vector<int32_t> vcell(vptr[nv]);
-  {
-    std::vector<int64_t> fill(vptr.begin(), vptr.end() - 1);
-    for (int c = 0; c < nc; ++c)
-      for (int a = 0; a < 3; ++a) vcell[fill[m->cells[3 * (size_t)c + a]]++] = c;
-  }
-  std::vector<int32_t> sptr(nv + 1, 0), scol;
-  {
-    std::vector<std::vector<int32_t>> rows(nv);
-    mx_par_for(nv, [&](int64_t a, int64_t b) {
-      for (int64_t v = a; v < b; ++v) {
-        auto& r = rows[v];
-        for (int64_t q = vptr[v]; q < vptr[v + 1]; ++q)
-          for (int k = 0; k < 3; ++k) r.push_back(m->cells[3 * (size_t)vcell[q] + k]);
-        std::sort(r.begin(), r.end());
-        r.erase(std::unique(r.begin(), r.end()), r.end());
-      }
-    });
-    for (int v = 0; v < nv; ++v) sptr[v + 1] = sptr[v] + (int32_t)rows[v].size();
-    scol.resize(sptr[nv]);
-    for (int v = 0; v < nv; ++v) std::copy(rows[v].begin(), rows[v].end(), scol.begin() + sptr[v]);
-  }
+  std::vector<int32_t> sptr, scol;
+  p1_adjacency(nv, nc, m->cells, false, sptr, scol);  // false, as this family always had it: a vertex of no cell has empty rows
   const int64_t nnz_s = sptr[nv];
   if (9 * nnz_s > 0x7fffffff) {
     h->err = "mixed matrix exceeds int32 nnz";
@@ -354,37 +307,19 @@ static int qvi_create_impl(pgx_qvi_handle* h, const pgx_mesh* m, const pgx_qvi_p
   std::vector<int32_t> nod(ntot);
   for (int v = 0; v < nv; ++v) nod[v] = nod[(size_t)nv + v] = nod[2 * (size_t)nv + v] = v;
   MXHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix A{};
-  A.n = ntot;
-  A.rowptr = rowptr.data();
-  A.col = col.data();
-  A.n_nodes = nv;
-  A.node_of_dof = nod.data();
-  A.dim = 2;
-  A.node_coords = m->coords;
-  A.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) A.leaf_nodes = atoi(e);
-  int rc = pgx_nd_create(&A, h->device, (void*)h->st, &h->lu);
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, nv, nod.data(), 2, m->coords);
+  if (rc) return rc;
   MXALLOC(h->coords, 2 * (size_t)nv);
   MXALLOC(h->cells, 3 * (size_t)nc);
   MXALLOC(h->mask, nv);
   MXALLOC(h->stash, 18 * (size_t)nc);
-  MXALLOC(h->rowptr, ntot + 1);
-  MXALLOC(h->col, tot);
   MXALLOC(h->kind, tot);
   MXALLOC(h->Jc, tot);
-  MXALLOC(h->Jv, tot);
   if ((rc = mx_alloc_state(h))) return rc;
+  if ((rc = mx_upload_pattern(h))) return rc;
   MXHIP(hipMemcpy(h->coords, m->coords, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->cells, m->cells, sizeof(int32_t) * 3 * (size_t)nc, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->mask, hmask.data(), nv, hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->rowptr, rowptr.data(), sizeof(int32_t) * (ntot + 1), hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->col, col.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->kind, kind.data(), tot, hipMemcpyHostToDevice));
   MXHIP(hipMemsetAsync(h->Jc, 0, sizeof(double) * tot, h->st));
   {
@@ -395,25 +330,10 @@ static int qvi_create_impl(pgx_qvi_handle* h, const pgx_mesh* m, const pgx_qvi_p
       return PGX_ENOMEM;
     }
   }
-  {  // constant blocks, once, deterministic: table and stash are temporary
-    std::vector<void*> tmp;
-    PgxScatter sc_c;
-    std::string e1 = pgx_scatter_build(d45.data(), (int64_t)45 * nc, tot, tmp, &sc_c);
-    double* st45 = nullptr;
-    hipError_t e = e1.empty() ? hipMalloc((void**)&st45, sizeof(double) * 45 * (size_t)nc) : hipErrorOutOfMemory;
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_qv_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cells, h->coords, h->beta, h->Q, st45);
-      pgx_scatter_run(h->st, sc_c, st45, 1.0, 0, h->Jc);
-      e = hipStreamSynchronize(h->st);
-    }
-    if (st45) hipFree(st45);
-    for (void* q : tmp) hipFree(q);
-    if (e != hipSuccess) {
-      h->err = std::string("constant Jacobian blocks: ") + (e1.empty() ? hipGetErrorString(e) : e1.c_str());
-      return PGX_EHIP;
-    }
-  }
-  return PGX_OK;
+  // constant blocks, once
+  return mx_scatter_once(h, d45.data(), 45, nc, tot, nullptr, [&](double* stash) {
+    hipLaunchKernelGGL(k_qv_const, dim3((nc + 127) / 128), dim3(128), 0, h->st, nc, h->cells, h->coords, h->beta, h->Q, stash);
+  }, h->Jc, 0);
 }
 
 extern "C" int pgx_qvi_create(const pgx_mesh* m, const pgx_qvi_problem* p, int device, pgx_qvi_handle** out) {

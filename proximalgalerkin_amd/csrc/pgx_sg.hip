@@ -502,6 +502,7 @@ void pgx_sg_handle::jacobian_dev(const double* xin) {
 template <int NPC, int NPF>
 static int sg_create_impl(pgx_sg_handle* h, const pgx_sg_mesh* m, const pgx_sg_problem* p, pgx_comm* comm) {
   constexpr int ND = 3 * NPC, NE = ND * ND, NF2 = NPF * NPF, NFS = 2 * NF2 + NPF;  // cell dofs, cell slots, facet block, facet slots
+  static_assert(ND <= PAT_MAX_ENTITY_DOFS && 2 * NPF <= PAT_MAX_ENTITY_DOFS, "an entity's dofs must fit the pattern builder's buffer");
   const int nv = m->n_vertices, nc = m->n_cells, nf = m->n_facets;
   h->npc = NPC, h->npf = NPF;
   if ((double)NE * nc * (sizeof(double) + sizeof(int32_t)) > 96e9) {  // stash + destination table of the one-pass constant-block assembly
@@ -537,11 +538,10 @@ static int sg_create_impl(pgx_sg_handle* h, const pgx_sg_mesh* m, const pgx_sg_p
     const int d = (NPF == 4) ? 1 : (NPF == 9 ? 2 : 0);
     h->Q.g[0] = 0, h->Q.g[1] = d ? d : 1, h->Q.g[2] = d ? d * (d + 1) : 2;
   }
-  for (size_t k = 0; k < NPC * (size_t)nc; ++k)
-    if (m->cells[k] < 0 || m->cells[k] >= nv) {
-      h->err = "cell vertex out of range";
-      return PGX_EINVAL;
-    }
+  if (const char* e = check_cells(m->cells, NPC, nc, nv)) {
+    h->err = e;
+    return PGX_EINVAL;
+  }
   // psi dofs = contact vertices ordered by vertex id
   std::vector<int32_t> v2psi(nv, -1);
   for (size_t k = 0; k < NPF * (size_t)nf; ++k) {
@@ -579,99 +579,17 @@ static int sg_create_impl(pgx_sg_handle* h, const pgx_sg_mesh* m, const pgx_sg_p
   auto facet_dofs = [&](int f, int32_t md[2 * NPF]) {
     for (int a = 0; a < NPF; ++a) md[a] = 2 * nv + m->facets[NPF * (size_t)f + a], md[NPF + a] = nu + fpsi[NPF * (size_t)f + a];
   };
-  std::vector<int64_t> dptr(ntot + 1, 0);
-  for (int c = 0; c < nc; ++c) {
-    int32_t md[ND];
-    cell_dofs(c, md);
-    for (int a = 0; a < ND; ++a) dptr[md[a] + 1]++;
-  }
-  for (int f = 0; f < nf; ++f) {
-    int32_t md[2 * NPF];
-    facet_dofs(f, md);
-    for (int a = 0; a < 2 * NPF; ++a) dptr[md[a] + 1]++;
-  }
-  for (int64_t i = 0; i < ntot; ++i) dptr[i + 1] += dptr[i];
-  std::vector<int64_t> dent(dptr[ntot]);  // entity id: cells [0,nc), facets [nc, nc+nf)
-  {
-    std::vector<int64_t> fill(dptr.begin(), dptr.end() - 1);
-    for (int c = 0; c < nc; ++c) {
-      int32_t md[ND];
-      cell_dofs(c, md);
-      for (int a = 0; a < ND; ++a) dent[fill[md[a]]++] = c;
-    }
-    for (int f = 0; f < nf; ++f) {
-      int32_t md[2 * NPF];
-      facet_dofs(f, md);
-      for (int a = 0; a < 2 * NPF; ++a) dent[fill[md[a]]++] = (int64_t)nc + f;
-    }
-  }
-  auto gather_row = [&](int64_t r, std::vector<int32_t>& tmp) {
-    tmp.clear();
-    for (int64_t q = dptr[r]; q < dptr[r + 1]; ++q) {
-      const int64_t e = dent[q];
-      if (e < nc) {
-        int32_t md[ND];
-        cell_dofs((int)e, md);
-        tmp.insert(tmp.end(), md, md + ND);
-      } else {
-        int32_t md[2 * NPF];
-        facet_dofs((int)(e - nc), md);
-        tmp.insert(tmp.end(), md, md + 2 * NPF);
-      }
-    }
-    std::sort(tmp.begin(), tmp.end());
-    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-  };
+  // pattern over the entity range: cells [0, nc), facets [nc, nc + nf)
   std::vector<int32_t>& rowptr = h->h_rowptr;
   std::vector<int32_t>& col = h->h_col;
-  rowptr.assign(ntot + 1, 0);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    std::vector<int32_t> tmp;
-    for (int64_t r = a; r < b; ++r) {
-      gather_row(r, tmp);
-      rowptr[r + 1] = (int32_t)tmp.size();
-    }
-  });
-  int64_t tot = 0;
-  for (int64_t r = 0; r < ntot; ++r) {
-    tot += rowptr[r + 1];
-    if (tot > 0x7fffffff) {
-      h->err = "mixed matrix exceeds int32 nnz";
-      return PGX_EINVAL;
-    }
-    rowptr[r + 1] = (int32_t)tot;
-  }
-  h->nnz = tot;
-  col.resize(tot);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    std::vector<int32_t> tmp;
-    for (int64_t r = a; r < b; ++r) {
-      gather_row(r, tmp);
-      std::copy(tmp.begin(), tmp.end(), col.begin() + rowptr[r]);
-    }
-  });
-  auto find = [&](int32_t r, int32_t c) -> int32_t {
-    const int32_t* b = col.data() + rowptr[r];
-    const int32_t* e = col.data() + rowptr[r + 1];
-    return (int32_t)(std::lower_bound(b, e, c) - col.data());
-  };
-  std::vector<uint8_t> kind(tot);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    for (int64_t r = a; r < b; ++r)
-      for (int32_t k = rowptr[r]; k < rowptr[r + 1]; ++k) {
-        const int32_t c = col[k];
-        uint8_t t;
-        if (r < nu && c < nu)
-          t = (hmask[r] || hmask[c]) ? ((r == c && hmask[r]) ? 3 : 4) : 0;
-        else if (r < nu)
-          t = hmask[r] ? 4 : 1;
-        else if (c < nu)
-          t = hmask[c] ? 4 : 1;
-        else
-          t = 2;
-        kind[k] = t;
-      }
-  });
+  const PatFind find = pattern_from_entities(ntot, (int64_t)nc + nf, [&](int64_t e, int32_t* md) {
+    if (e < nc) return cell_dofs((int)e, md), ND;
+    return facet_dofs((int)(e - nc), md), 2 * NPF;
+  }, rowptr, col, h->err);
+  if (!find) return PGX_EINVAL;
+  const int64_t tot = h->nnz = rowptr[ntot];
+  std::vector<uint8_t> kind;
+  saddle_kinds(ntot, nu, hmask, rowptr, col, kind);
   // Element partition of a distributed handle (round 4): the cells are cut into `size` slabs of equal count along the longest axis
   // of the mesh and every rank assembles the elasticity blocks of ITS slab only - what DOLFINx does with the owned cells of a
   // distributed mesh (signorini_dolfinx.py:283-291, `kind="mpi"`); ONE all-reduce sums the constant matrix at create time.  What a
@@ -739,22 +657,8 @@ static int sg_create_impl(pgx_sg_handle* h, const pgx_sg_mesh* m, const pgx_sg_p
   for (int k = 0; k < npsi; ++k) nod[(size_t)nu + k] = h->cverts[k];
   // device
   MXHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix A{};
-  A.n = ntot;
-  A.rowptr = rowptr.data();
-  A.col = col.data();
-  A.n_nodes = nv;
-  A.node_of_dof = nod.data();
-  A.dim = 3;
-  A.node_coords = m->coords;
-  A.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) A.leaf_nodes = atoi(e);
-  int rc = comm ? pgx_nd_create_dist(&A, comm, h->device, (void*)h->st, &h->lu) : pgx_nd_create(&A, h->device, (void*)h->st, &h->lu);
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, nv, nod.data(), 3, m->coords, comm);
+  if (rc) return rc;
   // [[alpha A, M_G^T], [-M_G, D(psi)]] with the rows of the latent block negated is the symmetric [[alpha A, M_G^T], [M_G, -D]]
   // (the Dirichlet rows AND columns of u are identity / zero): the LU takes it at half the flops (pgx_mixed.hip mx_lu_factor, pgx_nd.h);
   // PGX_SG_SYM=0 keeps the general LU of the matrix as UFL's derivative gives it (A/B)
@@ -773,12 +677,10 @@ static int sg_create_impl(pgx_sg_handle* h, const pgx_sg_mesh* m, const pgx_sg_p
   MXALLOC(h->mask, nu);
   MXALLOC(h->gbc, nu);
   MXALLOC(h->bg, npsi);
-  MXALLOC(h->rowptr, ntot + 1);
-  MXALLOC(h->col, tot);
   MXALLOC(h->kind, tot);
   MXALLOC(h->Jc, tot);
-  MXALLOC(h->Jv, tot);
   if ((rc = mx_alloc_state(h))) return rc;
+  if ((rc = mx_upload_pattern(h))) return rc;
   {  // diagnostics: every cell of the mesh (a distributed handle evaluates them on its replica of the iterate) and the reference
      // gradients of the cell basis at the cell's own nodes
     h->curved = g_sg_curved != nullptr;
@@ -831,8 +733,6 @@ static int sg_create_impl(pgx_sg_handle* h, const pgx_sg_mesh* m, const pgx_sg_p
   }
   MXHIP(hipMemcpy(h->mask, hmask.data(), nu, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->gbc, hg.data(), sizeof(double) * nu, hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->rowptr, rowptr.data(), sizeof(int32_t) * (ntot + 1), hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->col, col.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->kind, kind.data(), tot, hipMemcpyHostToDevice));
   MXHIP(hipMemsetAsync(h->Jc, 0, sizeof(double) * tot, h->st));
   MXHIP(hipMemsetAsync(h->bg, 0, sizeof(double) * npsi, h->st));

@@ -286,6 +286,7 @@ static void sg2_ref_grads(double X, double Y, double* r) {
 template <int NPC, int NPE>
 static int sg2_create_impl(pgx_sg_handle* h, const pgx_sg_mesh2d* m, const pgx_sg_problem2d* p) {
   constexpr int ND = 2 * NPC, NE = ND * ND, NF2 = NPE * NPE, NFS = 2 * NF2 + NPE;
+  static_assert(ND <= PAT_MAX_ENTITY_DOFS && 2 * NPE <= PAT_MAX_ENTITY_DOFS, "an entity's dofs must fit the pattern builder's buffer");
   constexpr bool quad = NPC == 4 || NPC == 9;
   constexpr int deg = NPE - 1;
   const int nv = m->n_vertices, nc = m->n_cells, nf = m->n_facets;
@@ -313,11 +314,10 @@ static int sg2_create_impl(pgx_sg_handle* h, const pgx_sg_mesh2d* m, const pgx_s
   }
   const int g0 = 0, g1 = quad ? deg : 1, g2 = quad ? deg * (deg + 1) : 2;
   h->vm_g[0] = g0, h->vm_g[1] = g1, h->vm_g[2] = g2, h->vm_g[3] = 0;
-  for (size_t k = 0; k < NPC * (size_t)nc; ++k)
-    if (m->cells[k] < 0 || m->cells[k] >= nv) {
-      h->err = "cell vertex out of range";
-      return PGX_EINVAL;
-    }
+  if (const char* e = check_cells(m->cells, NPC, nc, nv)) {
+    h->err = e;
+    return PGX_EINVAL;
+  }
   // reference positions of the local nodes; every cell must be the affine image of the reference cell (straight-sided triangles with
   // their edge nodes at the midpoints; parallelograms with their nodes on the lattice)
   double ref[NPC][2];
@@ -404,101 +404,18 @@ static int sg2_create_impl(pgx_sg_handle* h, const pgx_sg_mesh2d* m, const pgx_s
   auto facet_dofs = [&](int f, int32_t md[2 * NPE]) {
     for (int a = 0; a < NPE; ++a) md[a] = nv + m->facets[NPE * (size_t)f + a], md[NPE + a] = nu + fpsi[NPE * (size_t)f + a];
   };
-  // pattern: per dof the entities that touch it, then per row the sorted union of their dofs (as the 3-D code)
-  std::vector<int64_t> dptr(ntot + 1, 0);
-  for (int c = 0; c < nc; ++c) {
-    int32_t md[ND];
-    cell_dofs(c, md);
-    for (int a = 0; a < ND; ++a) dptr[md[a] + 1]++;
-  }
-  for (int f = 0; f < nf; ++f) {
-    int32_t md[2 * NPE];
-    facet_dofs(f, md);
-    for (int a = 0; a < 2 * NPE; ++a) dptr[md[a] + 1]++;
-  }
-  for (int64_t i = 0; i < ntot; ++i) dptr[i + 1] += dptr[i];
-  std::vector<int64_t> dent(dptr[ntot]);  // entity id: cells [0,nc), edges [nc, nc+nf)
-  {
-    std::vector<int64_t> fill(dptr.begin(), dptr.end() - 1);
-    for (int c = 0; c < nc; ++c) {
-      int32_t md[ND];
-      cell_dofs(c, md);
-      for (int a = 0; a < ND; ++a) dent[fill[md[a]]++] = c;
-    }
-    for (int f = 0; f < nf; ++f) {
-      int32_t md[2 * NPE];
-      facet_dofs(f, md);
-      for (int a = 0; a < 2 * NPE; ++a) dent[fill[md[a]]++] = (int64_t)nc + f;
-    }
-  }
-  auto gather_row = [&](int64_t r, std::vector<int32_t>& tmp) {
-    tmp.clear();
-    for (int64_t q = dptr[r]; q < dptr[r + 1]; ++q) {
-      const int64_t e = dent[q];
-      if (e < nc) {
-        int32_t md[ND];
-        cell_dofs((int)e, md);
-        tmp.insert(tmp.end(), md, md + ND);
-      } else {
-        int32_t md[2 * NPE];
-        facet_dofs((int)(e - nc), md);
-        tmp.insert(tmp.end(), md, md + 2 * NPE);
-      }
-    }
-    std::sort(tmp.begin(), tmp.end());
-    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-  };
+  // pattern over the entity range: cells [0, nc), edges [nc, nc + nf) (as the 3-D code)
   std::vector<int32_t>& rowptr = h->h_rowptr;
   std::vector<int32_t>& col = h->h_col;
-  rowptr.assign(ntot + 1, 0);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    std::vector<int32_t> tmp;
-    for (int64_t r = a; r < b; ++r) {
-      gather_row(r, tmp);
-      rowptr[r + 1] = (int32_t)tmp.size();
-    }
-  });
-  int64_t tot = 0;
-  for (int64_t r = 0; r < ntot; ++r) {
-    tot += rowptr[r + 1];
-    if (tot > 0x7fffffff) {
-      h->err = "mixed matrix exceeds int32 nnz";
-      return PGX_EINVAL;
-    }
-    rowptr[r + 1] = (int32_t)tot;
-  }
-  h->nnz = tot;
-  col.resize(tot);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    std::vector<int32_t> tmp;
-    for (int64_t r = a; r < b; ++r) {
-      gather_row(r, tmp);
-      std::copy(tmp.begin(), tmp.end(), col.begin() + rowptr[r]);
-    }
-  });
-  auto find = [&](int32_t r, int32_t c) -> int32_t {
-    const int32_t* b = col.data() + rowptr[r];
-    const int32_t* e = col.data() + rowptr[r + 1];
-    return (int32_t)(std::lower_bound(b, e, c) - col.data());
-  };
+  const PatFind find = pattern_from_entities(ntot, (int64_t)nc + nf, [&](int64_t e, int32_t* md) {
+    if (e < nc) return cell_dofs((int)e, md), ND;
+    return facet_dofs((int)(e - nc), md), 2 * NPE;
+  }, rowptr, col, h->err);
+  if (!find) return PGX_EINVAL;
+  const int64_t tot = h->nnz = rowptr[ntot];
   // kind (k_sg_jac_init of pgx_sg.hip): 0 = A slot, 1 = +-M_G slot, 2 = D slot, 3 = BC diagonal, 4 = zeroed by BCs (rows AND columns)
-  std::vector<uint8_t> kind(tot);
-  mx_par_for(ntot, [&](int64_t a, int64_t b) {
-    for (int64_t r = a; r < b; ++r)
-      for (int32_t k = rowptr[r]; k < rowptr[r + 1]; ++k) {
-        const int32_t c = col[k];
-        uint8_t t;
-        if (r < nu && c < nu)
-          t = (hmask[r] || hmask[c]) ? ((r == c && hmask[r]) ? 3 : 4) : 0;
-        else if (r < nu)
-          t = hmask[r] ? 4 : 1;
-        else if (c < nu)
-          t = hmask[c] ? 4 : 1;
-        else
-          t = 2;
-        kind[k] = t;
-      }
-  });
+  std::vector<uint8_t> kind;
+  saddle_kinds(ntot, nu, hmask, rowptr, col, kind);
   // destination tables, slot-major like the stashes the kernels write: table[slot * n_entities + entity]
   if ((double)NE * nc > 2.0e9) {
     h->err = "mesh too large for the one-pass assembly of the elasticity block";
@@ -531,22 +448,8 @@ static int sg2_create_impl(pgx_sg_handle* h, const pgx_sg_mesh2d* m, const pgx_s
   for (int k = 0; k < npsi; ++k) nod[(size_t)nu + k] = h->cverts[k];
   // device
   MXHIP(hipStreamCreate(&h->st));
-  pgx_nd_matrix A{};
-  A.n = ntot;
-  A.rowptr = rowptr.data();
-  A.col = col.data();
-  A.n_nodes = nv;
-  A.node_of_dof = nod.data();
-  A.dim = 2;
-  A.node_coords = m->coords;
-  A.leaf_nodes = 0;
-  if (const char* e = pgx_tune("PGX_ND_LEAF")) A.leaf_nodes = atoi(e);
-  int rc = pgx_nd_create(&A, h->device, (void*)h->st, &h->lu);
-  if (rc) {
-    h->err = std::string("direct solver: ") + pgx_nd_last_error(nullptr);
-    h->lu = nullptr;
-    return rc;
-  }
+  int rc = mx_lu_create(h, nv, nod.data(), 2, m->coords);
+  if (rc) return rc;
   {  // latent rows negated -> symmetric [[alpha A, M_G^T], [M_G, -D]] for the LU, as in 3-D; PGX_SG_SYM=0: the general LU
     const char* e = pgx_tune("PGX_SG_SYM");
     if (!(e && atoi(e) == 0)) {
@@ -561,12 +464,10 @@ static int sg2_create_impl(pgx_sg_handle* h, const pgx_sg_mesh2d* m, const pgx_s
   MXALLOC(h->mask, nu);
   MXALLOC(h->gbc, nu);
   MXALLOC(h->bg, npsi);
-  MXALLOC(h->rowptr, ntot + 1);
-  MXALLOC(h->col, tot);
   MXALLOC(h->kind, tot);
   MXALLOC(h->Jc, tot);
-  MXALLOC(h->Jv, tot);
   if ((rc = mx_alloc_state(h))) return rc;
+  if ((rc = mx_upload_pattern(h))) return rc;
   MXALLOC(h->cells, NPC * (size_t)nc);
   MXALLOC(h->vm_tab, (size_t)NPC * NPC * 2);
   {
@@ -580,8 +481,6 @@ static int sg2_create_impl(pgx_sg_handle* h, const pgx_sg_mesh2d* m, const pgx_s
   MXHIP(hipMemcpy(h->fpsi, fpsi.data(), sizeof(int32_t) * fpsi.size(), hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->mask, hmask.data(), nu, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->gbc, hg.data(), sizeof(double) * nu, hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->rowptr, rowptr.data(), sizeof(int32_t) * (ntot + 1), hipMemcpyHostToDevice));
-  MXHIP(hipMemcpy(h->col, col.data(), sizeof(int32_t) * tot, hipMemcpyHostToDevice));
   MXHIP(hipMemcpy(h->kind, kind.data(), tot, hipMemcpyHostToDevice));
   MXHIP(hipMemsetAsync(h->Jc, 0, sizeof(double) * tot, h->st));
   MXHIP(hipMemsetAsync(h->bg, 0, sizeof(double) * npsi, h->st));
