@@ -26,8 +26,10 @@ def main(argv=None):
     parser.add_argument("--tol", type=float, default=TOL, help="The script's tol: SNES tolerances, and 5 tol stops the loop")
     parser.add_argument("--verbose", "-v", action="store_true", help="Verbose output from the Newton solver")
     parser.add_argument("--result_dir", type=Path, default=Path("output"), help="Directory to store results")
+    parser.add_argument("--linear-solver", choices=("dense", "banded"), default="dense",
+                        help="LU with partial pivoting of the Newton matrix: dense (at most 32768 unknowns) or banded in the folded order")
     parser.add_argument("--profile", type=Path, default=None, nargs="?", const=Path("auto"),
-                        help="Write the timing split of the run to this JSON file (no value: profiles/ex09_nu<nu>_nv<nv>.json)")
+                        help="Write the timing split of the run to this JSON file (no value: profiles/ex09_nu<nu>_nv<nv>[_banded].json)")
     a = parser.parse_args(argv)
     sp = solver_parameters(a.tol)
     if a.verbose:
@@ -35,7 +37,7 @@ def main(argv=None):
     prof = {} if a.profile is not None else None
     t0 = time.perf_counter()
     fields, log = solve_problem(nu=a.nu, nv=a.nv, order=a.order, nq1=a.nq1, scale=a.scale, tol=a.tol, snes_opts=sp, profile=prof,
-                                result_dir=a.result_dir, verbose=True)
+                                result_dir=a.result_dir, verbose=True, linear_solver=a.linear_solver)
     wall = time.perf_counter() - t0
     unknowns = len(fields["u"]) + fields["psi"].size
     print(f"wall time {wall:.2f} s, {unknowns} unknowns, max u {fields['u'].max():.6f}, max |psi| {np.abs(fields['psi']).max():.4f}", flush=True)
@@ -46,12 +48,17 @@ def main(argv=None):
 
         path = a.profile
         if str(path) == "auto":
-            path = Path(__file__).resolve().parents[2] / "profiles" / f"ex09_nu{a.nu}_nv{a.nv}.json"
-        ms = {k: v for k, v in prof.items() if k != "lu"}
+            path = Path(__file__).resolve().parents[2] / "profiles" / f"ex09_nu{a.nu}_nv{a.nv}{'_banded' if a.linear_solver == 'banded' else ''}.json"
+        ms = {k: v for k, v in prof.items() if k not in ("lu", "band")}
         steps = int(log[:, 2].sum())
         out = dict(nu=a.nu, nv=a.nv, order=a.order, nq1=a.nq1, scale=a.scale, unknowns=unknowns, lvpp_iterations=len(log),
                    newton_iterations=steps, wall_s=wall, ms=ms,
-                   lu_factor_share_of_newton=ms["lu_factor"] / ms["newton_total"] if ms["newton_total"] > 0 else None, lu=prof["lu"])
+                   lu_factor_share_of_newton=ms["lu_factor"] / ms["newton_total"] if ms["newton_total"] > 0 else None, lu=prof["lu"],
+                   linear_solver=a.linear_solver)
+        if "band" in prof:  # flops of a band factorisation counted as 2 n kl (kl + ku)
+            b = prof["band"]
+            out["band"] = b
+            out["lu_factor_flops_each"] = 2.0 * b["n"] * b["kl"] * (b["kl"] + b["ku"])
         path.parent.mkdir(parents=True, exist_ok=True)
         path.write_text(json.dumps(out, indent=1) + "\n")
 

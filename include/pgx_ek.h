@@ -10,7 +10,7 @@
  *       R_tau = (u, div_G tau) + phi (psi / sqrt(1 + |psi|^2), tau)
  *   and the Jacobian the true derivative (:61), symmetric as assembled: [[0, B], [B^T, D(psi)]], D_ij = the mass form weighted by
  *   phi (delta_ij / s - psi_i psi_j / s^3), s = sqrt(1 + |psi|^2).  The (u, u) block is structurally zero: NO entry is stored there
- *   (pgx_dn_create asks for no diagonal).
+ *   (neither pgx_dn_create nor pgx_bd_create asks for a diagonal).
  *
  * Surface operators (UFL's on a manifold): the cell map x(X) is the Q_g interpolant of the cell's (g+1)^2 geometry nodes, g in
  * {1, 2, 3}; J = dx/dX (3 x 2), G = J^T J, K = G^-1 J^T (the pseudo-inverse), dS = sqrt(det G), grad_G N = (dN/dX) K,
@@ -32,9 +32,14 @@
  *                            dense LU with partial pivoting of include/pgx_dn.h plus iterative refinement on the exact operator: the
  *                            zero (u, u) block makes node-block elimination without pivoting (pgx_nd.h) unsafe (element growth 1e7
  *                            at 944 unknowns).  More than PGX_DN_MAX_N unknowns are refused at create, the message naming the size.
+ *   pgx_ek_create_banded     the same handle on the BAND LU with partial pivoting of include/pgx_bd.h in the symmetric ordering
+ *                            perm[new] = old (proximalgalerkin_amd.lagrange.band_order_mobius folds the ring flat: kl = ku =
+ *                            38 nv + 22); residual, Jacobian, refinement and every other entry point are shared.  The dense limit
+ *                            does not apply; the band solver's own (PGX_BD_MAX_KL, PGX_BD_MAX_BYTES) do, its message passed through.
  *   pgx_ek_l2_increment_u    sqrt(assemble_scalar((u - u0)^2 dx)) (:88-90, :160-161), a fixed-shape two-stage reduction
  *   pgx_ek_eval_cells        per cell and Q_g interpolation node: u (:84-86, :167), grad_G u (:134-139, :169), psi (:141-142, :170)
- *   pgx_ek_lu_stats          the pgx_dn_stats of the handle's dense LU (of the last factorisation)
+ *   pgx_ek_lu_stats          the pgx_dn_stats of the handle's LU (of the last factorisation), dense or banded
+ *   pgx_ek_band_stats        the pgx_bd_stats of a banded handle; PGX_ESTATE on a dense one
  *   pgx_ek_profile           device-event times of the phases
  *
  * Plain pointers and sizes only.  Returns 0 or a negative PGX_E* code (include/pgx.h); text via pgx_ek_last_error.  No CPU fallback.
@@ -44,6 +49,7 @@
 #include <stdint.h>
 
 #include "pgx.h"
+#include "pgx_bd.h"
 #include "pgx_dn.h"
 #ifdef __cplusplus
 extern "C" {
@@ -65,6 +71,7 @@ typedef struct {
 } pgx_ek_problem;
 
 int pgx_ek_create(const pgx_ek_problem* p, int device, pgx_ek_handle** out);
+int pgx_ek_create_banded(const pgx_ek_problem* p, const int32_t* perm /* [n1 + 3 n2] or NULL */, int device, pgx_ek_handle** out);
 void pgx_ek_destroy(pgx_ek_handle* h);
 const char* pgx_ek_last_error(const pgx_ek_handle* h);
 int pgx_ek_num_dofs(const pgx_ek_handle* h, int64_t* ntot); /* n1 + 3 n2 */
@@ -84,6 +91,7 @@ int pgx_ek_l2_increment_u(pgx_ek_handle* h, double* out);
 /* out [nc][(g+1)^2][7] (host): u, grad_G u (3), psi (3) at the Q_g interpolation nodes of every cell */
 int pgx_ek_eval_cells(pgx_ek_handle* h, double* out);
 int pgx_ek_lu_stats(const pgx_ek_handle* h, pgx_dn_stats* st);
+int pgx_ek_band_stats(const pgx_ek_handle* h, pgx_bd_stats* st);
 /* device-event ms: [0] residual [1] Jacobian fill [2] factorisation [3] solves [4] spmv [5] Newton total */
 int pgx_ek_profile(pgx_ek_handle* h, int enable, double ms[6]);
 

@@ -105,6 +105,19 @@ class pgx_dn_stats(C.Structure):  # include/pgx_dn.h
     ]
 
 
+class pgx_bd_stats(C.Structure):  # include/pgx_bd.h
+    _fields_ = [
+        ("n", C.c_int64),
+        ("kl", C.c_int64),
+        ("ku", C.c_int64),
+        ("bytes", C.c_int64),
+        ("interchanges", C.c_int64),
+        ("min_pivot", C.c_double),
+        ("max_pivot", C.c_double),
+        ("zero_pivots", C.c_int64),
+    ]
+
+
 class pgx_gc_problem(C.Structure):  # include/pgx_gc.h
     _fields_ = [
         ("nq", C.c_int32),
@@ -442,6 +455,15 @@ SYMBOLS = [
     ("pgx_dn_solve", C.c_int, [_H, c_double_p, c_double_p, C.c_int]),
     ("pgx_dn_export_pivots", C.c_int, [_H, c_int32_p]),
     ("pgx_dn_timing", C.c_int, [_H, C.c_int, c_double_p, c_double_p]),
+    # banded direct solver with partial pivoting (include/pgx_bd.h)
+    ("pgx_bd_create", C.c_int, [C.c_int64, c_int32_p, c_int32_p, c_int32_p, C.c_int, C.c_void_p, C.POINTER(_H)]),
+    ("pgx_bd_destroy", None, [_H]),
+    ("pgx_bd_last_error", C.c_char_p, [_H]),
+    ("pgx_bd_get_stats", C.c_int, [_H, C.POINTER(pgx_bd_stats)]),
+    ("pgx_bd_factor", C.c_int, [_H, c_double_p, C.c_int]),
+    ("pgx_bd_solve", C.c_int, [_H, c_double_p, c_double_p, C.c_int]),
+    ("pgx_bd_export_pivots", C.c_int, [_H, c_int32_p]),
+    ("pgx_bd_timing", C.c_int, [_H, C.c_int, c_double_p, c_double_p]),
     # example 06: gradient constraint, vector latent variable (include/pgx_gc.h)
     ("pgx_gc_create", C.c_int, [C.POINTER(pgx_mesh), C.POINTER(pgx_gc_problem), C.c_int, C.POINTER(_H)]),
     ("pgx_gc_create_general", C.c_int, [C.POINTER(pgx_gc_spaces), C.POINTER(pgx_gc_problem), C.c_int, C.POINTER(_H)]),
@@ -550,6 +572,8 @@ SYMBOLS = [
     ("pgx_ek_l2_increment_u", C.c_int, [_H, c_double_p]),
     ("pgx_ek_eval_cells", C.c_int, [_H, c_double_p]),
     ("pgx_ek_lu_stats", C.c_int, [_H, C.POINTER(pgx_dn_stats)]),
+    ("pgx_ek_create_banded", C.c_int, [C.POINTER(pgx_ek_problem), c_int32_p, C.c_int, C.POINTER(_H)]),
+    ("pgx_ek_band_stats", C.c_int, [_H, C.POINTER(pgx_bd_stats)]),
     # interior-point solver for bound-constrained quadratic programmes (include/pgx_ipm.h)
     ("pgx_ipm_create", C.c_int,
      [C.c_int64, C.c_int64, c_int32_p, c_int32_p, c_double_p, C.c_int64, C.c_int32, c_double_p, C.c_int, C.POINTER(_H)]),

@@ -23,6 +23,7 @@
 #include <cstring>
 #include <map>
 
+#include "../../include/pgx_bd.h"
 #include "../../include/pgx_dn.h"
 #include "../../include/pgx_ek.h"
 #include "pgx_mixed.h"
@@ -57,16 +58,18 @@ struct pgx_ek_handle : MixedBase {
   double* stash = nullptr;  // [nc * max(6 * 81, EK_CW)]
   double* d_cells = nullptr;  // [nc][(g+1)^2][7] eval_cells
   PgxScatter sc_res, sc_jac, sc_jac_t, sc_B, sc_Bt, sc_fv;
-  pgx_dn* dn = nullptr;
+  pgx_dn* dn = nullptr;  // the dense LU (pgx_ek_create) or
+  pgx_bd* bd = nullptr;  // the band LU (pgx_ek_create_banded): exactly one of the two
   pgx_ek_handle() : MixedBase("pgx_ek") {}
   void residual_dev(const double* xin, double* Fout) override;
   void jacobian_dev(const double* xin) override;
-  int lin_factor() override { return pgx_dn_factor(dn, Jv, 1); }
-  int lin_solve(const double* rhs, double* out) override { return pgx_dn_solve(dn, rhs, out, 1); }
-  const char* lin_error() const override { return pgx_dn_last_error(dn); }
+  int lin_factor() override { return bd ? pgx_bd_factor(bd, Jv, 1) : pgx_dn_factor(dn, Jv, 1); }
+  int lin_solve(const double* rhs, double* out) override { return bd ? pgx_bd_solve(bd, rhs, out, 1) : pgx_dn_solve(dn, rhs, out, 1); }
+  const char* lin_error() const override { return bd ? pgx_bd_last_error(bd) : pgx_dn_last_error(dn); }
   void lin_release() override {
     if (dn) pgx_dn_destroy(dn);
-    dn = nullptr;
+    if (bd) pgx_bd_destroy(bd);
+    dn = nullptr, bd = nullptr;
   }
 };
 
@@ -374,10 +377,11 @@ static void ek_lagrange(int k, double t, double* val4, double* der4) {
   }
 }
 
-static int ek_create_impl(pgx_ek_handle* h, const pgx_ek_problem* pr) {
+// banded: the band LU of include/pgx_bd.h in the symmetric ordering perm (NULL: as numbered) stands where the dense LU does
+static int ek_create_impl(pgx_ek_handle* h, const pgx_ek_problem* pr, bool banded, const int32_t* perm) {
   const int nc = pr->nc, g = pr->geo_order, g1 = g + 1, ng = g1 * g1, nq = pr->nq, npts = nq * nq, n1 = pr->n1, n2 = pr->n2;
   const int64_t ntot = (int64_t)n1 + 3 * (int64_t)n2;
-  if (ntot > PGX_DN_MAX_N) {
+  if (!banded && ntot > PGX_DN_MAX_N) {
     h->err = "pgx_ek_create: " + std::to_string(ntot) + " unknowns exceed the dense LU's limit of " + std::to_string(PGX_DN_MAX_N);
     return PGX_EINVAL;
   }
@@ -515,10 +519,11 @@ static int ek_create_impl(pgx_ek_handle* h, const pgx_ek_problem* pr) {
     }
   }
   MXHIP(hipStreamCreate(&h->st));
-  int rc = pgx_dn_create(ntot, rowptr.data(), col.data(), h->device, (void*)h->st, &h->dn);
+  int rc = banded ? pgx_bd_create(ntot, rowptr.data(), col.data(), perm, h->device, (void*)h->st, &h->bd)
+                  : pgx_dn_create(ntot, rowptr.data(), col.data(), h->device, (void*)h->st, &h->dn);
   if (rc) {
-    h->err = std::string("direct solver: ") + pgx_dn_last_error(nullptr);
-    h->dn = nullptr;
+    h->err = std::string("direct solver: ") + (banded ? pgx_bd_last_error(nullptr) : pgx_dn_last_error(nullptr));
+    h->dn = nullptr, h->bd = nullptr;
     return rc;
   }
   MXALLOC(h->tab, 1);
@@ -573,13 +578,19 @@ static int ek_create_impl(pgx_ek_handle* h, const pgx_ek_problem* pr) {
   return PGX_OK;
 }
 
-extern "C" int pgx_ek_create(const pgx_ek_problem* p, int device, pgx_ek_handle** out) {
+static int ek_create(const char* fn, const pgx_ek_problem* p, bool banded, const int32_t* perm, int device, pgx_ek_handle** out) {
   if (!p || !out || p->nc < 1 || p->geo_order < 1 || p->geo_order > 3 || !p->cell_nodes || p->n1 < 1 || p->n2 < 1 || !p->cell_dofs_u ||
       !p->cell_dofs_p || p->nq < 1 || p->nq > EK_MAXQ || !p->qpts || !p->qwts || !std::isfinite(p->f) || !std::isfinite(p->phi)) {
-    g_ek_error = "pgx_ek_create: bad arguments (geometry order 1..3 with its nodes, both numberings, a 1-D rule of 1..11 points, finite f and phi)";
+    g_ek_error = std::string(fn) + ": bad arguments (geometry order 1..3 with its nodes, both numberings, a 1-D rule of 1..11 points, finite f and phi)";
     return PGX_EINVAL;
   }
-  return mx_create("pgx_ek_create", g_ek_error, device, out, [&](pgx_ek_handle* h) { return ek_create_impl(h, p); });
+  return mx_create(fn, g_ek_error, device, out, [&](pgx_ek_handle* h) { return ek_create_impl(h, p, banded, perm); });
+}
+extern "C" int pgx_ek_create(const pgx_ek_problem* p, int device, pgx_ek_handle** out) {
+  return ek_create("pgx_ek_create", p, false, nullptr, device, out);
+}
+extern "C" int pgx_ek_create_banded(const pgx_ek_problem* p, const int32_t* perm, int device, pgx_ek_handle** out) {
+  return ek_create("pgx_ek_create_banded", p, true, perm, device, out);
 }
 
 extern "C" int pgx_ek_num_dofs(const pgx_ek_handle* h, int64_t* ntot) {
@@ -622,4 +633,16 @@ extern "C" int pgx_ek_eval_cells(pgx_ek_handle* h, double* out) {
   MXHIP(hipGetLastError());
   return PGX_OK;
 }
-extern "C" int pgx_ek_lu_stats(const pgx_ek_handle* h, pgx_dn_stats* st) { return h && h->dn ? pgx_dn_get_stats(h->dn, st) : PGX_EINVAL; }
+extern "C" int pgx_ek_lu_stats(const pgx_ek_handle* h, pgx_dn_stats* st) {
+  if (!h || !st || (!h->dn && !h->bd)) return PGX_EINVAL;
+  if (h->dn) return pgx_dn_get_stats(h->dn, st);
+  pgx_bd_stats b;
+  const int rc = pgx_bd_get_stats(h->bd, &b);
+  if (rc) return rc;
+  st->n = b.n, st->interchanges = b.interchanges, st->min_pivot = b.min_pivot, st->max_pivot = b.max_pivot, st->zero_pivots = b.zero_pivots;
+  return PGX_OK;
+}
+extern "C" int pgx_ek_band_stats(const pgx_ek_handle* h, pgx_bd_stats* st) {
+  if (!h || !st) return PGX_EINVAL;
+  return h->bd ? pgx_bd_get_stats(h->bd, st) : PGX_ESTATE;  // a dense handle has no band
+}

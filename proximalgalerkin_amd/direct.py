@@ -6,7 +6,8 @@ examples/06_gradient_constraints/gradient_constraint_dolfinx.py:118-121).  No CP
 `solve` raise without a GPU; `device=-1` builds the symbolic structure only (statistics, tests).
 
 `DenseSolver` below mirrors include/pgx_dn.h: a dense LU with partial pivoting for the matrices the sparse solver - which never pivots
-across nodes - cannot take (examples/10_monge_ampere/monge_ampere_dolfinx.py:15-23).
+across nodes - cannot take (examples/10_monge_ampere/monge_ampere_dolfinx.py:15-23).  `BandedSolver` mirrors include/pgx_bd.h: the same
+pivot rule on LAPACK's band storage, for such matrices when an ordering with a narrow band is known (example 09).
 """
 from __future__ import annotations
 
@@ -200,6 +201,78 @@ class DenseSolver:
     def close(self):
         if self._h:
             self._lib.pgx_dn_destroy(self._h)
+            self._h = L._H()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BandedSolver:
+    """Band LU with partial pivoting on the GPU - host mirror of include/pgx_bd.h, with the interface of `DenseSolver`.
+
+    LAPACK's dgbtrf / dgbtrs: the CSR pattern and a symmetric ordering `perm` (perm[new] = old; None: as numbered) are given once,
+    `factor` scatters the values into the band of the permuted matrix ((2 kl + ku + 1) n doubles) and computes P A = L U with
+    dgbtf2's pivot rule, `solve` substitutes and answers in the caller's numbering.  kl <= MAX_KL, at most MAX_BYTES of band."""
+
+    MAX_KL = 960
+    MAX_BYTES = 8 << 30
+    NB = 32
+
+    def __init__(self, indptr, indices, perm=None, device: int = 0):
+        self._lib = L.load()
+        self._h = L._H()
+        self.indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+        self.indices = np.ascontiguousarray(indices, dtype=np.int32)
+        self.perm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+        self.n = len(self.indptr) - 1
+        if self.perm is not None and self.perm.shape != (self.n,):
+            raise ValueError(f"perm has shape {self.perm.shape}, the matrix order is {self.n}")
+        rc = self._lib.pgx_bd_create(self.n, L.iptr(self.indptr), L.iptr(self.indices) if len(self.indices) else None, L.iptr(self.perm),
+                                     int(device), None, C.byref(self._h))
+        if rc:
+            msg = self._lib.pgx_bd_last_error(None)
+            raise L.PgxError(f"pgx_bd_create failed (code {rc}): {msg.decode() if msg else ''}")
+
+    def _check(self, rc, what):
+        if rc:
+            msg = self._lib.pgx_bd_last_error(self._h)
+            raise L.PgxError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+
+    def stats(self) -> dict:
+        st = L.pgx_bd_stats()
+        self._check(self._lib.pgx_bd_get_stats(self._h, C.byref(st)), "pgx_bd_get_stats")
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def factor(self, data):
+        """Raises PgxError when a column has no nonzero pivot candidate (singular matrix); `stats()["zero_pivots"]` counts them."""
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        assert data.shape == (int(self.indptr[-1]),)
+        self._check(self._lib.pgx_bd_factor(self._h, L.dptr(data), 0), "pgx_bd_factor")
+
+    def solve(self, b):
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        assert b.shape == (self.n,)
+        x = np.empty_like(b)
+        self._check(self._lib.pgx_bd_solve(self._h, L.dptr(b), L.dptr(x), 0), "pgx_bd_solve")
+        return x
+
+    def pivots(self) -> np.ndarray:
+        """The pivot vector of the last factorisation in the permuted numbering, 0-based (`scipy.linalg.lapack.dgbtrf`'s ipiv)."""
+        piv = np.zeros(self.n, dtype=np.int32)
+        self._check(self._lib.pgx_bd_export_pivots(self._h, L.iptr(piv)), "pgx_bd_export_pivots")
+        return piv
+
+    def timing(self, enable=True):
+        f, s = C.c_double(), C.c_double()
+        self._check(self._lib.pgx_bd_timing(self._h, int(enable), C.byref(f), C.byref(s)), "pgx_bd_timing")
+        return f.value, s.value
+
+    def close(self):
+        if self._h:
+            self._lib.pgx_bd_destroy(self._h)
             self._h = L._H()
 
     def __del__(self):

@@ -24,7 +24,8 @@ TOL = 1e-5  # :63
 
 
 def solver_parameters(tol: float = TOL) -> dict:
-    """the script's options (:65-77); ksp preonly + pc lu + MUMPS is the dense pivoting LU of include/pgx_dn.h"""
+    """the script's options (:65-77); ksp preonly + pc lu + MUMPS is the dense pivoting LU of include/pgx_dn.h or, with
+    linear_solver="banded", the band LU of include/pgx_bd.h"""
     return {"snes_linesearch_type": "l2", "snes_rtol": tol, "snes_atol": tol, "snes_stol": tol, "snes_max_it": 100}
 
 
@@ -34,12 +35,15 @@ class NotConvergedError(Exception):
 
 class EikonalProblem(_MixedHandle):
     """x = [u | psi0 | psi1 | psi2]: u in Q1, psi in [Q2]^3 (ambient components) on `mesh` (mesh_generation.MobiusMesh), f (:44) and
-    phi (:48) constant, `nq1` Gauss points per direction."""
+    phi (:48) constant, `nq1` Gauss points per direction.  `linear_solver`: "dense" (include/pgx_dn.h, at most 32 768 unknowns) or
+    "banded" (include/pgx_bd.h in the folded order lagrange.band_order_mobius: any strip whose band of 38 nv + 22 the solver admits)."""
 
     _prefix = "pgx_ek"
 
     def __init__(self, mesh: mesh_generation.MobiusMesh, nq1: int = 6, f: float = 1.0, phi: float = 1.0,
-                 petsc_options: dict | None = None, device=0):
+                 petsc_options: dict | None = None, device=0, linear_solver: str = "dense"):
+        if linear_solver not in ("dense", "banded"):
+            raise ValueError(f"linear_solver {linear_solver!r}: 'dense' or 'banded'")
         if not 1 <= int(nq1) <= 11:
             raise NotImplementedError(f"nq1 {nq1}: the example-09 kernels take 1 to 11 points per direction")
         self._lib = lib = _lib.load()
@@ -55,10 +59,16 @@ class EikonalProblem(_MixedHandle):
         pp = _lib.pgx_ek_problem(mesh.num_cells, mesh.order, _lib.dptr(nodes), self.n1, self.n2, _lib.iptr(self.cell_dofs_u),
                                  _lib.iptr(self.cell_dofs_p), self.nq1, _lib.dptr(t), _lib.dptr(w), float(f), float(phi))
         self._h = C.c_void_p()
-        rc = lib.pgx_ek_create(C.byref(pp), int(device), C.byref(self._h))
+        self.linear_solver = linear_solver
+        if linear_solver == "banded":
+            self.band_perm = lagrange.band_order_mobius(mesh.nu, mesh.nv)
+            rc = lib.pgx_ek_create_banded(C.byref(pp), _lib.iptr(self.band_perm), int(device), C.byref(self._h))
+        else:
+            rc = lib.pgx_ek_create(C.byref(pp), int(device), C.byref(self._h))
         if rc:
             msg = lib.pgx_ek_last_error(None)
-            raise _lib.PgxError(f"pgx_ek_create failed (code {rc}): {msg.decode() if msg else ''}")
+            what = "pgx_ek_create_banded" if linear_solver == "banded" else "pgx_ek_create"
+            raise _lib.PgxError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
         self._opts = _lib.pgx_snes_opts()
         lib.pgx_default_opts(C.byref(self._opts))
         for k, v in (solver_parameters() if petsc_options is None else petsc_options).items():
@@ -88,9 +98,15 @@ class EikonalProblem(_MixedHandle):
         return out
 
     def lu_stats(self):
-        """the dense LU's statistics of the last factorisation (include/pgx_dn.h)"""
+        """the LU's statistics of the last factorisation (include/pgx_dn.h), dense or banded"""
         st = _lib.pgx_dn_stats()
         self._check(self._lib.pgx_ek_lu_stats(self._h, C.byref(st)), "pgx_ek_lu_stats")
+        return {key: getattr(st, key) for key, _ in st._fields_}
+
+    def band_stats(self):
+        """the band LU's statistics (include/pgx_bd.h: n, kl, ku, bytes and the pivoting figures); raises on a dense handle"""
+        st = _lib.pgx_bd_stats()
+        self._check(self._lib.pgx_ek_band_stats(self._h, C.byref(st)), "pgx_ek_band_stats")
         return {key: getattr(st, key) for key, _ in st._fields_}
 
 
@@ -111,14 +127,16 @@ def _write(result_dir: Path, mesh, cells_out):
 
 def solve_problem(nu: int = 64, nv: int = 8, order: int = 3, nq1: int = 6, scale: float = 1.0, tol: float = TOL, f: float = 1.0,
                   phi: float = 1.0, max_lvpp: int = 99, snes_opts: dict | None = None, profile: dict | None = None,
-                  result_dir: Path | None = None, verbose: bool = False, monitor=None, device: int = 0):
+                  result_dir: Path | None = None, verbose: bool = False, monitor=None, device: int = 0,
+                  linear_solver: str = "dense"):
     """The script's body on the handle.  Returns (fields, log): `fields` holds the final u, psi (3, n2), the DG outputs `cells`
     (eval_cells) and the geometry nodes x; log rows are (i, alpha, Newton iterations, converged reason, |delta u|).  Raises
     NotConvergedError where the script's snes_error_if_not_converged (:74) would.  `snes_opts` replaces the script's options; a
-    `profile` dict receives the handle's timing split of the whole run; `monitor(problem, i)` is called after every step (tests)."""
+    `profile` dict receives the handle's timing split of the whole run; `monitor(problem, i)` is called after every step (tests).
+    `linear_solver`: "dense" or "banded" (EikonalProblem)."""
     mesh = mesh_generation.create_mobius_strip(nu, nv, order, scale)
     sp = solver_parameters(tol) if snes_opts is None else snes_opts
-    problem = EikonalProblem(mesh, nq1, f=f, phi=phi, petsc_options=sp, device=device)
+    problem = EikonalProblem(mesh, nq1, f=f, phi=phi, petsc_options=sp, device=device, linear_solver=linear_solver)
     log = []
     try:
         if profile is not None:
@@ -146,6 +164,8 @@ def solve_problem(nu: int = 64, nv: int = 8, order: int = 3, nq1: int = 6, scale
         if profile is not None:
             profile.update(problem.profile(False))
             profile["lu"] = problem.lu_stats()
+            if linear_solver == "banded":
+                profile["band"] = problem.band_stats()
         x = problem.get_state()
         cells_out = problem.eval_cells()
         fields = dict(u=x[:problem.n1].copy(), psi=x[problem.n1:].reshape(3, problem.n2).copy(), cells=cells_out, x=mesh.cell_nodes)

@@ -220,3 +220,16 @@ def numbering_mobius(nu: int, nv: int, k: int):
     seam = I == Lu
     I, J = np.where(seam, 0, I), np.where(seam, k * nv - J, J)
     return Lu * (k * nv + 1), np.ascontiguousarray(J * Lu + I, dtype=np.int32)
+
+
+def band_order_mobius(nu: int, nv: int) -> np.ndarray:
+    """-> perm (perm[new] = old) over x = [u | psi0 | psi1 | psi2] of example 09 (u in Q1, psi in [Q2]^3, `numbering_mobius`) that gives
+    the Newton matrix a narrow band (include/pgx_bd.h).  Numbered around the ring the band would be cyclic because of the seam; folding
+    the ring flat costs a doubled band instead: on the common grid of 2 nu lattice columns (Q1 column I sits at 2 I, Q2 column I at I)
+    column c gets the key min(c, 2 nu - c), and the unknowns are sorted by key, stably.  kl = ku = 38 nv + 22."""
+    nu, nv = int(nu), int(nv)
+    n1, n2 = nu * (nv + 1), 2 * nu * (2 * nv + 1)
+    c1 = 2 * (np.arange(n1) % nu)  # dof J nu + I
+    c2 = np.arange(n2) % (2 * nu)  # dof J (2 nu) + I
+    c = np.concatenate([c1, c2, c2, c2])
+    return np.ascontiguousarray(np.argsort(np.minimum(c, 2 * nu - c), kind="stable"), dtype=np.int32)
